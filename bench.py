@@ -4,23 +4,27 @@
 A "step" = one iteration of cpu/src/cnn.cpp:79-90 on one batch of synthetic 224x224x3 fp32 images already resident
 in HBM: forward, softmax + cross-entropy, backward, [RCCL all-reduce of the flat gradient arena], SGD.
     python bench.py --gpus 1 --steps 20 --warmup 5                      # the reference net, BASELINE configs[1] (the metric's config)
-    python bench.py --config vgg11 | resnet18                           # configs[3] / [4] alone, with their own CPU legs
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full               # ... and everything else the benchmark measures (below)
+    python bench.py --config vgg11 | resnet18 [--full]                  # configs[3] / [4] alone ([--full]: with their own CPU legs)
 `value` is measured through the boundary north_star names: the C++ Layer classes (architectures::Sequential::train_step,
-cnn_amd/host) with their DEFAULT settings; the default command adds the Python driver, the every-tensor-written variant, the
-north-star convolution and a few steps of configs[3] / [4] as extra keys.
+cnn_amd/host) with their DEFAULT settings.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
-Timing protocol (round 4): after the warm-up steps and >= 0.6 s of untimed steps (clock ramp), REPEATS = 7 regions of EXACTLY K steps are
-timed, each between two barriers + device synchronisations; `value` / `ms_per_step` are the MEDIAN region (max over ranks per region),
-`spread` holds the slowest / fastest region.  `reference_loop` is the same workload through the reference's own loop on the unchanged
-Layer API (cpu/src/cnn.cpp:79-90, host-side loss glue).
-Prints ONE JSON line on rank 0 (contract in the task brief) with two extra objects:
+Timing protocol: >= 0.6 s of untimed steps (clock ramp; reference net only), the parameters reset to their seeded initial values,
+the W warm-up steps, then ONE region of EXACTLY K steps, timed between two barriers + device synchronisations (max over ranks);
+`ms_per_step` is that region / K.  --dump-outputs DIR then writes what the last step computed (see dump_outputs); with the same
+arguments the inputs and the steps before it are the same in every run.
+Prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  --full adds, as the round-4
+protocol did: REPEATS = 7 timed regions of K steps (`value` / `ms_per_step` = the MEDIAN region, `spread` = slowest / fastest), and
   roofline     -- the dominant kernel of the step: algorithmic bytes (or FLOPs) per launch / its average duration,
                   measured with HIP events on the launch stream DURING the timed region (only that kernel is
                   bracketed, so the perturbation is two event records per step);
   cpu_baseline -- the CPU oracle (oracle/cnn_oracle.c, a line-by-line port of the reference loop nests) timed on the
-                  host, 1 thread, bounded sample.
-plus conv_ns: the north-star Conv2d forward shape (3x3, 64->128, 112x112, batch 256) against the fp32-MFMA peak.
+                  host, 1 thread, bounded sample;
+  the extra legs -- the Python driver, the every-tensor-written variant, `reference_loop` (the same workload through the reference's
+                  own loop on the unchanged Layer API, cpu/src/cnn.cpp:79-90, host-side loss glue), `without_input_gradient`;
+  conv_ns      -- the north-star Conv2d forward shape (3x3, 64->128, 112x112, batch 256) against the fp32-MFMA peak;
+  stacks       -- a few steps of configs[3] / [4]; at N > 1 the exchange figures; --staged-input, --breakdown.
 """
 import argparse
 import json
@@ -356,9 +360,10 @@ def init_comm(capi, torch, dist, world, rank):
 
 
 def make_runner(config, api, batch, torch, capi, world, rank, comm, pool_block=True):
-    """-> dict(step, flush, loss, ...): one train step (cnn.cpp:79-90) of a BASELINE workload on a device-resident synthetic
-    batch.  api "layer" (default, what `value` is measured through): the C++ Layer API -- architectures::Sequential::train_step
-    (cnn_amd/host) -> C ABI -- with its default settings; api "pynet": the Python driver -> C ABI (reference net only)."""
+    """-> dict(step, flush, loss, reset, outputs, ...): one train step (cnn.cpp:79-90) of a BASELINE workload on a device-resident
+    synthetic batch; reset() puts the seeded initial parameters back, outputs() is what --dump-outputs writes.  api "layer" (default,
+    what `value` is measured through): the C++ Layer API -- architectures::Sequential::train_step (cnn_amd/host) -> C ABI -- with its
+    default settings; api "pynet": the Python driver -> C ABI (reference net only)."""
     import numpy as np
 
     from cnn_amd import stacks
@@ -375,10 +380,16 @@ def make_runner(config, api, batch, torch, capi, world, rank, comm, pool_block=T
         # defer_input_grad: conv_layer_1's data gradient (no consumer) is launched one forward pass later on a second stream;
         # flush() launches a pending one, so the timed region contains exactly K of them (cnn_amd/pynet.py)
         net = AlexNetHip(B, 3, defer_input_grad=True, fuse_pool=pool_block)
-        net.load_params((rs.standard_normal(net.n_params) * 0.1).astype(np.float32))
+        p0 = (rs.standard_normal(net.n_params) * 0.1).astype(np.float32)
+        net.load_params(p0)
         handle = comm if world > 1 else None
+
+        def loss():
+            return float(net.loss_sum.item()) / B
+
         return dict(step=lambda: net.train_step(x, labels, lr, handle, world), flush=net.flush, B=B, n_params=net.n_params,
-                    loss=lambda: float(net.loss_sum.item()) / B, keep=(net, x, labels), close=lambda: None, params=None,
+                    loss=loss, keep=(net, x, labels), close=lambda: None, params=None, reset=lambda: net.load_params(p0),
+                    outputs=lambda: dict(params=net.params.cpu().numpy(), grads=net.grads.cpu().numpy(), loss=np.array([loss()], np.float32)),
                     api="python driver (cnn_amd/pynet.py) -> C ABI; first block pool-fused, conv_layer_1 data gradient deferred")
     from cnn_amd import hostapi
 
@@ -386,11 +397,12 @@ def make_runner(config, api, batch, torch, capi, world, rank, comm, pool_block=T
     lib.cnnh_set_fuse_pool_block(1 if pool_block else 0)  # (1 = the library's default)
     if config == "alexnet":
         net = hostapi.HostAlexNet(3)
-        net.set_params((rs.standard_normal(net.n_params) * 0.1).astype(np.float32))
+        p0 = (rs.standard_normal(net.n_params) * 0.1).astype(np.float32)
     else:
         spec = stacks.STACKS[config]()
         net = hostapi.HostSequential(spec)
-        net.set_params(stacks.he_init(net.layout, 1234))
+        p0 = stacks.he_init(net.layout, 1234)
+    net.set_params(p0)
     if comm is not None and api != "pynet":
         net.set_comm(comm.handle, world)  # train_step exchanges the gradient arena (two buckets for the reference net); BatchNorm2D runs as sync-BN
 
@@ -399,7 +411,8 @@ def make_runner(config, api, batch, torch, capi, world, rank, comm, pool_block=T
         lib.cnnh_set_fuse_pool_block(1)
 
     return dict(step=lambda: net.train_step(x, labels, lr), flush=net.flush, B=B, n_params=net.n_params, loss=net.last_loss,
-                keep=(net, x, labels), close=close, params=net.get_params,
+                keep=(net, x, labels), close=close, params=net.get_params, reset=lambda: net.set_params(p0),
+                outputs=lambda: dict(params=net.get_params(), grads=net.get_grads(), loss=np.array([net.last_loss()], np.float32)),
                 api="C++ Layer API (architectures::Sequential::train_step, cnn_amd/host) -> C ABI, default settings"
                     + ("" if pool_block else " except architectures::fuse_pool_block = false (every tensor written by the pass itself)"))
 
@@ -408,13 +421,52 @@ REPEATS = 7          # timed regions of exactly K steps each; `value` is their M
 CLOCK_WARMUP_S = 0.6  # untimed steps in front of the first region until the clocks have ramped (the driver's box was 7 % slower)
 
 
-def measure(run, steps, warmup, sample_every, capi, barrier, time_mod=time, repeats=1, clock_warmup_s=0.0, agree=lambda v: v):
-    """the measurement protocol of one workload: 3 plain + 3 instrumented steps (which kernel dominates?), `warmup` steps [+ steps
-    until `clock_warmup_s` have passed], then `repeats` timed regions of exactly `steps` steps, each between two barriers, with
-    only the dominant kernel event-bracketed -> (list of elapsed_s per region, key, launches, total_ms, table).
+def measure(run, steps, warmup, sample_every, capi, barrier, time_mod=time, repeats=1, clock_warmup_s=0.0, agree=lambda v: v,
+            instrument=True):
+    """the measurement protocol of one workload: [instrument: 3 plain + 3 instrumented steps (which kernel dominates?)], [steps until
+    `clock_warmup_s` have passed], the parameters reset to their seeded initial values, `warmup` steps, then `repeats` timed regions
+    of exactly `steps` steps, each between two barriers [instrument: only the dominant kernel event-bracketed] -> (list of elapsed_s
+    per region, key, launches, total_ms, table); without instrument key / launches / total_ms / table are None / 0 / 0.0 / {}.
+    The reset makes the state after the timed steps depend on the arguments alone (the clock warm-up runs as many steps as fit in
+    its time), so that --dump-outputs of two runs or two builds can be compared.
     agree(v): rank 0's value of v on every rank (identity on one rank) -- every decision that changes HOW MANY steps a rank runs goes
     through it: a step is a collective at N > 1, and ranks that disagree about the count would hang each other"""
     step = run["step"]
+    dominant, table = None, {}
+    if instrument:
+        dominant, table = find_dominant(step, steps, sample_every, capi, barrier, agree)
+    if clock_warmup_s > 0:
+        step()  # (the first call selects / tunes the kernels: not part of the clock warm-up)
+        barrier()
+        t0 = time_mod.perf_counter()
+        while agree(1 if time_mod.perf_counter() - t0 < clock_warmup_s else 0):
+            for _ in range(max(steps, 1)):
+                step()
+            barrier()
+    barrier()
+    run["reset"]()
+    for _ in range(warmup):
+        step()
+    if instrument:
+        capi.kernel_timing(2, dominant, every=sample_every)
+    regions = []
+    for _ in range(repeats):
+        barrier()
+        t0 = time_mod.perf_counter()
+        for _ in range(steps):
+            step()
+        barrier()
+        regions.append(time_mod.perf_counter() - t0)
+    if not instrument:
+        return regions, None, 0, 0.0, table
+    dom = capi.kernel_timing_report()
+    capi.kernel_timing(0)
+    cnt, ms = dom[dominant]
+    return regions, dominant, cnt, ms, table
+
+
+def find_dominant(step, steps, sample_every, capi, barrier, agree):
+    """3 plain + 3 instrumented steps -> (the kernel that dominates the step, the per-kernel table of the instrumented steps)"""
     for _ in range(3):
         step()
     barrier()
@@ -442,28 +494,7 @@ def measure(run, steps, warmup, sample_every, capi, barrier, time_mod=time, repe
             cnt, ms = rep.get(key, (0, 0.0))
             in_situ[key] = ms / cnt if cnt else 0.0
         dominant = max(in_situ.items(), key=lambda kv: kv[1])[0]
-    for _ in range(warmup):
-        step()
-    if clock_warmup_s > 0:
-        barrier()
-        t0 = time_mod.perf_counter()
-        while agree(1 if time_mod.perf_counter() - t0 < clock_warmup_s else 0):
-            for _ in range(max(steps, 1)):
-                step()
-            barrier()
-    capi.kernel_timing(2, dominant, every=sample_every)
-    regions = []
-    for _ in range(repeats):
-        barrier()
-        t0 = time_mod.perf_counter()
-        for _ in range(steps):
-            step()
-        barrier()
-        regions.append(time_mod.perf_counter() - t0)
-    dom = capi.kernel_timing_report()
-    capi.kernel_timing(0)
-    cnt, ms = dom[dominant]
-    return regions, dominant, cnt, ms, table
+    return dominant, table
 
 
 def median(v):
@@ -587,6 +618,23 @@ WORKLOADS = {
 }
 
 
+DUMP_MAX_VALUES = 1 << 22  # per array (16 MiB of float32): parameters + gradients of the largest stack stay under 64 MiB in all
+
+
+def dump_outputs(outputs, out_dir):
+    """--dump-outputs: what a caller of the timed path receives after its last step -- the parameters after the SGD update, the
+    gradients of that step, the mean loss -- as <out_dir>/<name>.npy, float32.  An array longer than DUMP_MAX_VALUES is written as
+    its values at a fixed, seeded set of DUMP_MAX_VALUES indices (ascending; the same set for every run of the same configuration)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in outputs.items():
+        a = np.ascontiguousarray(a, dtype=np.float32).ravel()
+        if a.size > DUMP_MAX_VALUES:
+            a = a[np.sort(np.random.RandomState(0).choice(a.size, DUMP_MAX_VALUES, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -611,9 +659,16 @@ def main():
                     help="also time the reference net with every batch coming from (pinned) HOST memory through cnn_batch_stager_* "
                          "-- the PCIe-inclusive rate, reported beside `value`, never as it")
     ap.add_argument("--repeats", type=int, default=None,
-                    help=f"timed regions of --steps steps each; value = their median (default {REPEATS}; 3 for the stacks)")
-    ap.add_argument("--breakdown", action="store_true", help="also print the per-kernel table to stderr")
+                    help=f"timed regions of --steps steps each; value = their median (default 1; with --full {REPEATS}, 3 for the stacks)")
+    ap.add_argument("--breakdown", action="store_true", help="(with --full) also print the per-kernel table to stderr")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the median of several timed regions, the dominant kernel's roofline, the extra "
+                         "legs, conv_ns, the stacks, the CPU baseline, the exchange figures at N > 1, --staged-input and --breakdown")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (parameters, gradients, loss) as DIR/<name>.npy")
     args = ap.parse_args()
+    if (args.staged_input or args.breakdown) and not args.full:
+        ap.error("--staged-input and --breakdown are part of --full")
     small = args.config == "alexnet"
     if args.steps is None:
         args.steps = 100 if small else 10
@@ -624,7 +679,7 @@ def main():
         raise SystemExit("--api pynet drives the reference net only; the stacks run through the C++ Layer API")
 
     rccl_log = None
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.one_rank_comm:
+    if args.full and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.one_rank_comm):
         # RCCL's own account of what it set up (version, channels, rings / trees): INFO-level init lines of this process into a file, an
         # excerpt of rank 0's goes into the JSON line.  Set BEFORE torch (and with it librccl) is loaded; init-time logging only, the
         # steady state is not touched.
@@ -675,11 +730,11 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # untimed: three plain + three instrumented steps to find the dominant kernel, then the warm-up; timed region: exactly K
-    # steps, only the dominant kernel event-bracketed (every 4th launch of it for the 0.45 ms net: the event pair around a
-    # kernel costs its stream two ~6 us bubbles -- measured 13 us per step)
+    # untimed: [--full: three plain + three instrumented steps to find the dominant kernel], the clock warm-up, the warm-up; timed
+    # region: exactly K steps [--full: REPEATS regions, only the dominant kernel event-bracketed (every 4th launch of it for the
+    # 0.45 ms net: the event pair around a kernel costs its stream two ~6 us bubbles -- measured 13 us per step)]
     every = 4 if small else 1
-    repeats = args.repeats or (REPEATS if small else 3)
+    repeats = args.repeats or ((REPEATS if small else 3) if args.full else 1)
     def agree(v):  # rank 0's decision on every rank (see measure())
         if world == 1:
             return v
@@ -688,13 +743,17 @@ def main():
         return int(t.item())
 
     regions, dominant, cnt, ms, table = measure(run, args.steps, args.warmup, every, capi, barrier, repeats=repeats,
-                                                clock_warmup_s=CLOCK_WARMUP_S if small else 0.0, agree=agree)
+                                                clock_warmup_s=CLOCK_WARMUP_S if small else 0.0, agree=agree, instrument=args.full)
     if world > 1:  # every region's time is the MAX over the ranks
         t = torch.tensor(regions, device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         regions = [float(v) for v in t.tolist()]
     elapsed = median(regions)  # `value` / `ms_per_step`: the median region of exactly K steps
-    if comm_info is not None and api != "pynet":
+    loss = run["loss"]()
+    assert np.isfinite(loss), "training diverged: loss is not finite"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(run["outputs"](), args.dump_outputs)
+    if args.full and comm_info is not None and api != "pynet":
         # how much of the gradient exchange is EXPOSED: the compute stream's wait for the communication stream at the end of the backward
         # walk (Sequential::backward / allreduce_gradients bracket it as "span:exchange_wait"), sampled in K more (untimed) steps on every
         # rank; the step's all-reduce kernels themselves run on the communication stream under the backward pass
@@ -711,9 +770,7 @@ def main():
         # (-1: this workload's step has no such wait -- the reference net's fused tail runs its second bucket ON the compute stream)
         comm_info["exchange_exposed_us"] = round(float(exposed.item()), 1) if float(exposed.item()) >= 0 else None
         comm_info["exchange_exposed_note"] = "max over ranks of the mean compute-stream wait for the exchange per step (HIP events around the wait)"
-    loss = run["loss"]()
-    assert np.isfinite(loss), "training diverged: loss is not finite"
-    if world > 1 and run["params"] is not None:
+    if args.full and world > 1 and run["params"] is not None:
         # replicas start identical and apply identical reduced gradients: after ALL the steps above their parameters must be the same
         # bits on every rank; a digest per rank, gathered and compared
         import hashlib
@@ -731,12 +788,12 @@ def main():
         if len(set(digests)) != 1:
             comm_info["param_digests_per_rank"] = [f"{d:014x}" for d in digests]
             print(f"bench.py: replicas diverged: parameter digests per rank {digests}", file=sys.stderr)
-    if comm_info is not None and not capi.load().cnn_amd_measure_build():
+    if args.full and comm_info is not None and not capi.load().cnn_amd_measure_build():
         # (the step without its all-reduce calls computes wrong results: that switch exists only in the measurement build of the library,
         # `make -C cnn_amd/csrc measure` + CNN_AMD_LIB=cnn_amd/lib/libcnn_amd_measure.so; the product library refuses it)
         comm_info["exchange_cost_us_per_step"] = None
         comm_info["exchange_cost_note"] = "needs the measurement build of the library (DP_SKIP_EXCHANGE is not in libcnn_amd.so); exchange_exposed_us is measured by the product library"
-    elif comm_info is not None:
+    elif args.full and comm_info is not None:
         # what the exchange COSTS the step: K more steps with and K without the all-reduce calls (DP_SKIP_EXCHANGE on every rank; everything
         # else -- buckets, events, the 1/N scale -- unchanged), back to back, max over ranks.  Behind the digest check: the replicas diverge here.
         pair = []
@@ -784,8 +841,8 @@ def main():
                 "parallelism": f"dp{world}" + (f" (RCCL all-reduce of the {run['n_params']}-float gradient arena per step)" if world > 1 else ""),
                 "driver": run["api"],
             },
-            "roofline": dict(roofline_entry(dominant, cnt, ms, with_traffic=True),
-                             sampled=("every 4th launch" if every == 4 else "every launch") + " in the timed region"),
+            **({"roofline": dict(roofline_entry(dominant, cnt, ms, with_traffic=True),
+                                 sampled=("every 4th launch" if every == 4 else "every launch") + " in the timed region")} if args.full else {}),
             "step_tflops": round(flops_img * B * args.steps / elapsed / 1e12, 2),
             "step_frac_of_mfma_peak": round(flops_img * B * args.steps / elapsed / 1e12 / PEAK_MFMA_F32_TFLOPS, 4),
             "final_loss": round(loss, 5),
@@ -803,14 +860,14 @@ def main():
     run["close"]()
     del run
     torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not small and out is not None:
+    if args.full and rank == 0 and world == 1 and not small and out is not None:
         alone = conv_kernel_alone(dominant, torch, capi)  # (the stacks: the dominant kernel's pass alone, beside the in-situ roofline)
         if alone:
             out["roofline"]["alone"] = alone
 
     if world > 1:
         dist.barrier()
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         if small and api == "layer" and not args.no_extra_legs:
             # the same workload (a) with every tensor written by the pass itself (architectures::fuse_pool_block = false: no lazy
             # re-materialisation, plain backward -> SGD sequence) and (b) through the Python driver over the same C ABI
