@@ -26,6 +26,15 @@ class ConvDesc(C.Structure):
 POOL_MASK_PACKED = 1  # CNN_CONV2D_POOL_MASK_PACKED (include/cnn_amd.h)
 
 
+class SgdOptions(C.Structure):
+    """mirror of cnn_sgd_options"""
+
+    _fields_ = [("lr", C.c_float), ("momentum", C.c_float), ("weight_decay", C.c_float), ("nesterov", C.c_int)]
+
+
+SGD_INLINE_RANGES = 64  # CNN_SGD_INLINE_RANGES
+
+
 _lib = None
 
 # name -> (restype, argtypes); the single source for the "exports every declared symbol" test
@@ -119,6 +128,7 @@ SIGNATURES = {
     "cnn_batchnorm2d_backward_from_sums": (C.c_int, [_P] * 6 + [C.c_float, _P, _P] + [C.c_int] * 4 + [C.c_float, _P]),
     "cnn_sgd_update": (C.c_int, [_P, _P, C.c_size_t, C.c_float, C.c_float, _P]),
     "cnn_sgd_update_keep": (C.c_int, [_P, _P, C.c_size_t, C.c_float, C.c_float, _P, _P]),
+    "cnn_sgd_momentum_update": (C.c_int, [_P, _P, _P, C.c_size_t, C.POINTER(SgdOptions), C.c_float, _P, _P, C.c_size_t, _P, _P]),
     "cnn_stream_wait_event_local": (C.c_int, [_P, _P]),
     "cnn_stream_create_priority": (C.c_int, [C.POINTER(C.c_void_p), C.c_int]),
     "cnn_conv2d_backward_weight_pooled2_sgd_keep": (C.c_int, [_D, _P, _P, _P, _P, _P, _P, C.c_float, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P,
@@ -654,6 +664,27 @@ def prepare_filters(convs, weights, biases, fwd_bufs, dgrad_bufs):
 def sgd_update(params, grads, lr, grad_scale=1.0):
     _need_gpu(params, grads)
     check(load().cnn_sgd_update(_ptr(params), _ptr(grads), params.numel(), float(lr), float(grad_scale), _stream()), "cnn_sgd_update")
+    return params
+
+
+def sgd_momentum_update(params, grads, velocity, lr, momentum=0.0, weight_decay=0.0, nesterov=False, grad_scale=1.0, decay_ranges=(),
+                        previous=None, n=None):
+    """cnn_sgd_momentum_update on device tensors (or views of them); decay_ranges: [(begin, end)] relative to params, ascending.
+    Tables longer than SGD_INLINE_RANGES are uploaded here (a caller that steps repeatedly would keep the device copy)."""
+    import numpy as np
+    import torch
+
+    _need_gpu(params, grads, velocity, previous)
+    n = params.numel() if n is None else int(n)
+    opt = SgdOptions(float(lr), float(momentum), float(weight_decay), 1 if nesterov else 0)
+    table = np.ascontiguousarray(np.asarray(list(decay_ranges), dtype=np.uint32).reshape(-1, 2))
+    n_ranges = table.shape[0]
+    dev = torch.from_numpy(table.view(np.int32).reshape(-1)).to(params.device) if n_ranges > SGD_INLINE_RANGES else None
+    check(load().cnn_sgd_momentum_update(_ptr(params), _ptr(grads), _ptr(velocity), n, C.byref(opt), float(grad_scale),
+                                         table.ctypes.data_as(C.c_void_p) if n_ranges else None, _ptr(dev), n_ranges, _ptr(previous), _stream()),
+          "cnn_sgd_momentum_update")
+    if dev is not None:
+        torch.cuda.current_stream().synchronize()  # (the table must outlive the kernel that reads it)
     return params
 
 

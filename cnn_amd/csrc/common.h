@@ -216,6 +216,36 @@ __device__ __forceinline__ float sgd_one(float p, float g, float lr, float scale
     return p - step;
 }
 
+// SGD with momentum / weight decay / Nesterov on one element (cnn_sgd_momentum_update, include/cnn_amd.h has the formula): the
+// arithmetic of torch.optim.SGD (dampening 0) in sgd_one's manner -- fp32, every product and sum rounded separately.  `decay` = this
+// element is inside a decayed range AND weight_decay != 0.  kMomentum = false: v is neither read nor written, and with decay false
+// the result is sgd_one's bit for bit.
+template <bool kMomentum>
+__device__ __forceinline__ float sgdm_one(float p, float g, float& v, float lr, float momentum, float wd, float scale, bool scaled,
+                                          bool decay, bool nesterov) {
+#pragma clang fp contract(off)
+    const float gs = scaled ? g * scale : g;
+    float d = gs;
+    if (decay) {
+        const float wp = wd * p;
+        d = gs + wp;
+    }
+    float u = d;
+    if (kMomentum) {
+        const float mv = momentum * v;
+        const float vn = mv + d;
+        v = vn;
+        if (nesterov) {
+            const float mvn = momentum * vn;
+            u = d + mvn;
+        } else {
+            u = vn;
+        }
+    }
+    const float step = lr * u;
+    return p - step;
+}
+
 constexpr int kWave = 64;          // CDNA wavefront
 constexpr int kNumXCD = 8;
 

@@ -92,6 +92,104 @@ __global__ __launch_bounds__(kBlock) void sgd_scalar(float* __restrict__ p, cons
     }
 }
 
+// ---- SGD with momentum / weight decay / Nesterov (cnn_sgd_momentum_update; sgdm_one(): common.h) -----------------------------
+// Same shape as sgd_vec: float4 body, the <= 3 trailing elements in workgroup 0, a scalar kernel for unaligned pointers, nullable
+// `keep`.  Reads p, g, v and writes p, v (20 B per element, 24 with keep).  Weight decay applies inside the sorted, disjoint index
+// ranges [begin(k), end(k)) of `r` only: by value in the kernel arguments up to CNN_SGD_INLINE_RANGES of them, a device table beyond.
+// A wave's 64 float4 are 256 consecutive elements: ONE wave-uniform binary search finds the first range that ends behind the wave's
+// first element; a wave that lies wholly inside or outside a range (nearly all of them: ranges are layers' weight blocks) is done
+// with that, the others walk on from there per lane.
+struct SgdmArgs {
+    float lr, momentum, wd, scale;
+    bool scaled, nesterov;
+    int nr;  // number of ranges; 0 when weight_decay == 0
+};
+struct InlineRanges {
+    uint32_t be[2 * CNN_SGD_INLINE_RANGES];
+    __device__ __forceinline__ uint32_t begin(int k) const { return be[2 * k]; }
+    __device__ __forceinline__ uint32_t end(int k) const { return be[2 * k + 1]; }
+};
+struct DeviceRanges {
+    const uint32_t* be;
+    __device__ __forceinline__ uint32_t begin(int k) const { return be[2 * k]; }
+    __device__ __forceinline__ uint32_t end(int k) const { return be[2 * k + 1]; }
+};
+// first range that ends behind element idx (nr: none)
+template <class Ranges>
+__device__ __forceinline__ int first_open_range(const Ranges& r, int nr, uint32_t idx) {
+    int lo = 0, hi = nr;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (r.end(mid) > idx) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+template <class Ranges>
+__device__ __forceinline__ bool in_range_from(const Ranges& r, int nr, int& k, uint32_t idx) {
+    while (k < nr && r.end(k) <= idx) ++k;
+    return k < nr && r.begin(k) <= idx;
+}
+
+template <bool kMomentum, class Ranges>
+__global__ __launch_bounds__(kBlock) void sgdm_vec(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ v,
+                                                   size_t n4, size_t n, const SgdmArgs a, float4* __restrict__ keep, const Ranges r) {
+    if (blockIdx.x == 0 && n4 * 4 + threadIdx.x < n) {
+        float* ps = (float*)p;
+        const float* gs = (const float*)g;
+        float* vs = (float*)v;
+        const size_t i = n4 * 4 + threadIdx.x;
+        int k = a.nr ? first_open_range(r, a.nr, (uint32_t)i) : 0;
+        const bool decay = a.nr && in_range_from(r, a.nr, k, (uint32_t)i);
+        float vel = kMomentum ? vs[i] : 0.f;
+        if (keep) ((float*)keep)[i] = ps[i];
+        ps[i] = sgdm_one<kMomentum>(ps[i], gs[i], vel, a.lr, a.momentum, a.wd, a.scale, a.scaled, decay, a.nesterov);
+        if (kMomentum) vs[i] = vel;
+    }
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (size_t)gridDim.x * kBlock) {
+        // (the streams' loads are issued first: the table search below runs while they are in flight)
+        float4 pv = p[i];
+        const float4 gv = g[i];
+        float4 vv = kMomentum ? v[i] : float4{0.f, 0.f, 0.f, 0.f};
+        unsigned bits = 0;  // bit j: element 4*i + j decays
+        if (a.nr) {
+            const uint32_t e = (uint32_t)(i * 4);
+            const uint32_t wave_first = __builtin_amdgcn_readfirstlane(e);  // (lanes hold ascending i: the first active one is the lowest)
+            const uint64_t wave_end = (uint64_t)wave_first + 4 * kWave;
+            const int k0 = first_open_range(r, a.nr, wave_first);
+            if (k0 < a.nr) {
+                const uint32_t b0 = r.begin(k0);
+                if (b0 <= wave_first && r.end(k0) >= wave_end) {
+                    bits = 15u;
+                } else if (b0 < wave_end) {
+                    int k = k0;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) bits |= in_range_from(r, a.nr, k, e + j) ? (1u << j) : 0u;
+                }
+            }
+        }
+        if (keep) keep[i] = pv;
+        pv.x = sgdm_one<kMomentum>(pv.x, gv.x, vv.x, a.lr, a.momentum, a.wd, a.scale, a.scaled, bits & 1u, a.nesterov);
+        pv.y = sgdm_one<kMomentum>(pv.y, gv.y, vv.y, a.lr, a.momentum, a.wd, a.scale, a.scaled, bits & 2u, a.nesterov);
+        pv.z = sgdm_one<kMomentum>(pv.z, gv.z, vv.z, a.lr, a.momentum, a.wd, a.scale, a.scaled, bits & 4u, a.nesterov);
+        pv.w = sgdm_one<kMomentum>(pv.w, gv.w, vv.w, a.lr, a.momentum, a.wd, a.scale, a.scaled, bits & 8u, a.nesterov);
+        p[i] = pv;
+        if (kMomentum) v[i] = vv;
+    }
+}
+template <bool kMomentum, class Ranges>
+__global__ __launch_bounds__(kBlock) void sgdm_scalar(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ v,
+                                                      size_t begin, size_t n, const SgdmArgs a, float* __restrict__ keep, const Ranges r) {
+    for (size_t i = begin + (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
+        int k = a.nr ? first_open_range(r, a.nr, (uint32_t)i) : 0;
+        const bool decay = a.nr && in_range_from(r, a.nr, k, (uint32_t)i);
+        float vel = kMomentum ? v[i] : 0.f;
+        if (keep) keep[i] = p[i];
+        p[i] = sgdm_one<kMomentum>(p[i], g[i], vel, a.lr, a.momentum, a.wd, a.scale, a.scaled, decay, a.nesterov);
+        if (kMomentum) v[i] = vel;
+    }
+}
+
 // func.cpp:6-12
 __device__ __forceinline__ float clamped_exp(float v) {
     if (v >= 88.f) return FLT_MAX;
@@ -140,6 +238,26 @@ __global__ __launch_bounds__(kBlock) void softmax_xent_kernel(const float* __res
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// one launch of the momentum step (the scalar kernel alone when a pointer is not 16-byte aligned, like cnn_sgd_update_keep)
+template <bool kMomentum, class Ranges>
+int launch_sgdm(float* params, const float* grads, float* velocity, size_t n, const SgdmArgs& a, float* previous, const Ranges& r,
+                hipStream_t s) {
+    const bool vec = aligned16(params) && aligned16(grads) && (!kMomentum || aligned16(velocity)) &&
+                     (previous == nullptr || aligned16(previous)) && n >= 4;
+    if (vec) {
+        const size_t n4 = n / 4;
+        CNN_KLAUNCH(s, "sgdm_vec",
+                    (sgdm_vec<kMomentum, Ranges><<<stream_grid(n4, kBlock), kBlock, 0, s>>>((float4*)params, (const float4*)grads, (float4*)velocity,
+                                                                                         n4, n, a, (float4*)previous, r)),
+                    "n=%zu ranges=%d", n, a.nr);
+    } else {
+        CNN_KLAUNCH(s, "sgdm_scalar",
+                    (sgdm_scalar<kMomentum, Ranges><<<stream_grid(n, kBlock), kBlock, 0, s>>>(params, grads, velocity, 0, n, a, previous, r)),
+                    "tail n=%zu ranges=%d", n, a.nr);
+    }
+    return CNN_AMD_OK;
+}
 
 
 // ---- AlexNet::grad_cam (alexnet.cpp:107-140) on a [B][C][H][W] feature map -------------------------------------------------
@@ -274,6 +392,44 @@ int cnn_sgd_update_keep(float* params, const float* grads, size_t n, float lr, f
                     "tail n=%zu", n - done);
     }
     return CNN_AMD_OK;
+}
+
+int cnn_sgd_momentum_update(float* params, const float* grads, float* velocity, size_t n, const cnn_sgd_options* opt, float grad_scale,
+                            const uint32_t* decay_ranges, const uint32_t* decay_ranges_dev, size_t n_ranges, float* previous,
+                            void* stream) {
+    if (n == 0) return CNN_AMD_OK;
+    CNN_REQUIRE(params && grads && opt, "cnn_sgd_momentum_update: null pointer");
+    CNN_REQUIRE(opt->momentum >= 0.f && opt->weight_decay >= 0.f, "cnn_sgd_momentum_update: momentum=%g weight_decay=%g", (double)opt->momentum,
+                (double)opt->weight_decay);
+    CNN_REQUIRE(velocity || opt->momentum == 0.f, "cnn_sgd_momentum_update: null velocity with momentum=%g", (double)opt->momentum);
+    CNN_REQUIRE(n <= (size_t)0xFFFFFFFFu - 4 * kWave, "cnn_sgd_momentum_update: n=%zu exceeds the 32-bit range table: step the arena in pieces", n);
+    CNN_REQUIRE(n_ranges <= n && (n_ranges == 0 || decay_ranges), "cnn_sgd_momentum_update: null decay_ranges / n_ranges=%zu with n=%zu", n_ranges, n);
+    CNN_REQUIRE(n_ranges <= (size_t)CNN_SGD_INLINE_RANGES || decay_ranges_dev,
+                "cnn_sgd_momentum_update: %zu ranges (more than CNN_SGD_INLINE_RANGES) need decay_ranges_dev", n_ranges);
+    uint32_t prev_end = 0;
+    for (size_t k = 0; k < n_ranges; ++k) {
+        const uint32_t b = decay_ranges[2 * k], e = decay_ranges[2 * k + 1];
+        CNN_REQUIRE(b >= prev_end && b < e && (size_t)e <= n, "cnn_sgd_momentum_update: range %zu = [%u, %u) is empty, unsorted, overlapping or beyond n=%zu", k,
+                    b, e, n);
+        prev_end = e;
+    }
+    hipStream_t s = as_stream(stream);
+    SgdmArgs a;
+    a.lr = opt->lr;
+    a.momentum = opt->momentum;
+    a.wd = opt->weight_decay;
+    a.scale = grad_scale;
+    a.scaled = grad_scale != 1.0f;
+    a.nesterov = opt->nesterov != 0;
+    a.nr = opt->weight_decay != 0.f ? (int)n_ranges : 0;
+    const bool mom = opt->momentum != 0.f;
+    if (a.nr > CNN_SGD_INLINE_RANGES) {
+        const DeviceRanges r{decay_ranges_dev};
+        return mom ? launch_sgdm<true>(params, grads, velocity, n, a, previous, r, s) : launch_sgdm<false>(params, grads, velocity, n, a, previous, r, s);
+    }
+    InlineRanges r;
+    for (int k = 0; k < 2 * CNN_SGD_INLINE_RANGES; ++k) r.be[k] = k < 2 * a.nr ? decay_ranges[k] : 0u;
+    return mom ? launch_sgdm<true>(params, grads, velocity, n, a, previous, r, s) : launch_sgdm<false>(params, grads, velocity, n, a, previous, r, s);
 }
 
 int cnn_softmax_xent(const float* logits, const int32_t* labels, float* probs, float* delta, float* loss_sum, int B,

@@ -9,6 +9,8 @@
 #include <fstream>
 #include <list>
 #include <random>
+#include <utility>
+#include <vector>
 
 #include "data_format.h"
 
@@ -87,6 +89,11 @@ public:
     // ---- additions: flat parameter arena support (one SGD kernel, one all-reduce per step) ----
     virtual size_t param_count() const { return 0; }
     virtual void bind_arena(data_type* params_dev, data_type* grads_dev) {}
+    // addition (Sequential::set_optimizer): the parts of this layer's parameter block that weight decay applies to, as [begin, end)
+    // offsets inside the block, ascending.  Default policy: weights only; bias_and_norm extends it to biases and BatchNorm2D's
+    // gamma / beta.  BatchNorm2D's moving statistics are never decayed.
+    typedef std::vector<std::pair<size_t, size_t> > RangeList;
+    virtual void decay_ranges(bool bias_and_norm, RangeList& out) const {}
 };
 
 class ReLU;
@@ -168,6 +175,9 @@ public:
     // the prepared images of this layer (and of every later one) are written on another stream: the next forward call waits
     void wait_before_forward(void* event) { prep_event = event; }
     size_t param_count() const override { return (size_t)get_params_num(); }
+    void decay_ranges(bool bias_and_norm, RangeList& out) const override {
+        out.emplace_back((size_t)0, bias_and_norm ? param_count() : (size_t)out_channels * params_for_one_kernel);
+    }
     void bind_arena(data_type* params_dev, data_type* grads_dev) override;
     // ---- additions for fuse_pool_block ----
     // alexnet.cpp:97,105: the output of the last forward, also when that pass fused it away (see architectures::fuse_pool_block)
@@ -318,6 +328,9 @@ public:
     void save_weights(std::ofstream& writer) const override;
     void load_weights(std::ifstream& reader) override;
     size_t param_count() const override { return (size_t)in_channels * out_channels + out_channels; }
+    void decay_ranges(bool bias_and_norm, RangeList& out) const override {
+        out.emplace_back((size_t)0, bias_and_norm ? param_count() : (size_t)in_channels * out_channels);
+    }
     void bind_arena(data_type* params_dev, data_type* grads_dev) override;
 };
 
@@ -376,6 +389,9 @@ public:
     void save_weights(std::ofstream& writer) const override;
     void load_weights(std::ifstream& reader) override;
     size_t param_count() const override { return (size_t)4 * out_channels; }
+    void decay_ranges(bool bias_and_norm, RangeList& out) const override {  // gamma, beta -- never moving_mean / moving_var
+        if (bias_and_norm) out.emplace_back((size_t)0, (size_t)2 * out_channels);
+    }
     void bind_arena(data_type* params_dev, data_type* grads_dev) override;
 };
 
@@ -408,7 +424,8 @@ public:
 //   * fusion wiring between neighbouring layers (architectures::fuse_layers / fuse_pool_block);
 //   * filter preparation hoisted out of the per-layer calls (cnn_conv2d_prepare_filters), redone after every parameter change;
 //   * an optional RCCL communicator (set_comm): the batch is then sharded over `world` replicas, BatchNorm2D layers
-//     normalise over the GLOBAL batch (sync-BN) and update_gradients() sums the gradient arena over the replicas first.
+//     normalise over the GLOBAL batch (sync-BN) and update_gradients() sums the gradient arena over the replicas first;
+//   * an optional optimizer (set_optimizer): momentum, weight decay and Nesterov on the arena instead of the reference's w -= lr * g.
 class Sequential {
 public:
     bool print_info = false;
@@ -454,6 +471,21 @@ protected:
     // go out on the communication stream behind an event.  Small arenas (the reference net: 445 KB, latency-bound) stay one call.
     size_t bucket_floats = (size_t)2 << 20;
     void flush_bucket(size_t lo, size_t hi);
+    // ---- optimizer (set_optimizer): the arena's step is cnn_sgd_momentum_update instead of cnn_sgd_update_keep ----
+    bool opt_active = false;           // false: the reference's plain step, every launch as without an optimizer
+    data_type opt_momentum = 0, opt_weight_decay = 0;
+    bool opt_nesterov = false, opt_decay_bias_and_norm = false;
+    data_type* velocity = nullptr;     // n_params floats, allocated (zeroed) by the first set_optimizer()
+    struct DecayTable {                // the decayed index ranges inside arena[lo, hi), relative to lo (begin, end pairs)
+        size_t lo = 0, hi = 0;
+        std::vector<uint32_t> host;
+        uint32_t* dev = nullptr;       // device copy, only for tables of more than CNN_SGD_INLINE_RANGES ranges
+    };
+    DecayTable decay_tables[3];        // the three ranges the container steps: the whole arena, behind the front block, the front block
+    void build_decay_table(DecayTable& t, size_t lo, size_t hi);
+    size_t front_block_params() const;
+    // the SGD step on arena[lo, hi) (parameters, gradients, velocity, snapshot) on `on_stream`, plain or with the optimizer
+    void step_arena(size_t lo, size_t hi, data_type learning_rate, data_type grad_scale, void* on_stream);
     bool exchange_active() const;
     void wire();
     void bind(data_type* p, data_type* g);
@@ -489,6 +521,23 @@ public:
     // re-arranged copies of their filters between update_gradients() calls
     void parameters_changed();
     const std::list<std::shared_ptr<Layer> >& layers() const { return layers_sequence; }
+    // SGD with momentum, weight decay and Nesterov for every step the container takes on its arena (update_gradients, train_step):
+    // v = momentum * v + (g + weight_decay * w);  w -= lr * (nesterov ? g + weight_decay * w + momentum * v : v) -- torch.optim.SGD's
+    // update, formula and rounding in include/cnn_amd.h (cnn_sgd_momentum_update).  Weight decay applies to Conv2D / LinearLayer
+    // weights; decay_bias_and_norm extends it to biases and BatchNorm2D's gamma / beta (never to the moving statistics).  Call it
+    // after finalize(), any number of times: the velocity arena is allocated and zeroed by the first call and kept by later ones.
+    // set_optimizer(0, 0) returns to the reference's plain step.  A train step with an optimizer set steps the front block's
+    // parameters with the arena kernel instead of inside its weight-gradient kernel.  Stand-alone
+    // Layer::update_gradients(lr) stays the plain step.  Under set_comm the velocity is per replica and needs no exchange.
+    void set_optimizer(data_type momentum, data_type weight_decay, bool nesterov = false, bool decay_bias_and_norm = false);
+    bool optimizer_active() const { return opt_active; }
+    data_type* velocity_device() const { return velocity; }  // null before the first set_optimizer()
+    // Optimizer state beside a .model checkpoint (whose format stays the reference's): magic "CNNAOPT1", n_params (uint64), momentum,
+    // weight_decay (float), nesterov, decay_bias_and_norm (uint32), then the velocity arena.  Both return 0 on success.  save: 1 =
+    // cannot write, 4 = no optimizer was ever set.  load: 1 = cannot open, 2 = not such a file / truncated, 3 = written for another
+    // n_params; nothing is changed on failure, on success the file's options are set as by set_optimizer().
+    int save_optimizer_state(const std::filesystem::path& path);
+    int load_optimizer_state(const std::filesystem::path& path);
 
 protected:
     void invalidate_filter_images();  // (the part of parameters_changed() the container's own SGD step needs too)
@@ -507,6 +556,10 @@ public:
     // recent step (-(1/B) * sum log p[label], func.cpp:67,71) -- the only call here that synchronises.
     void train_step(const std::vector<tensor>& input, const int* labels_dev, const data_type learning_rate);
     data_type last_loss();
+    // TEST SUPPORT (tests/test_gpu_optimizer.py's host-stepped reference net; no product path calls it): train_step without its SGD
+    // step, as the plain sequence (forward(), the loss kernel, backward(): no fused loss head, no fused step tail) -- the gradients of the
+    // batch are left in the arena, last_loss() works.
+    void forward_backward(const std::vector<tensor>& input, const int* labels_dev);
     const data_type* last_probs_device() const { return loss_probs.base; }
     // train_step defers the data gradient of a pool-fused first block (no consumer: alexnet.cpp:55 discards it) into the next
     // forward pass.  flush_deferred() launches a still-pending one and orders it before later work on architectures::stream; every
@@ -514,6 +567,7 @@ public:
     // layer's delta tensors through raw device pointers.
     void flush_deferred();
 private:
+    void ensure_loss_buffers(int B, int classes);
     BatchBuffer loss_probs, loss_delta, logits_stage;   // [B][classes] each
     data_type* loss_terms = nullptr;      // [B] log p[label] (fused head) ...
     data_type* loss_sum = nullptr;        // ... or the ordered sum (unfused head); [1]

@@ -110,6 +110,22 @@ void cnnh_net_destroy(void* hv) {
 size_t cnnh_net_num_params(void* hv) { return ((Handle*)hv)->net->num_params(); }
 float* cnnh_net_params_device(void* hv) { return ((Handle*)hv)->net->params_device(); }
 float* cnnh_net_grads_device(void* hv) { return ((Handle*)hv)->net->grads_device(); }
+// Sequential::set_optimizer and its state: the velocity arena (null before the first cnnh_net_set_optimizer) and the state files that go
+// beside a .model checkpoint (status codes: architectures.h)
+void cnnh_net_set_optimizer(void* hv, float momentum, float weight_decay, int nesterov, int decay_bias_and_norm) {
+    ((Handle*)hv)->net->set_optimizer(momentum, weight_decay, nesterov != 0, decay_bias_and_norm != 0);
+}
+float* cnnh_net_velocity_device(void* hv) { return ((Handle*)hv)->net->velocity_device(); }
+int cnnh_net_get_velocity(void* hv, float* host) {  // 1: no optimizer was ever set
+    Handle* h = (Handle*)hv;
+    if (h->net->velocity_device() == nullptr) return 1;
+    h->net->flush_deferred();
+    must(cnn_memcpy_d2h(host, h->net->velocity_device(), sizeof(float) * h->net->num_params(), stream), "cnn_memcpy_d2h");
+    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
+    return 0;
+}
+int cnnh_net_save_optimizer_state(void* hv, const char* path) { return ((Handle*)hv)->net->save_optimizer_state(path); }
+int cnnh_net_load_optimizer_state(void* hv, const char* path) { return ((Handle*)hv)->net->load_optimizer_state(path); }
 void cnnh_set_stream(void* hip_stream) { architectures::stream = hip_stream; }
 void cnnh_set_no_grad(int on) { architectures::no_grad = on != 0; }
 void cnnh_set_fuse_layers(int on) { architectures::fuse_layers = on != 0; }
@@ -197,6 +213,17 @@ void cnnh_net_train_step_device_loss(void* hv, float* x_dev, const int* labels_d
         for (int b = 0; b < B; ++b) views.emplace_back(Tensor3D::device_view(h->in_C, H, W, x_dev + len * b, "input_" + std::to_string(b)));
     }
     h->net->train_step(views, labels_dev, lr);
+}
+// (test support) Sequential::forward_backward: the same iteration WITHOUT its SGD step, as the plain sequence; gradients stay in the arena
+void cnnh_net_forward_backward_device_loss(void* hv, float* x_dev, const int* labels_dev, int B, int H, int W) {
+    Handle* h = (Handle*)hv;
+    auto& views = h->device_inputs[x_dev];
+    if ((int)views.size() != B) {
+        views.clear();
+        const size_t len = (size_t)h->in_C * H * W;
+        for (int b = 0; b < B; ++b) views.emplace_back(Tensor3D::device_view(h->in_C, H, W, x_dev + len * b, "input_" + std::to_string(b)));
+    }
+    h->net->forward_backward(views, labels_dev);
 }
 float cnnh_net_last_loss(void* hv) { return ((Handle*)hv)->net->last_loss(); }
 // the delta with respect to the network INPUT (the first layer's data gradient, conv2d.cpp:168-199; alexnet.cpp:55 discards it) of

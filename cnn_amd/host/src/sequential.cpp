@@ -5,7 +5,9 @@
 // replace, see INTEGRATION.md.)
 #include <algorithm>
 #include <cassert>
+#include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <iostream>
 #include <iterator>
 
@@ -175,6 +177,9 @@ Sequential::~Sequential() {
     }
     layers_sequence.clear();
     if (param_prev) cnn_device_free(param_prev);
+    if (velocity) cnn_device_free(velocity);
+    for (auto& t : decay_tables)
+        if (t.dev) cnn_device_free(t.dev);
     if (defer_stream) cnn_stream_destroy(defer_stream);
     if (ev_defer_done) cnn_event_destroy(ev_defer_done);
     if (ev_tail) cnn_event_destroy(ev_tail);
@@ -442,9 +447,136 @@ void Sequential::update_gradients(const data_type learning_rate, const data_type
             if (auto* c = dynamic_cast<Conv2D*>(layer.get())) c->params_of_last_forward_lost();
             if (auto* bn = dynamic_cast<BatchNorm2D*>(layer.get())) bn->params_of_last_forward_lost();
         }
-    must(cnn_sgd_update_keep(param_arena, grad_arena, n_params, learning_rate, grad_scale, param_prev, stream), "cnn_sgd_update_keep");
+    step_arena(0, n_params, learning_rate, grad_scale, stream);
     invalidate_filter_images();
     params_stepped = true;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// optimizer: SGD with momentum / weight decay / Nesterov on the arena
+void Sequential::build_decay_table(DecayTable& t, size_t lo, size_t hi) {
+    t.lo = lo;
+    t.hi = hi;
+    t.host.clear();
+    size_t idx = 0;
+    Layer::RangeList local;
+    for (const auto& layer : layers_sequence) {
+        const size_t off = layer_offsets[idx++];
+        local.clear();
+        layer->decay_ranges(opt_decay_bias_and_norm, local);
+        for (const auto& r : local) {
+            const size_t b = std::max(off + r.first, lo), e = std::min(off + r.second, hi);
+            if (b >= e) continue;
+            if (!t.host.empty() && t.host.back() == (uint32_t)(b - lo)) t.host.back() = (uint32_t)(e - lo);  // (neighbours merge)
+            else {
+                t.host.push_back((uint32_t)(b - lo));
+                t.host.push_back((uint32_t)(e - lo));
+            }
+        }
+    }
+    if (t.dev) {
+        must(cnn_device_free(t.dev), "cnn_device_free");
+        t.dev = nullptr;
+    }
+    if (t.host.size() / 2 > (size_t)CNN_SGD_INLINE_RANGES) {  // beyond what travels in the kernel arguments: the kernel reads a device copy
+        t.dev = (uint32_t*)dev_alloc(sizeof(uint32_t) * t.host.size());
+        must(cnn_memcpy_h2d(t.dev, t.host.data(), sizeof(uint32_t) * t.host.size(), stream), "cnn_memcpy_h2d");
+        must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
+    }
+}
+
+// the pool-fused front block's convolution owns arena[0, front_block_params()) (wire(): block_conv is the first layer); 0 without one
+size_t Sequential::front_block_params() const { return block_conv != nullptr ? block_conv->param_count() : 0; }
+
+void Sequential::set_optimizer(const data_type momentum, const data_type weight_decay, const bool nesterov, const bool decay_bias_and_norm) {
+    assert(finalized && "set_optimizer works on the flat arena: call finalize() first");
+    assert(momentum >= 0 && weight_decay >= 0);
+    assert(n_params < ((size_t)1 << 32) - 1024 && "set_optimizer: the decay-range table is 32-bit");
+    flush_deferred();  // (a side-stream tail of the previous step may still read the tables rebuilt below)
+    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
+    if (velocity == nullptr) {
+        velocity = (data_type*)dev_alloc(sizeof(data_type) * (n_params ? n_params : 1));
+        must(cnn_memset_zero(velocity, sizeof(data_type) * n_params, stream), "cnn_memset_zero");
+        must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
+    }
+    opt_momentum = momentum;
+    opt_weight_decay = weight_decay;
+    opt_nesterov = nesterov;
+    opt_decay_bias_and_norm = decay_bias_and_norm;
+    opt_active = momentum != 0 || weight_decay != 0;
+    const size_t front = front_block_params();
+    build_decay_table(decay_tables[0], 0, n_params);
+    build_decay_table(decay_tables[1], front, n_params);
+    build_decay_table(decay_tables[2], 0, front);
+}
+
+void Sequential::step_arena(const size_t lo, const size_t hi, const data_type learning_rate, const data_type grad_scale, void* on_stream) {
+    if (hi <= lo) return;
+    if (!opt_active) {  // the reference's w -= lr * g
+        must(cnn_sgd_update_keep(param_arena + lo, grad_arena + lo, hi - lo, learning_rate, grad_scale, param_prev + lo, on_stream),
+             "cnn_sgd_update_keep");
+        return;
+    }
+    const DecayTable* t = nullptr;
+    for (const auto& cand : decay_tables)
+        if (cand.lo == lo && cand.hi == hi) t = &cand;
+    if (t == nullptr) {  // (the container steps the three ranges set_optimizer built tables for, and no other)
+        std::fprintf(stderr, "cnn_amd host: step_arena: no decay table for arena[%zu, %zu)\n", lo, hi);
+        std::abort();
+    }
+    const cnn_sgd_options o{learning_rate, opt_momentum, opt_weight_decay, opt_nesterov ? 1 : 0};
+    must(cnn_sgd_momentum_update(param_arena + lo, grad_arena + lo, velocity + lo, hi - lo, &o, grad_scale, t->host.data(), t->dev,
+                                 t->host.size() / 2, param_prev + lo, on_stream),
+         "cnn_sgd_momentum_update");
+}
+
+namespace {
+struct OptStateHeader {
+    char magic[8];
+    uint64_t n_params;
+    float momentum, weight_decay;
+    uint32_t nesterov, decay_bias_and_norm;
+};
+const char kOptMagic[8] = {'C', 'N', 'N', 'A', 'O', 'P', 'T', '1'};
+}  // namespace
+
+int Sequential::save_optimizer_state(const std::filesystem::path& path) {
+    assert(finalized);
+    if (velocity == nullptr) return 4;
+    flush_deferred();
+    std::vector<data_type> host(n_params);
+    must(cnn_memcpy_d2h(host.data(), velocity, sizeof(data_type) * n_params, stream), "cnn_memcpy_d2h");
+    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
+    OptStateHeader h;
+    std::memcpy(h.magic, kOptMagic, 8);
+    h.n_params = n_params;
+    h.momentum = opt_momentum;
+    h.weight_decay = opt_weight_decay;
+    h.nesterov = opt_nesterov ? 1 : 0;
+    h.decay_bias_and_norm = opt_decay_bias_and_norm ? 1 : 0;
+    std::ofstream writer(path.c_str(), std::ios::binary);
+    writer.write((const char*)&h, sizeof(h));
+    writer.write((const char*)host.data(), sizeof(data_type) * host.size());
+    writer.close();
+    return writer.good() ? 0 : 1;
+}
+
+int Sequential::load_optimizer_state(const std::filesystem::path& path) {
+    assert(finalized);
+    std::ifstream reader(path.c_str(), std::ios::binary);
+    if (!reader.good()) return 1;
+    OptStateHeader h;
+    reader.read((char*)&h, sizeof(h));
+    if (!reader.good() || std::memcmp(h.magic, kOptMagic, 8) != 0) return 2;
+    if (h.n_params != (uint64_t)n_params) return 3;
+    if (!(h.momentum >= 0) || !(h.weight_decay >= 0)) return 2;
+    std::vector<data_type> host(n_params);
+    reader.read((char*)host.data(), sizeof(data_type) * host.size());
+    if ((size_t)reader.gcount() != sizeof(data_type) * host.size()) return 2;  // (nothing has been changed yet: no partial read)
+    set_optimizer(h.momentum, h.weight_decay, h.nesterov != 0, h.decay_bias_and_norm != 0);
+    must(cnn_memcpy_h2d(velocity, host.data(), sizeof(data_type) * n_params, stream), "cnn_memcpy_h2d");
+    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
+    return 0;
 }
 
 // filter images of every convolution behind the pool-fused front block, from the current parameters, on `on_stream`
@@ -485,7 +617,7 @@ bool Sequential::fused_tail(std::vector<tensor>& delta, const data_type learning
         !filters_prepared || layer_offsets.empty() || layer_offsets[0] != 0)
         return false;
     if (cnn_amd_get_option("NO_FUSED_TAIL", nullptr, 0) == 0) return false;  // (A/B switch)
-    const size_t lo = block_conv->param_count();  // the block's convolution owns arena[0, lo)
+    const size_t lo = front_block_params();  // the block's convolution owns arena[0, lo)
     const bool dp = exchange_active();
     const data_type scale = dp ? 1.f / (data_type)comm_world : 1.f;
     if (ev_tail == nullptr) must(cnn_event_create(&ev_tail), "cnn_event_create");
@@ -494,7 +626,8 @@ bool Sequential::fused_tail(std::vector<tensor>& delta, const data_type learning
     // TAIL_BEHIND_BLOCK (single rank, own arena): the later layers' reductions / SGD / filter images do not run under the block's
     // weight gradient but BEHIND it, and the compute stream does not wait for them here: they overlap the next step's first
     // forward kernel, whose successor waits (train_step / flush_deferred)
-    const bool tail_behind = !dp && owns_arena && cnn_amd_get_option("TAIL_BEHIND_BLOCK", nullptr, 0) == 0;
+    // (not with an optimizer set: the block's kernel has no momentum form, its step would be one more launch in front of the side tail)
+    const bool tail_behind = !dp && !opt_active && owns_arena && cnn_amd_get_option("TAIL_BEHIND_BLOCK", nullptr, 0) == 0;
     if (tail_behind) {
         if (ev_side_tail == nullptr) must(cnn_event_create(&ev_side_tail), "cnn_event_create");
         pending_dgrad = block_conv->backward_weight_pooled(delta, /*fused_sgd=*/true, learning_rate, scale);
@@ -505,9 +638,7 @@ bool Sequential::fused_tail(std::vector<tensor>& delta, const data_type learning
         for (auto& layer : layers_sequence)
             if (auto* lin = dynamic_cast<LinearLayer*>(layer.get())) lin->join_pending(side);
         must(cnn_amd_flush_reduces(side), "cnn_amd_flush_reduces");
-        if (n_params > lo)
-            must(cnn_sgd_update_keep(param_arena + lo, grad_arena + lo, n_params - lo, learning_rate, scale, param_prev + lo, side),
-                 "cnn_sgd_update_keep");
+        step_arena(lo, n_params, learning_rate, scale, side);
         prepare_later_filters(side);
         must(cnn_event_record(ev_side_tail, side), "cnn_event_record");
         side_tail_pending = true;
@@ -538,12 +669,12 @@ bool Sequential::fused_tail(std::vector<tensor>& delta, const data_type learning
     if (n_params > lo) {
         // bucket 1 of the exchange: everything behind the block is final ~one weight-gradient kernel before the step ends
         if (dp) must(cnn_allreduce_grads(comm, grad_arena + lo, n_params - lo, side), "cnn_allreduce_grads");
-        must(cnn_sgd_update_keep(param_arena + lo, grad_arena + lo, n_params - lo, learning_rate, scale, param_prev + lo, side),
-             "cnn_sgd_update_keep");
+        step_arena(lo, n_params, learning_rate, scale, side);
     }
     prepare_later_filters(side);
     // compute stream: the block's weight gradient (+ its share of the tail)
-    pending_dgrad = block_conv->backward_weight_pooled(delta, /*fused_sgd=*/!dp, learning_rate, scale);
+    // (with an optimizer set the block's in-kernel step -- plain SGD only -- is not used: the route of the data-parallel branch below)
+    pending_dgrad = block_conv->backward_weight_pooled(delta, /*fused_sgd=*/!dp && !opt_active, learning_rate, scale);
     block_conv->set_delta_computed(input_gradient);
     if (!input_gradient) pending_dgrad.valid = false;  // (architectures::input_gradient: nobody wants d(loss) / d(input image))
     if (dgrad_now && pending_dgrad.valid) {
@@ -552,15 +683,46 @@ bool Sequential::fused_tail(std::vector<tensor>& delta, const data_type learning
         pending_dgrad.valid = false;
         defer_in_flight = true;
     }
-    if (dp) {  // bucket 2: this layer's few floats
-        must(cnn_allreduce_grads(comm, grad_arena, lo, stream), "cnn_allreduce_grads");
-        must(cnn_sgd_update_keep(param_arena, grad_arena, lo, learning_rate, scale, param_prev, stream), "cnn_sgd_update_keep");
+    if (dp || opt_active) {  // bucket 2: this layer's few floats
+        if (dp) must(cnn_allreduce_grads(comm, grad_arena, lo, stream), "cnn_allreduce_grads");
+        step_arena(0, lo, learning_rate, scale, stream);
         block_conv->prepare_own_filters();
     }
     must(cnn_amd_side_stream_join(stream), "cnn_amd_side_stream_join");
     grads_reduced = dp;
     params_stepped = true;  // (filters_prepared stays true: every image above was made from the updated parameters)
     return true;
+}
+
+void Sequential::ensure_loss_buffers(const int B, const int classes) {
+    if (loss_delta.empty() || loss_batch < B) {
+        assert(loss_delta.empty() && "train_step: batch larger than the first call's");
+        loss_probs.allocate(B, classes, 1, 1, "probs");
+        loss_delta.allocate(B, classes, 1, 1, "loss_delta");
+        loss_terms = (data_type*)dev_alloc(sizeof(data_type) * B);
+        loss_sum = (data_type*)dev_alloc(sizeof(data_type));
+        loss_batch = B;
+    }
+}
+
+// train_step without its SGD step, as the plain sequence: forward(), the loss kernel, backward() -- no fused loss head, no fused tail
+void Sequential::forward_backward(const std::vector<tensor>& input, const int* labels_dev) {
+    assert(!input.empty() && labels_dev != nullptr && !layers_sequence.empty());
+    auto* head = dynamic_cast<LinearLayer*>(layers_sequence.back().get());
+    assert(head != nullptr && "forward_backward: the last layer must be a LinearLayer (the logits)");
+    const int B = (int)input.size();
+    const int classes = head->out_features();
+    ensure_loss_buffers(B, classes);
+    const bool was_lazy = lazy_host_sync;
+    lazy_host_sync = true;
+    std::vector<tensor> output = forward(input);
+    lazy_host_sync = was_lazy;
+    const data_type* logits = batch_device_pointer(output, logits_stage, "logits");
+    must(cnn_softmax_xent(logits, labels_dev, loss_probs.base, loss_delta.base, loss_sum, B, classes, stream), "cnn_softmax_xent");
+    loss_in_terms = false;
+    loss_last_B = B;
+    std::vector<tensor> delta(loss_delta.views.begin(), loss_delta.views.begin() + B);
+    backward(delta);
 }
 
 // cnn.cpp:79-90 without leaving the device
@@ -570,14 +732,7 @@ void Sequential::train_step(const std::vector<tensor>& input, const int* labels_
     assert(head != nullptr && "train_step: the last layer must be a LinearLayer (the logits)");
     const int B = (int)input.size();
     const int classes = head->out_features();
-    if (loss_delta.empty() || loss_batch < B) {
-        assert(loss_delta.empty() && "train_step: batch larger than the first call's");
-        loss_probs.allocate(B, classes, 1, 1, "probs");
-        loss_delta.allocate(B, classes, 1, 1, "loss_delta");
-        loss_terms = (data_type*)dev_alloc(sizeof(data_type) * B);
-        loss_sum = (data_type*)dev_alloc(sizeof(data_type));
-        loss_batch = B;
-    }
+    ensure_loss_buffers(B, classes);
     if (print_info) input[0]->print_shape();
     if (finalized && fuse_layers && !filters_prepared) {
         flush_deferred();  // (a full re-preparation rewrites filter images a pending data gradient may read)

@@ -33,6 +33,11 @@ SIGNATURES = {
     "cnnh_net_num_params": (C.c_size_t, [C.c_void_p]),
     "cnnh_net_params_device": (C.c_void_p, [C.c_void_p]),
     "cnnh_net_grads_device": (C.c_void_p, [C.c_void_p]),
+    "cnnh_net_set_optimizer": (None, [C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int]),
+    "cnnh_net_velocity_device": (C.c_void_p, [C.c_void_p]),
+    "cnnh_net_get_velocity": (C.c_int, [C.c_void_p, _F]),
+    "cnnh_net_save_optimizer_state": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "cnnh_net_load_optimizer_state": (C.c_int, [C.c_void_p, C.c_char_p]),
     "cnnh_set_stream": (None, [C.c_void_p]),
     "cnnh_set_no_grad": (None, [C.c_int]),
     "cnnh_set_fuse_layers": (None, [C.c_int]),
@@ -48,6 +53,7 @@ SIGNATURES = {
     "cnnh_net_train_step_device": (C.c_float, [C.c_void_p, C.c_void_p, _I, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int]),
     "cnnh_net_update": (None, [C.c_void_p, C.c_float, C.c_float]),
     "cnnh_net_train_step_device_loss": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float]),
+    "cnnh_net_forward_backward_device_loss": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "cnnh_net_last_loss": (C.c_float, [C.c_void_p]),
     "cnnh_net_flush": (None, [C.c_void_p]),
     "cnnh_net_input_delta": (C.c_int, [C.c_void_p, _F, C.c_size_t]),
@@ -139,6 +145,33 @@ class HostNet:
     def save_checkpoint(self, path):
         self.lib.cnnh_net_save_checkpoint(self.h, str(path).encode())
 
+    def set_optimizer(self, momentum, weight_decay=0.0, nesterov=False, decay_bias_and_norm=False):
+        """Sequential::set_optimizer: SGD with momentum / weight decay / Nesterov for every later step on the arena;
+        set_optimizer(0, 0) returns to the plain step"""
+        self.lib.cnnh_net_set_optimizer(self.h, float(momentum), float(weight_decay), 1 if nesterov else 0, 1 if decay_bias_and_norm else 0)
+
+    def velocity_ptr(self):
+        """device pointer of the velocity arena (n_params floats); None before the first set_optimizer"""
+        return self.lib.cnnh_net_velocity_device(self.h)
+
+    def get_velocity(self):
+        out = np.empty(self.n_params, np.float32)
+        if self.lib.cnnh_net_get_velocity(self.h, _fp(out)) != 0:
+            raise capi.CnnAmdError("get_velocity before set_optimizer")
+        return out
+
+    def save_optimizer_state(self, path):
+        rc = self.lib.cnnh_net_save_optimizer_state(self.h, str(path).encode())
+        if rc != 0:
+            raise capi.CnnAmdError(f"save_optimizer_state({path}): rc={rc}")
+
+    def load_optimizer_state(self, path):
+        rc = self.lib.cnnh_net_load_optimizer_state(self.h, str(path).encode())
+        if rc == 1:
+            raise FileNotFoundError(path)
+        if rc != 0:
+            raise capi.CnnAmdError(f"load_optimizer_state({path}): rc={rc}" + (" (written for another n_params)" if rc == 3 else ""))
+
     def forward_host(self, x):
         x = np.ascontiguousarray(x, dtype=np.float32)
         B, _, H, W = x.shape
@@ -169,6 +202,12 @@ class HostNet:
         B, _, H, W = x_dev.shape
         self.lib.cnnh_net_train_step_device_loss(self.h, C.c_void_p(x_dev.data_ptr()), C.c_void_p(labels_dev.data_ptr()), B, H, W,
                                                  float(lr))
+
+    def forward_backward(self, x_dev, labels_dev):
+        """(test support) Sequential::forward_backward: train_step without its SGD step, as the plain sequence; get_grads() /
+        last_loss() afterwards"""
+        B, _, H, W = x_dev.shape
+        self.lib.cnnh_net_forward_backward_device_loss(self.h, C.c_void_p(x_dev.data_ptr()), C.c_void_p(labels_dev.data_ptr()), B, H, W)
 
     def train_step_ptr(self, x_ptr, labels_dev, B, H, W, lr):
         """train_step on a raw device pointer (e.g. a capi.BatchStager slot)"""

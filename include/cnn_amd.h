@@ -414,6 +414,32 @@ int cnn_sgd_update(float* params, const float* grads, size_t n, float lr, float 
 /* the same step; previous[i] (nullable) receives params[i] as it was before (see cnn_conv2d_backward_weight_pooled2_sgd_keep) */
 int cnn_sgd_update_keep(float* params, const float* grads, size_t n, float lr, float grad_scale, float* previous, void* stream);
 
+/* SGD with momentum, weight decay and Nesterov over a range of the flat arena -- the update of torch.optim.SGD with dampening 0,
+ * in cnn_sgd_update's arithmetic (fp32, every product and sum rounded separately, no FMA).  Per element i:
+ *     gs = grad_scale != 1 ? g * grad_scale : g
+ *     d  = (decays(i) && weight_decay != 0) ? gs + weight_decay * p : gs
+ *     momentum == 0 :  u = d                                     (velocity is neither read nor written, and may be NULL)
+ *     otherwise     :  v' = momentum * v + d ;  u = nesterov ? d + momentum * v' : v'
+ *     p' = p - lr * u
+ * velocity: n floats of state, zero before the first step.  previous (nullable) as in cnn_sgd_update_keep.  With momentum == 0 and
+ * weight_decay == 0 the result equals cnn_sgd_update_keep's bit for bit.
+ * decays(i): weight decay applies inside n_ranges half-open index ranges only -- a layer's weights, not BatchNorm2D's moving
+ * statistics, which share the arena.  decay_ranges is a HOST array of 2 * n_ranges values, begin then end of every range, relative
+ * to the `params` pointer of this call, ascending, non-empty and disjoint, end <= n (checked).  Up to CNN_SGD_INLINE_RANGES ranges
+ * travel in the kernel arguments; beyond that the kernel reads them from decay_ranges_dev, a DEVICE copy of the same array that
+ * the caller keeps (NULL is fine for smaller tables).  n <= 2^32 - 257 per call (the table is 32-bit).
+ * One call is one kernel launch, whatever the number of ranges: 20 bytes per element, 24 with `previous`. */
+typedef struct cnn_sgd_options {
+    float lr;
+    float momentum;     /* >= 0 */
+    float weight_decay; /* >= 0 */
+    int nesterov;       /* 0 / 1 */
+} cnn_sgd_options;
+#define CNN_SGD_INLINE_RANGES 64
+int cnn_sgd_momentum_update(float* params, const float* grads, float* velocity, size_t n, const cnn_sgd_options* opt, float grad_scale,
+                            const uint32_t* decay_ranges, const uint32_t* decay_ranges_dev, size_t n_ranges, float* previous,
+                            void* stream);
+
 /* AlexNet::grad_cam (alexnet.cpp:107-140) from the feature map of the chosen layer, [B][C][H][W] on the device:
  *   weights[b][o] = mean_i feature[b][o][i];  cam[b] = ReLU(sum_o weights[b][o] * feature[b][o]);  cam = (cam - min) / (max - min)
  * with min / max over the whole [B][H][W] tensor (:136-139).  cam: [B][H][W] floats (output).  image (nullable): H*W bytes, the 8-bit
