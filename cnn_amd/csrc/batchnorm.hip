@@ -328,12 +328,14 @@ struct PoolDelta {
     const int32_t* mask;
     const float* pooled;
     int W, PW, PHPW;   // input row length, pooled row length, pooled plane size
-    unsigned wmagic;   // ceil(2^32 / W): hw / W == umulhi(hw, wmagic) for hw < H * W
+    unsigned wmagic;   // ceil(2^32 / W): umulhi(hw, wmagic) is hw / W or one above it -- one correction step (unsigned: h * W <= hw + W < 2^32) makes it exact for every hw < 2^31
 };
 // the four deltas of the aligned slot at element hw (a multiple of 4) of plane `plane` = b * C + c; cbase = c * H * W (the mask holds
 // indices into the SAMPLE, pool2d.cpp:81)
 __device__ inline float4 pool_delta4(const PoolDelta& s, long long plane, int cbase, int hw) {
-    const int h = (int)__umulhi((unsigned)hw, s.wmagic), w = hw - h * s.W;
+    int h = (int)__umulhi((unsigned)hw, s.wmagic);
+    if ((unsigned)h * (unsigned)s.W > (unsigned)hw) --h;
+    const int w = hw - h * s.W;
     const long long wi = plane * s.PHPW + (long long)(h >> 1) * s.PW + (w >> 1);
     const float2 dp = *(const float2*)(s.dpool + wi);
     const int2 mk = *(const int2*)(s.mask + wi);
@@ -343,7 +345,9 @@ __device__ inline float4 pool_delta4(const PoolDelta& s, long long plane, int cb
     return make_float4(m0 == f ? d0 : 0.f, m0 == f + 1 ? d0 : 0.f, m1 == f + 2 ? d1 : 0.f, m1 == f + 3 ? d1 : 0.f);
 }
 __device__ inline float pool_delta1(const PoolDelta& s, long long plane, int cbase, int hw) {
-    const int h = (int)__umulhi((unsigned)hw, s.wmagic), w = hw - h * s.W;
+    int h = (int)__umulhi((unsigned)hw, s.wmagic);
+    if ((unsigned)h * (unsigned)s.W > (unsigned)hw) --h;
+    const int w = hw - h * s.W;
     const long long wi = plane * s.PHPW + (long long)(h >> 1) * s.PW + (w >> 1);
     const float d = s.pooled[wi] <= 0.f ? 0.f : s.dpool[wi];
     return (s.mask[wi] & 0x7fffffff) == cbase + hw ? d : 0.f;
