@@ -35,6 +35,17 @@ class SgdOptions(C.Structure):
 SGD_INLINE_RANGES = 64  # CNN_SGD_INLINE_RANGES
 
 
+class AdamOptions(C.Structure):
+    """mirror of cnn_adam_options"""
+
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float),
+                ("decoupled", C.c_int), ("step", C.c_uint64)]
+
+
+CLIP_MAX_BLOCKS = 2048  # CNN_CLIP_MAX_BLOCKS: the largest grid of the clip kernels (workgroups of CLIP_BLOCK lanes, a float4 per lane)
+CLIP_BLOCK = 256
+
+
 _lib = None
 
 # name -> (restype, argtypes); the single source for the "exports every declared symbol" test
@@ -129,6 +140,9 @@ SIGNATURES = {
     "cnn_sgd_update": (C.c_int, [_P, _P, C.c_size_t, C.c_float, C.c_float, _P]),
     "cnn_sgd_update_keep": (C.c_int, [_P, _P, C.c_size_t, C.c_float, C.c_float, _P, _P]),
     "cnn_sgd_momentum_update": (C.c_int, [_P, _P, _P, C.c_size_t, C.POINTER(SgdOptions), C.c_float, _P, _P, C.c_size_t, _P, _P]),
+    "cnn_adam_update": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.POINTER(AdamOptions), C.c_float, _P, _P, C.c_size_t, _P, _P]),
+    "cnn_clip_grad_norm_workspace_bytes": (C.c_size_t, [C.c_size_t]),
+    "cnn_clip_grad_norm": (C.c_int, [_P, C.c_size_t, C.c_float, C.c_float, _P, C.c_size_t, _P, _P]),
     "cnn_stream_wait_event_local": (C.c_int, [_P, _P]),
     "cnn_stream_create_priority": (C.c_int, [C.POINTER(C.c_void_p), C.c_int]),
     "cnn_conv2d_backward_weight_pooled2_sgd_keep": (C.c_int, [_D, _P, _P, _P, _P, _P, _P, C.c_float, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P,
@@ -686,6 +700,44 @@ def sgd_momentum_update(params, grads, velocity, lr, momentum=0.0, weight_decay=
     if dev is not None:
         torch.cuda.current_stream().synchronize()  # (the table must outlive the kernel that reads it)
     return params
+
+
+def adam_update(params, grads, exp_avg, exp_avg_sq, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, decoupled=False, step=1,
+                grad_scale=1.0, decay_ranges=(), previous=None, n=None):
+    """cnn_adam_update on device tensors (or views of them); step: the 1-based number of this step; decay_ranges as in
+    sgd_momentum_update, tables longer than SGD_INLINE_RANGES are uploaded here"""
+    import numpy as np
+    import torch
+
+    _need_gpu(params, grads, exp_avg, exp_avg_sq, previous)
+    n = params.numel() if n is None else int(n)
+    opt = AdamOptions(float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), 1 if decoupled else 0, int(step))
+    table = np.ascontiguousarray(np.asarray(list(decay_ranges), dtype=np.uint32).reshape(-1, 2))
+    n_ranges = table.shape[0]
+    dev = torch.from_numpy(table.view(np.int32).reshape(-1)).to(params.device) if n_ranges > SGD_INLINE_RANGES else None
+    check(load().cnn_adam_update(_ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), n, C.byref(opt), float(grad_scale),
+                                 table.ctypes.data_as(C.c_void_p) if n_ranges else None, _ptr(dev), n_ranges, _ptr(previous), _stream()),
+          "cnn_adam_update")
+    if dev is not None:
+        torch.cuda.current_stream().synchronize()  # (the table must outlive the kernel that reads it)
+    return params
+
+
+def clip_grad_norm(grads, max_norm, grad_scale=1.0, n=None):
+    """cnn_clip_grad_norm on a device tensor (or a view of one), in place -> the stats tensor [total norm, coefficient] on the
+    device (reading it is the caller's synchronisation)"""
+    import torch
+
+    _need_gpu(grads)
+    n = grads.numel() if n is None else int(n)
+    lib = load()
+    ws_bytes = int(lib.cnn_clip_grad_norm_workspace_bytes(n))
+    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=grads.device)
+    stats = torch.empty(2, dtype=torch.float32, device=grads.device)
+    check(lib.cnn_clip_grad_norm(_ptr(grads), n, float(max_norm), float(grad_scale), _ptr(ws), ws_bytes, _ptr(stats), _stream()),
+          "cnn_clip_grad_norm")
+    torch.cuda.current_stream().synchronize()  # (the workspace must outlive the kernels that use it)
+    return stats
 
 
 def softmax_xent(logits, labels, want_probs=True):

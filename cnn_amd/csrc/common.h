@@ -246,7 +246,58 @@ __device__ __forceinline__ float sgdm_one(float p, float g, float& v, float lr, 
     return p - step;
 }
 
-constexpr int kWave = 64;          // CDNA wavefront
+// Adam / AdamW on one element (cnn_adam_update, include/cnn_amd.h has the formula): the arithmetic of torch.optim.Adam / AdamW
+// (amsgrad off) in sgdm_one's manner -- fp32, every product, sum, quotient and root rounded separately; the quotient and the root
+// are the correctly rounded ones (no fast-math flag in the build), denormals are kept.  The scalars that do not depend on the
+// element are computed once on the host (cnn_adam_update):
+//     om   = 1.f - lr * weight_decay                                  (two fp32 operations)
+//     omb1 = 1.f - beta1,  omb2 = 1.f - beta2                         (fp32)
+//     bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step))
+//     ss   = (float)((double)lr / (1.0 - pow((double)beta1, (double)step)))
+// Per element, `decay` = inside a decayed range AND weight_decay != 0:
+//     gs  = scaled ? g * scale : g
+//     d   = (decay && !decoupled) ? gs + wd * p : gs
+//     p0  = (decay &&  decoupled) ? p * om : p
+//     m'  = beta1 * m + omb1 * d
+//     v'  = beta2 * v + omb2 * (d * d)
+//     den = sqrt(v') / bc2s + eps
+//     q   = m' / den
+//     p'  = p0 - ss * q
+struct AdamScalars {
+    float beta1, beta2, omb1, omb2, eps, wd, om, bc2s, ss, scale;
+    bool scaled, decoupled;
+};
+__device__ __forceinline__ float adam_one(float p, float g, float& m, float& v, const AdamScalars& a, bool decay) {
+#pragma clang fp contract(off)
+    const float gs = a.scaled ? g * a.scale : g;
+    float d = gs;
+    float p0 = p;
+    if (decay) {
+        if (a.decoupled) {
+            p0 = p * a.om;
+        } else {
+            const float wp = a.wd * p;
+            d = gs + wp;
+        }
+    }
+    const float b1m = a.beta1 * m;
+    const float o1d = a.omb1 * d;
+    const float mn = b1m + o1d;
+    const float b2v = a.beta2 * v;
+    const float dd = d * d;
+    const float o2d = a.omb2 * dd;
+    const float vn = b2v + o2d;
+    m = mn;
+    v = vn;
+    const float root = sqrtf(vn);
+    const float rb = root / a.bc2s;
+    const float den = rb + a.eps;
+    const float q = mn / den;
+    const float step = a.ss * q;
+    return p0 - step;
+}
+
+constexpr int kWave = 64;         // CDNA wavefront
 constexpr int kNumXCD = 8;
 
 // Workgroups are dealt round-robin to the 8 XCDs (id % 8), each with its own L2: neighbouring tiles of an image -- which share

@@ -131,6 +131,35 @@ __device__ __forceinline__ bool in_range_from(const Ranges& r, int nr, int& k, u
     return k < nr && r.begin(k) <= idx;
 }
 
+// which of the four elements of float4 i decay (bit j: element 4*i + j); the search is wave-uniform, see above
+template <class Ranges>
+__device__ __forceinline__ unsigned decay_bits4(const Ranges& r, int nr, size_t i) {
+    unsigned bits = 0;
+    if (nr) {
+        const uint32_t e = (uint32_t)(i * 4);
+        const uint32_t wave_first = __builtin_amdgcn_readfirstlane(e);  // (lanes hold ascending i: the first active one is the lowest)
+        const uint64_t wave_end = (uint64_t)wave_first + 4 * kWave;
+        const int k0 = first_open_range(r, nr, wave_first);
+        if (k0 < nr) {
+            const uint32_t b0 = r.begin(k0);
+            if (b0 <= wave_first && r.end(k0) >= wave_end) {
+                bits = 15u;
+            } else if (b0 < wave_end) {
+                int k = k0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) bits |= in_range_from(r, nr, k, e + j) ? (1u << j) : 0u;
+            }
+        }
+    }
+    return bits;
+}
+// one element's answer (the tails and the scalar kernels)
+template <class Ranges>
+__device__ __forceinline__ bool decays_at(const Ranges& r, int nr, size_t i) {
+    int k = nr ? first_open_range(r, nr, (uint32_t)i) : 0;
+    return nr && in_range_from(r, nr, k, (uint32_t)i);
+}
+
 template <bool kMomentum, class Ranges>
 __global__ __launch_bounds__(kBlock) void sgdm_vec(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ v,
                                                    size_t n4, size_t n, const SgdmArgs a, float4* __restrict__ keep, const Ranges r) {
@@ -151,23 +180,7 @@ __global__ __launch_bounds__(kBlock) void sgdm_vec(float4* __restrict__ p, const
         float4 pv = p[i];
         const float4 gv = g[i];
         float4 vv = kMomentum ? v[i] : float4{0.f, 0.f, 0.f, 0.f};
-        unsigned bits = 0;  // bit j: element 4*i + j decays
-        if (a.nr) {
-            const uint32_t e = (uint32_t)(i * 4);
-            const uint32_t wave_first = __builtin_amdgcn_readfirstlane(e);  // (lanes hold ascending i: the first active one is the lowest)
-            const uint64_t wave_end = (uint64_t)wave_first + 4 * kWave;
-            const int k0 = first_open_range(r, a.nr, wave_first);
-            if (k0 < a.nr) {
-                const uint32_t b0 = r.begin(k0);
-                if (b0 <= wave_first && r.end(k0) >= wave_end) {
-                    bits = 15u;
-                } else if (b0 < wave_end) {
-                    int k = k0;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) bits |= in_range_from(r, a.nr, k, e + j) ? (1u << j) : 0u;
-                }
-            }
-        }
+        const unsigned bits = decay_bits4(r, a.nr, i);  // bit j: element 4*i + j decays
         if (keep) keep[i] = pv;
         pv.x = sgdm_one<kMomentum>(pv.x, gv.x, vv.x, a.lr, a.momentum, a.wd, a.scale, a.scaled, bits & 1u, a.nesterov);
         pv.y = sgdm_one<kMomentum>(pv.y, gv.y, vv.y, a.lr, a.momentum, a.wd, a.scale, a.scaled, bits & 2u, a.nesterov);
@@ -187,6 +200,151 @@ __global__ __launch_bounds__(kBlock) void sgdm_scalar(float* __restrict__ p, con
         if (keep) keep[i] = p[i];
         p[i] = sgdm_one<kMomentum>(p[i], g[i], vel, a.lr, a.momentum, a.wd, a.scale, a.scaled, decay, a.nesterov);
         if (kMomentum) v[i] = vel;
+    }
+}
+
+// ---- Adam / AdamW (cnn_adam_update; adam_one(): common.h) -------------------------------------------------------------------------
+// sgdm_vec's shape with four streams: reads p, g, m, v and writes p, m, v (28 B per element, 32 with keep); the same range structs
+// and wave-uniform search decide where weight decay applies.  Three correctly rounded divide / root sequences per element.
+struct AdamArgs {
+    AdamScalars s;
+    int nr;  // number of ranges; 0 when weight_decay == 0
+};
+
+template <class Ranges>
+__global__ __launch_bounds__(kBlock) void adam_vec(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ m,
+                                                   float4* __restrict__ v, size_t n4, size_t n, const AdamArgs a, float4* __restrict__ keep,
+                                                   const Ranges r) {
+    if (blockIdx.x == 0 && n4 * 4 + threadIdx.x < n) {
+        float* ps = (float*)p;
+        const float* gs = (const float*)g;
+        float* ms = (float*)m;
+        float* vs = (float*)v;
+        const size_t i = n4 * 4 + threadIdx.x;
+        const bool decay = decays_at(r, a.nr, i);
+        float mi = ms[i], vi = vs[i];
+        if (keep) ((float*)keep)[i] = ps[i];
+        ps[i] = adam_one(ps[i], gs[i], mi, vi, a.s, decay);
+        ms[i] = mi;
+        vs[i] = vi;
+    }
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (size_t)gridDim.x * kBlock) {
+        // (the streams' loads are issued first: the table search below runs while they are in flight)
+        float4 pv = p[i];
+        const float4 gv = g[i];
+        float4 mv = m[i];
+        float4 vv = v[i];
+        const unsigned bits = decay_bits4(r, a.nr, i);  // bit j: element 4*i + j decays
+        if (keep) keep[i] = pv;
+        pv.x = adam_one(pv.x, gv.x, mv.x, vv.x, a.s, bits & 1u);
+        pv.y = adam_one(pv.y, gv.y, mv.y, vv.y, a.s, bits & 2u);
+        pv.z = adam_one(pv.z, gv.z, mv.z, vv.z, a.s, bits & 4u);
+        pv.w = adam_one(pv.w, gv.w, mv.w, vv.w, a.s, bits & 8u);
+        p[i] = pv;
+        m[i] = mv;
+        v[i] = vv;
+    }
+}
+template <class Ranges>
+__global__ __launch_bounds__(kBlock) void adam_scalar(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                      float* __restrict__ v, size_t begin, size_t n, const AdamArgs a, float* __restrict__ keep,
+                                                      const Ranges r) {
+    for (size_t i = begin + (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
+        const bool decay = decays_at(r, a.nr, i);
+        float mi = m[i], vi = v[i];
+        if (keep) keep[i] = p[i];
+        p[i] = adam_one(p[i], g[i], mi, vi, a.s, decay);
+        m[i] = mi;
+        v[i] = vi;
+    }
+}
+
+// ---- clipping by the global L2 norm (cnn_clip_grad_norm) ----------------------------------------------------------------------------
+// Three launches, no host round trip, no floating-point atomics:
+//   clip_partial : every workgroup sums (double)g * (double)g over its grid-stride share (per lane, then the wave's shuffle tree, then
+//                  the four waves in order) into partial[blockIdx.x] -- the products are exact in fp64;
+//   clip_finish  : ONE workgroup adds the partials (each lane its strided share in ascending order, then the same tree), takes the
+//                  root, and writes stats = {total norm, coefficient};
+//   clip_scale   : g *= coefficient; every workgroup returns at once when the coefficient is 1 (the arena is not written).
+// The order of every sum is fixed by n and the grid alone, so the result is the same from run to run.  The grid never exceeds
+// kClipMaxBlocks workgroups: the workspace is that many doubles whatever n is.
+constexpr int kClipMaxBlocks = CNN_CLIP_MAX_BLOCKS;
+
+__device__ __forceinline__ double block_sum(double x, double* lds) {
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) x += __shfl_down(x, off, kWave);
+    const int wave = threadIdx.x / kWave;
+    if (threadIdx.x % kWave == 0) lds[wave] = x;
+    __syncthreads();
+    double total = 0.0;
+    if (threadIdx.x == 0) {
+        total = lds[0];
+        for (int w = 1; w < kBlock / kWave; ++w) total += lds[w];
+    }
+    return total;  // (valid in thread 0)
+}
+
+template <bool kVec>
+__global__ __launch_bounds__(kBlock) void clip_partial(const float* __restrict__ g, size_t n, double* __restrict__ partial) {
+    __shared__ double lds[kBlock / kWave];
+    double acc = 0.0;
+    if (kVec) {
+        const size_t n4 = n / 4;
+        const float4* g4 = (const float4*)g;
+        if (blockIdx.x == 0 && n4 * 4 + threadIdx.x < n) {
+            const double x = (double)g[n4 * 4 + threadIdx.x];
+            acc += x * x;
+        }
+        for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (size_t)gridDim.x * kBlock) {
+            const float4 q = g4[i];
+            const double x = (double)q.x, y = (double)q.y, z = (double)q.z, w = (double)q.w;
+            acc += x * x;
+            acc += y * y;
+            acc += z * z;
+            acc += w * w;
+        }
+    } else {
+        for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
+            const double x = (double)g[i];
+            acc += x * x;
+        }
+    }
+    const double total = block_sum(acc, lds);
+    if (threadIdx.x == 0) partial[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(kBlock) void clip_finish(const double* __restrict__ partial, int n_partial, float max_norm, float scale, bool scaled,
+                                                      float* __restrict__ stats) {
+    __shared__ double lds[kBlock / kWave];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n_partial; i += kBlock) acc += partial[i];
+    const double S = block_sum(acc, lds);
+    if (threadIdx.x == 0) {
+#pragma clang fp contract(off)
+        const float norm = (float)sqrt(S);
+        const float total = scaled ? norm * scale : norm;
+        const float sum = total + 1e-6f;
+        const float c = max_norm / sum;
+        stats[0] = total;
+        stats[1] = c < 1.f ? c : 1.f;  // (a NaN total: the comparison is false, the gradients stay as they are)
+    }
+}
+
+template <bool kVec>
+__global__ __launch_bounds__(kBlock) void clip_scale(float* __restrict__ g, size_t n, const float* __restrict__ stats) {
+    const float coef = stats[1];
+    if (!(coef < 1.f)) return;
+    if (kVec) {
+        const size_t n4 = n / 4;
+        float4* g4 = (float4*)g;
+        if (blockIdx.x == 0 && n4 * 4 + threadIdx.x < n) g[n4 * 4 + threadIdx.x] *= coef;
+        for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (size_t)gridDim.x * kBlock) {
+            float4 q = g4[i];
+            q.x *= coef; q.y *= coef; q.z *= coef; q.w *= coef;
+            g4[i] = q;
+        }
+    } else {
+        for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) g[i] *= coef;
     }
 }
 
@@ -257,6 +415,54 @@ int launch_sgdm(float* params, const float* grads, float* velocity, size_t n, co
                     "tail n=%zu ranges=%d", n, a.nr);
     }
     return CNN_AMD_OK;
+}
+
+// one launch of the Adam step (the scalar kernel alone when a pointer is not 16-byte aligned)
+template <class Ranges>
+int launch_adam(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n, const AdamArgs& a, float* previous,
+                const Ranges& r, hipStream_t s) {
+    const bool vec = aligned16(params) && aligned16(grads) && aligned16(exp_avg) && aligned16(exp_avg_sq) &&
+                     (previous == nullptr || aligned16(previous)) && n >= 4;
+    if (vec) {
+        const size_t n4 = n / 4;
+        CNN_KLAUNCH(s, "adam_vec",
+                    (adam_vec<Ranges><<<stream_grid(n4, kBlock), kBlock, 0, s>>>((float4*)params, (const float4*)grads, (float4*)exp_avg,
+                                                                              (float4*)exp_avg_sq, n4, n, a, (float4*)previous, r)),
+                    "n=%zu ranges=%d", n, a.nr);
+    } else {
+        CNN_KLAUNCH(s, "adam_scalar",
+                    (adam_scalar<Ranges><<<stream_grid(n, kBlock), kBlock, 0, s>>>(params, grads, exp_avg, exp_avg_sq, 0, n, a, previous, r)),
+                    "tail n=%zu ranges=%d", n, a.nr);
+    }
+    return CNN_AMD_OK;
+}
+
+// the scalars of one Adam step that do not depend on the element (common.h, adam_one): plain host arithmetic, every fp32 operation
+// rounded separately
+AdamScalars adam_scalars(const cnn_adam_options& o, float grad_scale) {
+#pragma clang fp contract(off)
+    AdamScalars a;
+    a.beta1 = o.beta1;
+    a.beta2 = o.beta2;
+    a.omb1 = 1.f - o.beta1;
+    a.omb2 = 1.f - o.beta2;
+    a.eps = o.eps;
+    a.wd = o.weight_decay;
+    const volatile float lw = o.lr * o.weight_decay;
+    a.om = 1.f - lw;
+    const double t = (double)o.step;
+    a.bc2s = (float)std::sqrt(1.0 - std::pow((double)o.beta2, t));
+    a.ss = (float)((double)o.lr / (1.0 - std::pow((double)o.beta1, t)));
+    a.scale = grad_scale;
+    a.scaled = grad_scale != 1.0f;
+    a.decoupled = o.decoupled != 0;
+    return a;
+}
+
+// grid of the clip kernels: stream_grid, never more than the workspace holds
+inline unsigned clip_grid(size_t work_items) {
+    const unsigned g = stream_grid(work_items, kBlock);
+    return g > (unsigned)kClipMaxBlocks ? (unsigned)kClipMaxBlocks : g;
 }
 
 
@@ -430,6 +636,74 @@ int cnn_sgd_momentum_update(float* params, const float* grads, float* velocity, 
     InlineRanges r;
     for (int k = 0; k < 2 * CNN_SGD_INLINE_RANGES; ++k) r.be[k] = k < 2 * a.nr ? decay_ranges[k] : 0u;
     return mom ? launch_sgdm<true>(params, grads, velocity, n, a, previous, r, s) : launch_sgdm<false>(params, grads, velocity, n, a, previous, r, s);
+}
+
+int cnn_adam_update(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n, const cnn_adam_options* opt,
+                    float grad_scale, const uint32_t* decay_ranges, const uint32_t* decay_ranges_dev, size_t n_ranges, float* previous,
+                    void* stream) {
+    CNN_REQUIRE(params && grads && exp_avg && exp_avg_sq && opt, "cnn_adam_update: null pointer");
+    CNN_REQUIRE(opt->beta1 >= 0.f && opt->beta1 < 1.f && opt->beta2 >= 0.f && opt->beta2 < 1.f, "cnn_adam_update: beta1=%g beta2=%g outside [0, 1)",
+                (double)opt->beta1, (double)opt->beta2);
+    CNN_REQUIRE(opt->eps > 0.f, "cnn_adam_update: eps=%g must be positive", (double)opt->eps);
+    CNN_REQUIRE(opt->weight_decay >= 0.f, "cnn_adam_update: weight_decay=%g", (double)opt->weight_decay);
+    CNN_REQUIRE(opt->step != 0, "cnn_adam_update: step=0 (the number of this step, counted from 1)");
+    CNN_REQUIRE(n <= (size_t)0xFFFFFFFFu - 4 * kWave, "cnn_adam_update: n=%zu exceeds the 32-bit range table: step the arena in pieces", n);
+    CNN_REQUIRE(n_ranges <= n && (n_ranges == 0 || decay_ranges), "cnn_adam_update: null decay_ranges / n_ranges=%zu with n=%zu", n_ranges, n);
+    CNN_REQUIRE(n_ranges <= (size_t)CNN_SGD_INLINE_RANGES || decay_ranges_dev,
+                "cnn_adam_update: %zu ranges (more than CNN_SGD_INLINE_RANGES) need decay_ranges_dev", n_ranges);
+    uint32_t prev_end = 0;
+    for (size_t k = 0; k < n_ranges; ++k) {
+        const uint32_t b = decay_ranges[2 * k], e = decay_ranges[2 * k + 1];
+        CNN_REQUIRE(b >= prev_end && b < e && (size_t)e <= n, "cnn_adam_update: range %zu = [%u, %u) is empty, unsorted, overlapping or beyond n=%zu", k, b,
+                    e, n);
+        prev_end = e;
+    }
+    if (n == 0) return CNN_AMD_OK;
+    hipStream_t s = as_stream(stream);
+    AdamArgs a;
+    a.s = adam_scalars(*opt, grad_scale);
+    a.nr = opt->weight_decay != 0.f ? (int)n_ranges : 0;
+    if (a.nr > CNN_SGD_INLINE_RANGES) {
+        const DeviceRanges r{decay_ranges_dev};
+        return launch_adam(params, grads, exp_avg, exp_avg_sq, n, a, previous, r, s);
+    }
+    InlineRanges r;
+    for (int k = 0; k < 2 * CNN_SGD_INLINE_RANGES; ++k) r.be[k] = k < 2 * a.nr ? decay_ranges[k] : 0u;
+    return launch_adam(params, grads, exp_avg, exp_avg_sq, n, a, previous, r, s);
+}
+
+size_t cnn_clip_grad_norm_workspace_bytes(size_t n) {
+    // one double per workgroup of the largest grid a call with this n launches (the scalar kernels': one element per lane)
+    const size_t need = (n + kBlock - 1) / kBlock;
+    return sizeof(double) * (need < 1 ? 1 : (need > (size_t)kClipMaxBlocks ? (size_t)kClipMaxBlocks : need));
+}
+
+int cnn_clip_grad_norm(float* grads, size_t n, float max_norm, float grad_scale, void* workspace, size_t workspace_bytes, float* stats_dev,
+                       void* stream) {
+    CNN_REQUIRE(grads && workspace && stats_dev, "cnn_clip_grad_norm: null pointer");
+    CNN_REQUIRE(n != 0, "cnn_clip_grad_norm: n=0");
+    CNN_REQUIRE(max_norm > 0.f, "cnn_clip_grad_norm: max_norm=%g must be positive", (double)max_norm);
+    const size_t need = cnn_clip_grad_norm_workspace_bytes(n);
+    CNN_REQUIRE(workspace_bytes >= need, "cnn_clip_grad_norm: workspace of %zu bytes, n=%zu needs %zu (cnn_clip_grad_norm_workspace_bytes)",
+                workspace_bytes, n, need);
+    CNN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0, "cnn_clip_grad_norm: the workspace must be 8-byte aligned");
+    hipStream_t s = as_stream(stream);
+    double* partial = (double*)workspace;
+    const bool vec = aligned16(grads);
+    const unsigned grid = clip_grid(vec ? n / 4 : n);
+    if (vec) {
+        CNN_KLAUNCH(s, "clip_partial_vec", (clip_partial<true><<<grid, kBlock, 0, s>>>(grads, n, partial)), "n=%zu", n);
+    } else {
+        CNN_KLAUNCH(s, "clip_partial_scalar", (clip_partial<false><<<grid, kBlock, 0, s>>>(grads, n, partial)), "n=%zu", n);
+    }
+    CNN_KLAUNCH(s, "clip_finish", (clip_finish<<<1, kBlock, 0, s>>>(partial, (int)grid, max_norm, grad_scale, grad_scale != 1.0f, stats_dev)),
+                "partials=%u", grid);
+    if (vec) {
+        CNN_KLAUNCH(s, "clip_scale_vec", (clip_scale<true><<<grid, kBlock, 0, s>>>(grads, n, stats_dev)), "n=%zu", n);
+    } else {
+        CNN_KLAUNCH(s, "clip_scale_scalar", (clip_scale<false><<<grid, kBlock, 0, s>>>(grads, n, stats_dev)), "n=%zu", n);
+    }
+    return CNN_AMD_OK;
 }
 
 int cnn_softmax_xent(const float* logits, const int32_t* labels, float* probs, float* delta, float* loss_sum, int B,

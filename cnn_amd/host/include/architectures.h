@@ -425,7 +425,8 @@ public:
 //   * filter preparation hoisted out of the per-layer calls (cnn_conv2d_prepare_filters), redone after every parameter change;
 //   * an optional RCCL communicator (set_comm): the batch is then sharded over `world` replicas, BatchNorm2D layers
 //     normalise over the GLOBAL batch (sync-BN) and update_gradients() sums the gradient arena over the replicas first;
-//   * an optional optimizer (set_optimizer): momentum, weight decay and Nesterov on the arena instead of the reference's w -= lr * g.
+//   * an optional optimizer (set_optimizer): momentum, weight decay and Nesterov on the arena instead of the reference's w -= lr * g;
+//   * Adam / AdamW (set_adam) and clipping by the global gradient norm (set_grad_clip) on the same arena.
 class Sequential {
 public:
     bool print_info = false;
@@ -482,7 +483,21 @@ protected:
         uint32_t* dev = nullptr;       // device copy, only for tables of more than CNN_SGD_INLINE_RANGES ranges
     };
     DecayTable decay_tables[3];        // the three ranges the container steps: the whole arena, behind the front block, the front block
-    void build_decay_table(DecayTable& t, size_t lo, size_t hi);
+    void build_decay_table(DecayTable& t, size_t lo, size_t hi, bool bias_and_norm);
+    void build_decay_tables(bool bias_and_norm);
+    // ---- Adam / AdamW (set_adam): the arena's step is cnn_adam_update; opt_active is true as well, so the fused tail takes the
+    // momentum optimizer's route (the front block's step is the arena kernel, no TAIL_BEHIND_BLOCK) ----
+    bool adam_active = false;          // the optimizer set last was set_adam()
+    data_type adam_beta1 = 0, adam_beta2 = 0, adam_eps = 0, adam_weight_decay = 0;
+    bool adam_decoupled = false, adam_decay_bias_and_norm = false;
+    data_type* adam_m = nullptr;       // exp_avg and exp_avg_sq: n_params floats each, allocated (zeroed) by the first set_adam()
+    data_type* adam_v = nullptr;
+    uint64_t adam_t = 0;               // container steps taken under Adam (the step the next launch carries is adam_t after its increment)
+    // ---- clipping by the global gradient norm (set_grad_clip) ----
+    data_type clip_max_norm = 0;       // 0: off
+    void* clip_workspace = nullptr;    // cnn_clip_grad_norm's partial sums
+    size_t clip_workspace_bytes = 0;
+    data_type* clip_stats = nullptr;   // [2] on the device: total norm, coefficient of the latest clipped step
     size_t front_block_params() const;
     // the SGD step on arena[lo, hi) (parameters, gradients, velocity, snapshot) on `on_stream`, plain or with the optimizer
     void step_arena(size_t lo, size_t hi, data_type learning_rate, data_type grad_scale, void* on_stream);
@@ -538,6 +553,36 @@ public:
     // n_params; nothing is changed on failure, on success the file's options are set as by set_optimizer().
     int save_optimizer_state(const std::filesystem::path& path);
     int load_optimizer_state(const std::filesystem::path& path);
+
+    // Adam / AdamW (torch.optim.Adam / AdamW, amsgrad off) for every step the container takes on its arena; formula and rounding in
+    // include/cnn_amd.h (cnn_adam_update).  decoupled = false adds weight_decay * w to the gradient (Adam's L2 term), true shrinks the
+    // parameter by 1 - lr * weight_decay (AdamW); the decay policy is set_optimizer's.  Call it after finalize(), any number of times:
+    // the two state arenas (exp_avg, exp_avg_sq) are allocated and zeroed, and the step counter set to 0, by the first call only.
+    // set_adam and set_optimizer replace each other -- the one called last is the active optimizer, set_optimizer(0, 0) still returns
+    // to the plain step -- and no state arena is freed or zeroed by a switch.  The step counter advances once per container step
+    // (update_gradients / train_step), also where the fused tail steps the arena in two launches.  The price in a train step is
+    // the momentum optimizer's: the front block is stepped by the arena kernel.
+    void set_adam(data_type beta1 = 0.9, data_type beta2 = 0.999, data_type eps = 1e-8, data_type weight_decay = 0, bool decoupled = false,
+                  bool decay_bias_and_norm = false);
+    bool adam_is_active() const { return adam_active; }
+    data_type* adam_m_device() const { return adam_m; }  // null before the first set_adam()
+    data_type* adam_v_device() const { return adam_v; }
+    uint64_t adam_step() const { return adam_t; }
+    // With Adam active save_optimizer_state writes a second format: magic "CNNAADM1", n_params (uint64), step (uint64), beta1, beta2, eps,
+    // weight_decay (float), decoupled, decay_bias_and_norm (uint32), then exp_avg, then exp_avg_sq.  load_optimizer_state recognises
+    // both magics and activates the optimizer the file was written for; the status codes are the ones above.
+    //
+    // Clipping by the global L2 norm of the gradient arena (torch.nn.utils.clip_grad_norm_; cnn_clip_grad_norm): with max_norm > 0
+    // update_gradients(lr, grad_scale) clips the whole arena -- behind the data-parallel all-reduce, in front of the step, on the same
+    // stream, without a host round trip -- for the plain step, the momentum optimizer and Adam alike.  0 (the default) switches it
+    // off.  BatchNorm2D's moving statistics have a zero gradient and add nothing to the norm.  THE PRICE: the norm needs every
+    // gradient of the step before any parameter moves, so with clipping on the fused step tail (fused_tail) declines and a train
+    // step takes the plain sequence -- the whole backward walk, the joins, update_gradients -- plus the three clip launches.
+    void set_grad_clip(data_type max_norm);
+    data_type grad_clip() const { return clip_max_norm; }
+    bool grad_clip_ever_on() const { return clip_stats != nullptr; }
+    // total norm (and coefficient) of the latest clipped step; like last_loss() it synchronises.  Asserts when clipping was never on.
+    data_type last_grad_norm(data_type* coef_out = nullptr);
 
 protected:
     void invalidate_filter_images();  // (the part of parameters_changed() the container's own SGD step needs too)

@@ -124,6 +124,33 @@ int cnnh_net_get_velocity(void* hv, float* host) {  // 1: no optimizer was ever 
     must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
     return 0;
 }
+// Sequential::set_adam and its state (the two moment arenas are null before the first cnnh_net_set_adam), Sequential::set_grad_clip
+void cnnh_net_set_adam(void* hv, float beta1, float beta2, float eps, float weight_decay, int decoupled, int decay_bias_and_norm) {
+    ((Handle*)hv)->net->set_adam(beta1, beta2, eps, weight_decay, decoupled != 0, decay_bias_and_norm != 0);
+}
+float* cnnh_net_adam_m_device(void* hv) { return ((Handle*)hv)->net->adam_m_device(); }
+float* cnnh_net_adam_v_device(void* hv) { return ((Handle*)hv)->net->adam_v_device(); }
+int cnnh_net_get_adam_state(void* hv, float* m_host, float* v_host, uint64_t* step_out) {  // 1: Adam was never set
+    Handle* h = (Handle*)hv;
+    if (h->net->adam_m_device() == nullptr) return 1;
+    h->net->flush_deferred();
+    const size_t bytes = sizeof(float) * h->net->num_params();
+    if (m_host) must(cnn_memcpy_d2h(m_host, h->net->adam_m_device(), bytes, stream), "cnn_memcpy_d2h");
+    if (v_host) must(cnn_memcpy_d2h(v_host, h->net->adam_v_device(), bytes, stream), "cnn_memcpy_d2h");
+    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
+    if (step_out) *step_out = h->net->adam_step();
+    return 0;
+}
+void cnnh_net_set_grad_clip(void* hv, float max_norm) { ((Handle*)hv)->net->set_grad_clip(max_norm); }
+int cnnh_net_last_grad_norm(void* hv, float* norm_out, float* coef_out) {  // 1: clipping was never on
+    Handle* h = (Handle*)hv;
+    if (!h->net->grad_clip_ever_on()) return 1;
+    float coef = 0.f;
+    const float norm = h->net->last_grad_norm(&coef);
+    if (norm_out) *norm_out = norm;
+    if (coef_out) *coef_out = coef;
+    return 0;
+}
 int cnnh_net_save_optimizer_state(void* hv, const char* path) { return ((Handle*)hv)->net->save_optimizer_state(path); }
 int cnnh_net_load_optimizer_state(void* hv, const char* path) { return ((Handle*)hv)->net->load_optimizer_state(path); }
 void cnnh_set_stream(void* hip_stream) { architectures::stream = hip_stream; }

@@ -178,6 +178,10 @@ Sequential::~Sequential() {
     layers_sequence.clear();
     if (param_prev) cnn_device_free(param_prev);
     if (velocity) cnn_device_free(velocity);
+    if (adam_m) cnn_device_free(adam_m);
+    if (adam_v) cnn_device_free(adam_v);
+    if (clip_workspace) cnn_device_free(clip_workspace);
+    if (clip_stats) cnn_device_free(clip_stats);
     for (auto& t : decay_tables)
         if (t.dev) cnn_device_free(t.dev);
     if (defer_stream) cnn_stream_destroy(defer_stream);
@@ -447,6 +451,10 @@ void Sequential::update_gradients(const data_type learning_rate, const data_type
             if (auto* c = dynamic_cast<Conv2D*>(layer.get())) c->params_of_last_forward_lost();
             if (auto* bn = dynamic_cast<BatchNorm2D*>(layer.get())) bn->params_of_last_forward_lost();
         }
+    if (clip_max_norm > 0 && n_params > 0)  // (behind the all-reduce, in front of the step; the step applies grad_scale to the clipped values)
+        must(cnn_clip_grad_norm(grad_arena, n_params, clip_max_norm, grad_scale, clip_workspace, clip_workspace_bytes, clip_stats, stream),
+             "cnn_clip_grad_norm");
+    if (adam_active) ++adam_t;
     step_arena(0, n_params, learning_rate, grad_scale, stream);
     invalidate_filter_images();
     params_stepped = true;
@@ -454,7 +462,7 @@ void Sequential::update_gradients(const data_type learning_rate, const data_type
 
 // ---------------------------------------------------------------------------------------------------------------
 // optimizer: SGD with momentum / weight decay / Nesterov on the arena
-void Sequential::build_decay_table(DecayTable& t, size_t lo, size_t hi) {
+void Sequential::build_decay_table(DecayTable& t, size_t lo, size_t hi, const bool bias_and_norm) {
     t.lo = lo;
     t.hi = hi;
     t.host.clear();
@@ -463,7 +471,7 @@ void Sequential::build_decay_table(DecayTable& t, size_t lo, size_t hi) {
     for (const auto& layer : layers_sequence) {
         const size_t off = layer_offsets[idx++];
         local.clear();
-        layer->decay_ranges(opt_decay_bias_and_norm, local);
+        layer->decay_ranges(bias_and_norm, local);
         for (const auto& r : local) {
             const size_t b = std::max(off + r.first, lo), e = std::min(off + r.second, hi);
             if (b >= e) continue;
@@ -504,10 +512,63 @@ void Sequential::set_optimizer(const data_type momentum, const data_type weight_
     opt_nesterov = nesterov;
     opt_decay_bias_and_norm = decay_bias_and_norm;
     opt_active = momentum != 0 || weight_decay != 0;
+    adam_active = false;
+    build_decay_tables(decay_bias_and_norm);
+}
+
+void Sequential::build_decay_tables(const bool bias_and_norm) {
     const size_t front = front_block_params();
-    build_decay_table(decay_tables[0], 0, n_params);
-    build_decay_table(decay_tables[1], front, n_params);
-    build_decay_table(decay_tables[2], 0, front);
+    build_decay_table(decay_tables[0], 0, n_params, bias_and_norm);
+    build_decay_table(decay_tables[1], front, n_params, bias_and_norm);
+    build_decay_table(decay_tables[2], 0, front, bias_and_norm);
+}
+
+void Sequential::set_adam(const data_type beta1, const data_type beta2, const data_type eps, const data_type weight_decay, const bool decoupled,
+                          const bool decay_bias_and_norm) {
+    assert(finalized && "set_adam works on the flat arena: call finalize() first");
+    assert(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1 && eps > 0 && weight_decay >= 0);
+    assert(n_params < ((size_t)1 << 32) - 1024 && "set_adam: the decay-range table is 32-bit");
+    flush_deferred();  // (a side-stream tail of the previous step may still read the tables rebuilt below)
+    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
+    if (adam_m == nullptr) {
+        adam_m = (data_type*)dev_alloc(sizeof(data_type) * (n_params ? n_params : 1));
+        adam_v = (data_type*)dev_alloc(sizeof(data_type) * (n_params ? n_params : 1));
+        must(cnn_memset_zero(adam_m, sizeof(data_type) * n_params, stream), "cnn_memset_zero");
+        must(cnn_memset_zero(adam_v, sizeof(data_type) * n_params, stream), "cnn_memset_zero");
+        must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
+        adam_t = 0;
+    }
+    adam_beta1 = beta1;
+    adam_beta2 = beta2;
+    adam_eps = eps;
+    adam_weight_decay = weight_decay;
+    adam_decoupled = decoupled;
+    adam_decay_bias_and_norm = decay_bias_and_norm;
+    adam_active = true;
+    opt_active = true;  // (every place that asks "is the step more than the block's in-kernel plain SGD")
+    build_decay_tables(decay_bias_and_norm);
+}
+
+void Sequential::set_grad_clip(const data_type max_norm) {
+    assert(finalized && "set_grad_clip works on the flat arena: call finalize() first");
+    assert(max_norm >= 0);
+    flush_deferred();  // (a side-stream tail of the previous step is ordered before the first clipped step's plain sequence)
+    if (max_norm > 0 && clip_stats == nullptr) {
+        clip_workspace_bytes = cnn_clip_grad_norm_workspace_bytes(n_params);
+        clip_workspace = dev_alloc(clip_workspace_bytes);
+        clip_stats = (data_type*)dev_alloc(sizeof(data_type) * 2);
+        must(cnn_memset_zero(clip_stats, sizeof(data_type) * 2, stream), "cnn_memset_zero");
+    }
+    clip_max_norm = max_norm;
+}
+
+data_type Sequential::last_grad_norm(data_type* coef_out) {
+    assert(clip_stats != nullptr && "last_grad_norm: clipping was never switched on (set_grad_clip)");
+    data_type host[2] = {0, 0};
+    must(cnn_memcpy_d2h(host, clip_stats, sizeof(host), stream), "cnn_memcpy_d2h");
+    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
+    if (coef_out) *coef_out = host[1];
+    return host[0];
 }
 
 void Sequential::step_arena(const size_t lo, const size_t hi, const data_type learning_rate, const data_type grad_scale, void* on_stream) {
@@ -524,6 +585,13 @@ void Sequential::step_arena(const size_t lo, const size_t hi, const data_type le
         std::fprintf(stderr, "cnn_amd host: step_arena: no decay table for arena[%zu, %zu)\n", lo, hi);
         std::abort();
     }
+    if (adam_active) {
+        const cnn_adam_options o{learning_rate, adam_beta1, adam_beta2, adam_eps, adam_weight_decay, adam_decoupled ? 1 : 0, adam_t};
+        must(cnn_adam_update(param_arena + lo, grad_arena + lo, adam_m + lo, adam_v + lo, hi - lo, &o, grad_scale, t->host.data(), t->dev,
+                             t->host.size() / 2, param_prev + lo, on_stream),
+             "cnn_adam_update");
+        return;
+    }
     const cnn_sgd_options o{learning_rate, opt_momentum, opt_weight_decay, opt_nesterov ? 1 : 0};
     must(cnn_sgd_momentum_update(param_arena + lo, grad_arena + lo, velocity + lo, hi - lo, &o, grad_scale, t->host.data(), t->dev,
                                  t->host.size() / 2, param_prev + lo, on_stream),
@@ -538,10 +606,40 @@ struct OptStateHeader {
     uint32_t nesterov, decay_bias_and_norm;
 };
 const char kOptMagic[8] = {'C', 'N', 'N', 'A', 'O', 'P', 'T', '1'};
+struct AdamStateHeader {
+    char magic[8];
+    uint64_t n_params, step;
+    float beta1, beta2, eps, weight_decay;
+    uint32_t decoupled, decay_bias_and_norm;
+};
+static_assert(sizeof(AdamStateHeader) == 48, "the Adam state file's header is 48 bytes");
+const char kAdamMagic[8] = {'C', 'N', 'N', 'A', 'A', 'D', 'M', '1'};
 }  // namespace
 
 int Sequential::save_optimizer_state(const std::filesystem::path& path) {
     assert(finalized);
+    if (adam_active) {
+        flush_deferred();
+        std::vector<data_type> host(2 * n_params);
+        must(cnn_memcpy_d2h(host.data(), adam_m, sizeof(data_type) * n_params, stream), "cnn_memcpy_d2h");
+        must(cnn_memcpy_d2h(host.data() + n_params, adam_v, sizeof(data_type) * n_params, stream), "cnn_memcpy_d2h");
+        must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
+        AdamStateHeader h;
+        std::memcpy(h.magic, kAdamMagic, 8);
+        h.n_params = n_params;
+        h.step = adam_t;
+        h.beta1 = adam_beta1;
+        h.beta2 = adam_beta2;
+        h.eps = adam_eps;
+        h.weight_decay = adam_weight_decay;
+        h.decoupled = adam_decoupled ? 1 : 0;
+        h.decay_bias_and_norm = adam_decay_bias_and_norm ? 1 : 0;
+        std::ofstream writer(path.c_str(), std::ios::binary);
+        writer.write((const char*)&h, sizeof(h));
+        writer.write((const char*)host.data(), sizeof(data_type) * host.size());
+        writer.close();
+        return writer.good() ? 0 : 1;
+    }
     if (velocity == nullptr) return 4;
     flush_deferred();
     std::vector<data_type> host(n_params);
@@ -565,6 +663,27 @@ int Sequential::load_optimizer_state(const std::filesystem::path& path) {
     assert(finalized);
     std::ifstream reader(path.c_str(), std::ios::binary);
     if (!reader.good()) return 1;
+    char magic[8] = {0};
+    reader.read(magic, 8);
+    if (reader.good() && std::memcmp(magic, kAdamMagic, 8) == 0) {
+        AdamStateHeader h;
+        std::memcpy(h.magic, magic, 8);
+        reader.read((char*)&h + 8, sizeof(h) - 8);
+        if (!reader.good()) return 2;
+        if (h.n_params != (uint64_t)n_params) return 3;
+        if (!(h.beta1 >= 0 && h.beta1 < 1) || !(h.beta2 >= 0 && h.beta2 < 1) || !(h.eps > 0) || !(h.weight_decay >= 0)) return 2;
+        std::vector<data_type> host(2 * n_params);
+        reader.read((char*)host.data(), sizeof(data_type) * host.size());
+        if ((size_t)reader.gcount() != sizeof(data_type) * host.size()) return 2;  // (nothing has been changed yet: no partial read)
+        set_adam(h.beta1, h.beta2, h.eps, h.weight_decay, h.decoupled != 0, h.decay_bias_and_norm != 0);
+        adam_t = h.step;
+        must(cnn_memcpy_h2d(adam_m, host.data(), sizeof(data_type) * n_params, stream), "cnn_memcpy_h2d");
+        must(cnn_memcpy_h2d(adam_v, host.data() + n_params, sizeof(data_type) * n_params, stream), "cnn_memcpy_h2d");
+        must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
+        return 0;
+    }
+    reader.clear();
+    reader.seekg(0);
     OptStateHeader h;
     reader.read((char*)&h, sizeof(h));
     if (!reader.good() || std::memcmp(h.magic, kOptMagic, 8) != 0) return 2;
@@ -617,9 +736,11 @@ bool Sequential::fused_tail(std::vector<tensor>& delta, const data_type learning
         !filters_prepared || layer_offsets.empty() || layer_offsets[0] != 0)
         return false;
     if (cnn_amd_get_option("NO_FUSED_TAIL", nullptr, 0) == 0) return false;  // (A/B switch)
+    if (clip_max_norm > 0) return false;  // (the norm needs every gradient of the step before any parameter moves: the plain sequence)
     const size_t lo = front_block_params();  // the block's convolution owns arena[0, lo)
     const bool dp = exchange_active();
     const data_type scale = dp ? 1.f / (data_type)comm_world : 1.f;
+    if (adam_active) ++adam_t;  // (ONE container step: both range launches below carry this number)
     if (ev_tail == nullptr) must(cnn_event_create(&ev_tail), "cnn_event_create");
     void* side = nullptr;
     must(cnn_amd_side_stream_get(&side), "cnn_amd_side_stream_get");

@@ -36,6 +36,12 @@ SIGNATURES = {
     "cnnh_net_set_optimizer": (None, [C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int]),
     "cnnh_net_velocity_device": (C.c_void_p, [C.c_void_p]),
     "cnnh_net_get_velocity": (C.c_int, [C.c_void_p, _F]),
+    "cnnh_net_set_adam": (None, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int]),
+    "cnnh_net_adam_m_device": (C.c_void_p, [C.c_void_p]),
+    "cnnh_net_adam_v_device": (C.c_void_p, [C.c_void_p]),
+    "cnnh_net_get_adam_state": (C.c_int, [C.c_void_p, _F, _F, C.POINTER(C.c_uint64)]),
+    "cnnh_net_set_grad_clip": (None, [C.c_void_p, C.c_float]),
+    "cnnh_net_last_grad_norm": (C.c_int, [C.c_void_p, _F, _F]),
     "cnnh_net_save_optimizer_state": (C.c_int, [C.c_void_p, C.c_char_p]),
     "cnnh_net_load_optimizer_state": (C.c_int, [C.c_void_p, C.c_char_p]),
     "cnnh_set_stream": (None, [C.c_void_p]),
@@ -159,6 +165,36 @@ class HostNet:
         if self.lib.cnnh_net_get_velocity(self.h, _fp(out)) != 0:
             raise capi.CnnAmdError("get_velocity before set_optimizer")
         return out
+
+    def set_adam(self, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, decoupled=False, decay_bias_and_norm=False):
+        """Sequential::set_adam: Adam (decoupled=False: L2 term in the gradient) or AdamW (decoupled=True) for every later step on the
+        arena; replaces set_optimizer and is replaced by it, the moments and the step counter survive a switch"""
+        self.lib.cnnh_net_set_adam(self.h, float(beta1), float(beta2), float(eps), float(weight_decay), 1 if decoupled else 0,
+                                   1 if decay_bias_and_norm else 0)
+
+    def adam_ptrs(self):
+        """device pointers of exp_avg and exp_avg_sq (n_params floats each); (None, None) before the first set_adam"""
+        return self.lib.cnnh_net_adam_m_device(self.h), self.lib.cnnh_net_adam_v_device(self.h)
+
+    def get_adam_state(self):
+        """(exp_avg, exp_avg_sq, step): the moments on the host and the number of container steps taken under Adam"""
+        m, v = np.empty(self.n_params, np.float32), np.empty(self.n_params, np.float32)
+        step = C.c_uint64(0)
+        if self.lib.cnnh_net_get_adam_state(self.h, _fp(m), _fp(v), C.byref(step)) != 0:
+            raise capi.CnnAmdError("get_adam_state before set_adam")
+        return m, v, int(step.value)
+
+    def set_grad_clip(self, max_norm):
+        """Sequential::set_grad_clip: clip every later step's gradient arena to this global L2 norm (0: off); a clipped train step
+        takes the plain sequence instead of the fused tail"""
+        self.lib.cnnh_net_set_grad_clip(self.h, float(max_norm))
+
+    def last_grad_norm(self):
+        """(total norm, coefficient) of the latest clipped step; synchronises"""
+        norm, coef = np.zeros(1, np.float32), np.zeros(1, np.float32)
+        if self.lib.cnnh_net_last_grad_norm(self.h, _fp(norm), _fp(coef)) != 0:
+            raise capi.CnnAmdError("last_grad_norm before set_grad_clip")
+        return norm[0], coef[0]
 
     def save_optimizer_state(self, path):
         rc = self.lib.cnnh_net_save_optimizer_state(self.h, str(path).encode())

@@ -440,6 +440,50 @@ int cnn_sgd_momentum_update(float* params, const float* grads, float* velocity, 
                             const uint32_t* decay_ranges, const uint32_t* decay_ranges_dev, size_t n_ranges, float* previous,
                             void* stream);
 
+/* Adam / AdamW over a range of the flat arena -- the update of torch.optim.Adam / AdamW with amsgrad off, in
+ * cnn_sgd_momentum_update's arithmetic: fp32, every product, sum, quotient and root rounded separately (no FMA), the quotient and the
+ * root correctly rounded, denormals kept.  Host scalars of the call:
+ *     om   = 1.f - lr * weight_decay   (two fp32 operations)       omb1 = 1.f - beta1, omb2 = 1.f - beta2   (fp32)
+ *     bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step))   ss   = (float)((double)lr / (1.0 - pow((double)beta1, (double)step)))
+ * Per element i:
+ *     gs  = grad_scale != 1 ? g * grad_scale : g
+ *     dec = decays(i) && weight_decay != 0
+ *     d   = (dec && !decoupled) ? gs + weight_decay * p : gs
+ *     p0  = (dec &&  decoupled) ? p * om : p
+ *     m'  = beta1 * m + omb1 * d
+ *     v'  = beta2 * v + omb2 * (d * d)
+ *     den = sqrt(v') / bc2s + eps
+ *     q   = m' / den
+ *     p'  = p0 - ss * q
+ * exp_avg (m), exp_avg_sq (v): n floats of state each, zero before the first step.  grad_scale, previous, decays(i), decay_ranges,
+ * decay_ranges_dev, n_ranges and the limit on n are cnn_sgd_momentum_update's.  Checked before any launch: beta1, beta2 in [0, 1),
+ * eps > 0, weight_decay >= 0, step >= 1, the range table.  One call is one kernel launch: 28 bytes per element, 32 with `previous`. */
+typedef struct cnn_adam_options {
+    float lr, beta1, beta2, eps, weight_decay;
+    int decoupled;        /* 0: Adam (L2 term added to the gradient)   1: AdamW (parameter shrunk by 1 - lr * wd) */
+    uint64_t step;        /* 1-based number of THIS step */
+} cnn_adam_options;
+int cnn_adam_update(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n, const cnn_adam_options* opt,
+                    float grad_scale, const uint32_t* decay_ranges, const uint32_t* decay_ranges_dev, size_t n_ranges,
+                    float* previous, void* stream);
+
+/* Clipping by the global L2 norm of one flat gradient range -- torch.nn.utils.clip_grad_norm_ (error_if_nonfinite=False) without a
+ * host round trip:
+ *     S      = sum_i (double)g[i] * (double)g[i]                (fp64: per-workgroup partials in `workspace`, summed in a fixed order,
+ *                                                                no floating-point atomics -- the same words from run to run)
+ *     norm   = (float)sqrt(S)
+ *     total  = grad_scale != 1 ? norm * grad_scale : norm       (fp32)
+ *     c      = max_norm / (total + 1e-6f)                       (fp32, two operations)
+ *     coef   = c < 1 ? c : 1                                    (a NaN total leaves coef = 1)
+ *     g[i]   = g[i] * coef                                      only when coef < 1; otherwise the range is not written
+ *     stats_dev[0] = total, stats_dev[1] = coef                 (device memory, two floats)
+ * workspace: device memory, 8-byte aligned, at least cnn_clip_grad_norm_workspace_bytes(n) bytes (never more than
+ * 8 * CNN_CLIP_MAX_BLOCKS).  max_norm > 0, n > 0 (checked).  Three kernel launches per call, the host never waits. */
+#define CNN_CLIP_MAX_BLOCKS 2048
+size_t cnn_clip_grad_norm_workspace_bytes(size_t n);
+int cnn_clip_grad_norm(float* grads, size_t n, float max_norm, float grad_scale, void* workspace, size_t workspace_bytes,
+                       float* stats_dev /* [2]: total norm, coefficient */, void* stream);
+
 /* AlexNet::grad_cam (alexnet.cpp:107-140) from the feature map of the chosen layer, [B][C][H][W] on the device:
  *   weights[b][o] = mean_i feature[b][o][i];  cam[b] = ReLU(sum_o weights[b][o] * feature[b][o]);  cam = (cam - min) / (max - min)
  * with min / max over the whole [B][H][W] tensor (:136-139).  cam: [B][H][W] floats (output).  image (nullable): H*W bytes, the 8-bit
