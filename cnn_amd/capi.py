@@ -42,6 +42,24 @@ class AdamOptions(C.Structure):
                 ("decoupled", C.c_int), ("step", C.c_uint64)]
 
 
+class LambOptions(C.Structure):
+    """mirror of cnn_lamb_options"""
+
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float),
+                ("step", C.c_uint64)]
+
+
+class LarsOptions(C.Structure):
+    """mirror of cnn_lars_options"""
+
+    _fields_ = [("lr", C.c_float), ("momentum", C.c_float), ("weight_decay", C.c_float), ("trust_coefficient", C.c_float), ("eps", C.c_float),
+                ("nesterov", C.c_int)]
+
+
+SEG_DECAY = 1  # CNN_SEG_DECAY
+SEG_ADAPT = 2  # CNN_SEG_ADAPT
+SEG_CHUNK = 1024  # CNN_SEG_CHUNK: elements of the flat range per workgroup of the layer-wise kernels
+
 CLIP_MAX_BLOCKS = 2048  # CNN_CLIP_MAX_BLOCKS: the largest grid of the clip kernels (workgroups of CLIP_BLOCK lanes, a float4 per lane)
 CLIP_BLOCK = 256
 
@@ -143,6 +161,12 @@ SIGNATURES = {
     "cnn_adam_update": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.POINTER(AdamOptions), C.c_float, _P, _P, C.c_size_t, _P, _P]),
     "cnn_clip_grad_norm_workspace_bytes": (C.c_size_t, [C.c_size_t]),
     "cnn_clip_grad_norm": (C.c_int, [_P, C.c_size_t, C.c_float, C.c_float, _P, C.c_size_t, _P, _P]),
+    "cnn_layerwise_create": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "cnn_layerwise_destroy": (C.c_int, [_P]),
+    "cnn_layerwise_stats": (C.c_int, [_P, C.POINTER(C.c_void_p)]),
+    "cnn_segment_norms": (C.c_int, [_P, _P, _P, _P]),
+    "cnn_lamb_update": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(LambOptions), C.c_float, _P, _P]),
+    "cnn_lars_update": (C.c_int, [_P, _P, _P, _P, C.POINTER(LarsOptions), C.c_float, _P, _P]),
     "cnn_stream_wait_event_local": (C.c_int, [_P, _P]),
     "cnn_stream_create_priority": (C.c_int, [C.POINTER(C.c_void_p), C.c_int]),
     "cnn_conv2d_backward_weight_pooled2_sgd_keep": (C.c_int, [_D, _P, _P, _P, _P, _P, _P, C.c_float, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P,
@@ -738,6 +762,81 @@ def clip_grad_norm(grads, max_norm, grad_scale=1.0, n=None):
           "cnn_clip_grad_norm")
     torch.cuda.current_stream().synchronize()  # (the workspace must outlive the kernels that use it)
     return stats
+
+
+class Layerwise:
+    """cnn_layerwise_create's handle: the flat range [0, n) cut into tensors.  bounds: n_segments + 1 ascending offsets from 0 to n;
+    flags: SEG_DECAY | SEG_ADAPT per segment.  The tensors passed to the methods hold at least n floats from their data pointer."""
+
+    def __init__(self, bounds, flags):
+        import numpy as np
+
+        self.bounds = np.ascontiguousarray(np.asarray(bounds, dtype=np.uint32).reshape(-1))
+        self.flags = np.ascontiguousarray(np.asarray(flags, dtype=np.uint32).reshape(-1))
+        if self.bounds.size != self.flags.size + 1:
+            raise CnnAmdError(f"Layerwise: {self.bounds.size} bounds for {self.flags.size} segments (one more is needed)")
+        self.n_segments = int(self.flags.size)
+        self.n = int(self.bounds[-1]) if self.bounds.size else 0
+        self.h = C.c_void_p()
+        check(load().cnn_layerwise_create(self.bounds.ctypes.data_as(C.c_void_p), self.flags.ctypes.data_as(C.c_void_p), self.n_segments,
+                                          C.byref(self.h)), "cnn_layerwise_create")
+
+    def close(self):
+        if self.h:
+            check(load().cnn_layerwise_destroy(self.h), "cnn_layerwise_destroy")
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _fits(self, what, *tensors):
+        _need_gpu(*tensors)
+        for t in tensors:
+            if t is not None and t.numel() < self.n:
+                raise CnnAmdError(f"{what}: a tensor of {t.numel()} floats, the segment table ends at n={self.n}")
+
+    def stats(self):
+        """(w_norm, u_norm, ratio) of the latest update call, copied to the host (synchronises)"""
+        import numpy as np
+        import torch
+
+        ptr = C.c_void_p()
+        check(load().cnn_layerwise_stats(self.h, C.byref(ptr)), "cnn_layerwise_stats")
+        host = torch.empty(3 * self.n_segments, dtype=torch.float32)
+        check(load().cnn_memcpy_d2h(C.c_void_p(host.data_ptr()), ptr, 4 * 3 * self.n_segments, _stream()), "cnn_memcpy_d2h")
+        torch.cuda.current_stream().synchronize()
+        a = host.numpy().reshape(3, self.n_segments)
+        return np.array(a[0]), np.array(a[1]), np.array(a[2])
+
+    def segment_norms(self, x, out=None):
+        """cnn_segment_norms -> a device tensor of n_segments floats"""
+        import torch
+
+        self._fits("segment_norms", x)
+        out = torch.empty(self.n_segments, dtype=torch.float32, device=x.device) if out is None else out
+        check(load().cnn_segment_norms(self.h, _ptr(x), _ptr(out), _stream()), "cnn_segment_norms")
+        return out
+
+    def lamb_update(self, params, grads, exp_avg, exp_avg_sq, update, lr, beta1=0.9, beta2=0.999, eps=1e-6, weight_decay=0.0, step=1,
+                    grad_scale=1.0, previous=None):
+        """cnn_lamb_update on device tensors (or views of them); update: n floats of scratch that receive r"""
+        self._fits("lamb_update", params, grads, exp_avg, exp_avg_sq, update, previous)
+        opt = LambOptions(float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step))
+        check(load().cnn_lamb_update(self.h, _ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(update), C.byref(opt),
+                                     float(grad_scale), _ptr(previous), _stream()), "cnn_lamb_update")
+        return params
+
+    def lars_update(self, params, grads, velocity, lr, momentum=0.0, weight_decay=0.0, trust_coefficient=1e-3, eps=1e-8, nesterov=False,
+                    grad_scale=1.0, previous=None):
+        """cnn_lars_update on device tensors (or views of them); velocity may be None with momentum == 0"""
+        self._fits("lars_update", params, grads, velocity, previous)
+        opt = LarsOptions(float(lr), float(momentum), float(weight_decay), float(trust_coefficient), float(eps), 1 if nesterov else 0)
+        check(load().cnn_lars_update(self.h, _ptr(params), _ptr(grads), _ptr(velocity), C.byref(opt), float(grad_scale), _ptr(previous),
+                                     _stream()), "cnn_lars_update")
+        return params
 
 
 def softmax_xent(logits, labels, want_probs=True):

@@ -297,6 +297,94 @@ __device__ __forceinline__ float adam_one(float p, float g, float& m, float& v, 
     return p0 - step;
 }
 
+// LAMB on one element (cnn_lamb_update, include/cnn_amd.h has the formula): Adam's moments with a per-tensor trust ratio, in
+// adam_one's arithmetic -- fp32, every product, sum, quotient and root rounded separately, correctly rounded quotients and roots,
+// denormals kept.  The step is two element passes with the segment norms in between.  Host scalars (cnn_lamb_update):
+//     omb1 = 1.f - beta1,  omb2 = 1.f - beta2                         (fp32)
+//     bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step))
+//     bc1  = (float)(1.0 - pow((double)beta1, (double)step))
+// First pass, `decay` = the element's segment has CNN_SEG_DECAY AND weight_decay != 0; the result r goes to the `update` scratch:
+//     gs  = scaled ? g * scale : g
+//     m'  = beta1 * m + omb1 * gs
+//     v'  = beta2 * v + omb2 * (gs * gs)
+//     den = sqrt(v') / bc2s + eps
+//     mh  = m' / bc1
+//     q   = mh / den
+//     r   = decay ? q + wd * p : q
+struct LambScalars {
+    float beta1, beta2, omb1, omb2, eps, wd, bc2s, bc1, scale;
+    bool scaled;
+};
+__device__ __forceinline__ float lamb_moments_one(float p, float g, float& m, float& v, const LambScalars& a, bool decay) {
+#pragma clang fp contract(off)
+    const float gs = a.scaled ? g * a.scale : g;
+    const float b1m = a.beta1 * m;
+    const float o1g = a.omb1 * gs;
+    const float mn = b1m + o1g;
+    const float b2v = a.beta2 * v;
+    const float gg = gs * gs;
+    const float o2g = a.omb2 * gg;
+    const float vn = b2v + o2g;
+    m = mn;
+    v = vn;
+    const float root = sqrtf(vn);
+    const float rb = root / a.bc2s;
+    const float den = rb + a.eps;
+    const float mh = mn / a.bc1;
+    const float q = mh / den;
+    float r = q;
+    if (decay) {
+        const float wp = a.wd * p;
+        r = q + wp;
+    }
+    return r;
+}
+// Second pass, ratio = the trust ratio of the element's segment (exactly 1 where it does not apply):
+//     t  = ratio * r
+//     p' = p - lr * t
+__device__ __forceinline__ float lamb_apply_one(float p, float r, float ratio, float lr) {
+#pragma clang fp contract(off)
+    const float t = ratio * r;
+    const float step = lr * t;
+    return p - step;
+}
+
+// LARS on one element (cnn_lars_update, include/cnn_amd.h has the formula): sgdm_one with the trust ratio of the element's segment
+// on the decayed gradient.  `decay` = the segment has CNN_SEG_DECAY AND weight_decay != 0.
+//     gs = scaled ? g * scale : g
+//     d  = decay ? gs + wd * p : gs
+//     dl = ratio * d
+//     momentum == 0 :  u = dl
+//     otherwise     :  v' = momentum * v + dl ;  u = nesterov ? dl + momentum * v' : v'
+//     p' = p - lr * u
+// x * 1.0f is exact: with ratio = 1 the result is sgdm_one's bit for bit.
+template <bool kMomentum>
+__device__ __forceinline__ float lars_one(float p, float g, float& v, float ratio, float lr, float momentum, float wd, float scale, bool scaled,
+                                          bool decay, bool nesterov) {
+#pragma clang fp contract(off)
+    const float gs = scaled ? g * scale : g;
+    float d = gs;
+    if (decay) {
+        const float wp = wd * p;
+        d = gs + wp;
+    }
+    const float dl = ratio * d;
+    float u = dl;
+    if (kMomentum) {
+        const float mv = momentum * v;
+        const float vn = mv + dl;
+        v = vn;
+        if (nesterov) {
+            const float mvn = momentum * vn;
+            u = dl + mvn;
+        } else {
+            u = vn;
+        }
+    }
+    const float step = lr * u;
+    return p - step;
+}
+
 constexpr int kWave = 64;         // CDNA wavefront
 constexpr int kNumXCD = 8;
 

@@ -94,6 +94,9 @@ public:
     // gamma / beta.  BatchNorm2D's moving statistics are never decayed.
     typedef std::vector<std::pair<size_t, size_t> > RangeList;
     virtual void decay_ranges(bool bias_and_norm, RangeList& out) const {}
+    // addition (Sequential::set_lamb / set_lars): the tensors inside this layer's parameter block as [begin, end) offsets that tile the
+    // whole block, in checkpoint order -- Conv2D / LinearLayer: weights, bias; BatchNorm2D: gamma, beta, moving_mean, moving_var.
+    virtual void param_tensors(RangeList& out) const {}
 };
 
 class ReLU;
@@ -177,6 +180,11 @@ public:
     size_t param_count() const override { return (size_t)get_params_num(); }
     void decay_ranges(bool bias_and_norm, RangeList& out) const override {
         out.emplace_back((size_t)0, bias_and_norm ? param_count() : (size_t)out_channels * params_for_one_kernel);
+    }
+    void param_tensors(RangeList& out) const override {
+        const size_t w = (size_t)out_channels * params_for_one_kernel;
+        out.emplace_back((size_t)0, w);
+        if (param_count() > w) out.emplace_back(w, param_count());
     }
     void bind_arena(data_type* params_dev, data_type* grads_dev) override;
     // ---- additions for fuse_pool_block ----
@@ -331,6 +339,10 @@ public:
     void decay_ranges(bool bias_and_norm, RangeList& out) const override {
         out.emplace_back((size_t)0, bias_and_norm ? param_count() : (size_t)in_channels * out_channels);
     }
+    void param_tensors(RangeList& out) const override {
+        out.emplace_back((size_t)0, (size_t)in_channels * out_channels);
+        out.emplace_back((size_t)in_channels * out_channels, param_count());
+    }
     void bind_arena(data_type* params_dev, data_type* grads_dev) override;
 };
 
@@ -392,6 +404,9 @@ public:
     void decay_ranges(bool bias_and_norm, RangeList& out) const override {  // gamma, beta -- never moving_mean / moving_var
         if (bias_and_norm) out.emplace_back((size_t)0, (size_t)2 * out_channels);
     }
+    void param_tensors(RangeList& out) const override {
+        for (size_t k = 0; k < 4; ++k) out.emplace_back(k * out_channels, (k + 1) * out_channels);
+    }
     void bind_arena(data_type* params_dev, data_type* grads_dev) override;
 };
 
@@ -426,7 +441,8 @@ public:
 //   * an optional RCCL communicator (set_comm): the batch is then sharded over `world` replicas, BatchNorm2D layers
 //     normalise over the GLOBAL batch (sync-BN) and update_gradients() sums the gradient arena over the replicas first;
 //   * an optional optimizer (set_optimizer): momentum, weight decay and Nesterov on the arena instead of the reference's w -= lr * g;
-//   * Adam / AdamW (set_adam) and clipping by the global gradient norm (set_grad_clip) on the same arena.
+//   * Adam / AdamW (set_adam) and clipping by the global gradient norm (set_grad_clip) on the same arena;
+//   * the layer-wise optimizers LAMB (set_lamb) and LARS (set_lars): a trust ratio per parameter tensor of the arena.
 class Sequential {
 public:
     bool print_info = false;
@@ -498,6 +514,19 @@ protected:
     void* clip_workspace = nullptr;    // cnn_clip_grad_norm's partial sums
     size_t clip_workspace_bytes = 0;
     data_type* clip_stats = nullptr;   // [2] on the device: total norm, coefficient of the latest clipped step
+    // ---- layer-wise optimizers (set_lamb / set_lars): the arena's step is ONE cnn_lamb_update / cnn_lars_update over the whole arena ----
+    enum LayerwiseMode { kLayerwiseOff = 0, kLamb = 1, kLars = 2 };
+    LayerwiseMode lw_mode = kLayerwiseOff;  // the optimizer set last was set_lamb() / set_lars()
+    void* lw_handle = nullptr;              // cnn_layerwise_create: the device table, the norm workspace, the statistics
+    std::vector<uint32_t> lw_bounds, lw_flags;  // the segment table of lw_handle (host copy)
+    bool lw_decay_bias_and_norm = false, lw_adapt_bias_and_norm = false;
+    data_type lamb_beta1 = 0, lamb_beta2 = 0, lamb_eps = 0, lamb_weight_decay = 0;  // (state: adam_m, adam_v, adam_t)
+    data_type lars_momentum = 0, lars_weight_decay = 0, lars_trust = 0, lars_eps = 0;  // (state: velocity)
+    bool lars_nesterov = false;
+    data_type* lw_update = nullptr;         // n_params floats of scratch: LAMB's r between its two passes
+    void build_segment_table(bool decay_bias_and_norm, bool adapt_bias_and_norm);
+    void ensure_adam_state();
+    void ensure_velocity();
     size_t front_block_params() const;
     // the SGD step on arena[lo, hi) (parameters, gradients, velocity, snapshot) on `on_stream`, plain or with the optimizer
     void step_arena(size_t lo, size_t hi, data_type learning_rate, data_type grad_scale, void* on_stream);
@@ -583,6 +612,36 @@ public:
     bool grad_clip_ever_on() const { return clip_stats != nullptr; }
     // total norm (and coefficient) of the latest clipped step; like last_loss() it synchronises.  Asserts when clipping was never on.
     data_type last_grad_norm(data_type* coef_out = nullptr);
+
+    // Layer-wise adaptive rates (include/cnn_amd.h: cnn_lamb_update, cnn_lars_update): LAMB is Adam with a trust ratio per parameter
+    // tensor, LARS momentum SGD with one.  The tensors are the layers' param_tensors() at their arena offsets.  CNN_SEG_DECAY follows
+    // set_optimizer's decay policy (decay_bias_and_norm); CNN_SEG_ADAPT is set on Conv2D / LinearLayer weights, with
+    // adapt_bias_and_norm on biases and BatchNorm2D's gamma / beta as well; the moving statistics never get either flag.  Call them
+    // after finalize(), any number of times.  LAMB uses Adam's state (exp_avg, exp_avg_sq, the step counter: allocated and zeroed by
+    // whichever of set_adam / set_lamb comes first, never zeroed by a switch), LARS uses the velocity arena.  set_optimizer, set_adam,
+    // set_lamb and set_lars replace each other -- the one called last is active, set_optimizer(0, 0) still returns to the plain step.
+    // THE PRICE: a trust ratio needs every gradient of a tensor before that tensor moves, so the step is one call over the whole
+    // arena inside update_gradients(lr, grad_scale) -- behind the all-reduce and the clip -- and the fused step tail (fused_tail)
+    // declines, as under clipping.  Under set_comm the state is per replica and nothing new is exchanged.
+    void set_lamb(data_type beta1 = 0.9, data_type beta2 = 0.999, data_type eps = 1e-6, data_type weight_decay = 0, bool decay_bias_and_norm = false,
+                  bool adapt_bias_and_norm = false);
+    void set_lars(data_type momentum, data_type weight_decay, data_type trust_coefficient = 1e-3, data_type eps = 1e-8, bool nesterov = false,
+                  bool decay_bias_and_norm = false, bool adapt_bias_and_norm = false);
+    bool layerwise_active() const { return lw_mode != kLayerwiseOff; }
+    bool lamb_is_active() const { return lw_mode == kLamb; }
+    bool lars_is_active() const { return lw_mode == kLars; }
+    size_t segment_count() const { return lw_flags.size(); }  // 0 before the first set_lamb() / set_lars()
+    void segment_table(std::vector<uint32_t>& bounds, std::vector<uint32_t>& flags) const {
+        bounds = lw_bounds;
+        flags = lw_flags;
+    }
+    // w_norm, u_norm, ratio of the latest layer-wise step (segment_count() values each); like last_grad_norm() it synchronises.
+    // false: no layer-wise optimizer was ever set.
+    bool trust_stats(std::vector<data_type>& w_norm, std::vector<data_type>& u_norm, std::vector<data_type>& ratio);
+    // With LAMB / LARS active save_optimizer_state writes two more formats.  "CNNALMB1": magic, n_params (uint64), step (uint64), beta1,
+    // beta2, eps, weight_decay (float), decay_bias_and_norm, adapt_bias_and_norm (uint32), then exp_avg, then exp_avg_sq.  "CNNALRS1":
+    // magic, n_params (uint64), momentum, weight_decay, trust_coefficient, eps (float), nesterov, decay_bias_and_norm,
+    // adapt_bias_and_norm (uint32), 4 bytes of padding, then the velocity arena.  load_optimizer_state recognises all four magics.
 
 protected:
     void invalidate_filter_images();  // (the part of parameters_changed() the container's own SGD step needs too)

@@ -141,6 +141,31 @@ int cnnh_net_get_adam_state(void* hv, float* m_host, float* v_host, uint64_t* st
     if (step_out) *step_out = h->net->adam_step();
     return 0;
 }
+// Sequential::set_lamb / set_lars, the segment table they build and the statistics of the latest layer-wise step
+void cnnh_net_set_lamb(void* hv, float beta1, float beta2, float eps, float weight_decay, int decay_bias_and_norm, int adapt_bias_and_norm) {
+    ((Handle*)hv)->net->set_lamb(beta1, beta2, eps, weight_decay, decay_bias_and_norm != 0, adapt_bias_and_norm != 0);
+}
+void cnnh_net_set_lars(void* hv, float momentum, float weight_decay, float trust_coefficient, float eps, int nesterov, int decay_bias_and_norm,
+                       int adapt_bias_and_norm) {
+    ((Handle*)hv)->net->set_lars(momentum, weight_decay, trust_coefficient, eps, nesterov != 0, decay_bias_and_norm != 0, adapt_bias_and_norm != 0);
+}
+size_t cnnh_net_segment_count(void* hv) { return ((Handle*)hv)->net->segment_count(); }
+int cnnh_net_layerwise_active(void* hv) { return ((Handle*)hv)->net->layerwise_active() ? 1 : 0; }
+// bounds_out: segment_count + 1 values, flags_out: segment_count values
+void cnnh_net_get_segments(void* hv, uint32_t* bounds_out, uint32_t* flags_out) {
+    std::vector<uint32_t> b, f;
+    ((Handle*)hv)->net->segment_table(b, f);
+    if (bounds_out) std::memcpy(bounds_out, b.data(), sizeof(uint32_t) * b.size());
+    if (flags_out) std::memcpy(flags_out, f.data(), sizeof(uint32_t) * f.size());
+}
+int cnnh_net_get_trust_stats(void* hv, float* w_norm, float* u_norm, float* ratio) {  // 1: no layer-wise optimizer was ever set
+    std::vector<float> w, u, r;
+    if (!((Handle*)hv)->net->trust_stats(w, u, r)) return 1;
+    if (w_norm) std::memcpy(w_norm, w.data(), sizeof(float) * w.size());
+    if (u_norm) std::memcpy(u_norm, u.data(), sizeof(float) * u.size());
+    if (ratio) std::memcpy(ratio, r.data(), sizeof(float) * r.size());
+    return 0;
+}
 void cnnh_net_set_grad_clip(void* hv, float max_norm) { ((Handle*)hv)->net->set_grad_clip(max_norm); }
 int cnnh_net_last_grad_norm(void* hv, float* norm_out, float* coef_out) {  // 1: clipping was never on
     Handle* h = (Handle*)hv;

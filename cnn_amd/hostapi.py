@@ -41,6 +41,12 @@ SIGNATURES = {
     "cnnh_net_adam_v_device": (C.c_void_p, [C.c_void_p]),
     "cnnh_net_get_adam_state": (C.c_int, [C.c_void_p, _F, _F, C.POINTER(C.c_uint64)]),
     "cnnh_net_set_grad_clip": (None, [C.c_void_p, C.c_float]),
+    "cnnh_net_set_lamb": (None, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int]),
+    "cnnh_net_set_lars": (None, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int]),
+    "cnnh_net_segment_count": (C.c_size_t, [C.c_void_p]),
+    "cnnh_net_layerwise_active": (C.c_int, [C.c_void_p]),
+    "cnnh_net_get_segments": (None, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cnnh_net_get_trust_stats": (C.c_int, [C.c_void_p, _F, _F, _F]),
     "cnnh_net_last_grad_norm": (C.c_int, [C.c_void_p, _F, _F]),
     "cnnh_net_save_optimizer_state": (C.c_int, [C.c_void_p, C.c_char_p]),
     "cnnh_net_load_optimizer_state": (C.c_int, [C.c_void_p, C.c_char_p]),
@@ -195,6 +201,42 @@ class HostNet:
         if self.lib.cnnh_net_last_grad_norm(self.h, _fp(norm), _fp(coef)) != 0:
             raise capi.CnnAmdError("last_grad_norm before set_grad_clip")
         return norm[0], coef[0]
+
+    def set_lamb(self, beta1=0.9, beta2=0.999, eps=1e-6, weight_decay=0.0, decay_bias_and_norm=False, adapt_bias_and_norm=False):
+        """Sequential::set_lamb: LAMB (Adam's moments, a trust ratio per parameter tensor) for every later step on the arena; shares
+        the moments and the step counter with set_adam.  A layer-wise step is one call over the whole arena: no fused step tail."""
+        self.lib.cnnh_net_set_lamb(self.h, float(beta1), float(beta2), float(eps), float(weight_decay), 1 if decay_bias_and_norm else 0,
+                                   1 if adapt_bias_and_norm else 0)
+
+    def set_lars(self, momentum, weight_decay=0.0, trust_coefficient=1e-3, eps=1e-8, nesterov=False, decay_bias_and_norm=False,
+                 adapt_bias_and_norm=False):
+        """Sequential::set_lars: LARS (momentum SGD, a trust ratio per parameter tensor) for every later step on the arena; shares the
+        velocity with set_optimizer"""
+        self.lib.cnnh_net_set_lars(self.h, float(momentum), float(weight_decay), float(trust_coefficient), float(eps), 1 if nesterov else 0,
+                                   1 if decay_bias_and_norm else 0, 1 if adapt_bias_and_norm else 0)
+
+    def layerwise_active(self):
+        return self.lib.cnnh_net_layerwise_active(self.h) != 0
+
+    def segment_count(self):
+        """number of parameter tensors in the segment table; 0 before the first set_lamb / set_lars"""
+        return int(self.lib.cnnh_net_segment_count(self.h))
+
+    def segment_table(self):
+        """(bounds, flags): segment_count + 1 ascending arena offsets from 0 to n_params, capi.SEG_DECAY | capi.SEG_ADAPT per tensor"""
+        ns = self.segment_count()
+        bounds, flags = np.zeros(ns + 1, np.uint32), np.zeros(ns, np.uint32)
+        if ns:
+            self.lib.cnnh_net_get_segments(self.h, bounds.ctypes.data_as(C.c_void_p), flags.ctypes.data_as(C.c_void_p))
+        return bounds, flags
+
+    def trust_stats(self):
+        """(w_norm, u_norm, ratio) per parameter tensor of the latest layer-wise step; synchronises"""
+        ns = self.segment_count()
+        w, u, r = (np.zeros(max(ns, 1), np.float32) for _ in range(3))
+        if self.lib.cnnh_net_get_trust_stats(self.h, _fp(w), _fp(u), _fp(r)) != 0:
+            raise capi.CnnAmdError("trust_stats before set_lamb / set_lars")
+        return w[:ns], u[:ns], r[:ns]
 
     def save_optimizer_state(self, path):
         rc = self.lib.cnnh_net_save_optimizer_state(self.h, str(path).encode())

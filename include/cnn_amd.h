@@ -484,6 +484,68 @@ size_t cnn_clip_grad_norm_workspace_bytes(size_t n);
 int cnn_clip_grad_norm(float* grads, size_t n, float max_norm, float grad_scale, void* workspace, size_t workspace_bytes,
                        float* stats_dev /* [2]: total norm, coefficient */, void* stream);
 
+/* ---- layer-wise optimizers: LAMB and LARS over one flat arena cut into tensors ("segments") --------------------------------------
+ * A handle describes how the flat range [0, n) is cut into n_segments tensors and owns the device copy of that table, the workspace
+ * of the segmented norm and a device statistics array; it is created once and reused every step (no per-step host-to-device copy).
+ *   seg_bounds : HOST array of n_segments + 1 values, seg_bounds[0] = 0, strictly ascending, the last one is n (<= 2^32 - 257)
+ *   seg_flags  : HOST array of n_segments values, any of CNN_SEG_DECAY | CNN_SEG_ADAPT
+ * Both are checked; a bad table is an error status with a message and nothing is allocated.
+ *
+ * Segment norms: norm[s] = (float)sqrt( sum over the segment of (double)x[i] * (double)x[i] ).  The flat range is cut into chunks of
+ * CNN_SEG_CHUNK elements, one workgroup each; a workgroup reduces every (segment, chunk) overlap separately into that overlap's own
+ * fp64 slot, a finish kernel adds each segment's slots in ascending order.  No floating-point atomics, and the order of every sum
+ * depends on the table alone -- not on the grid, not on the pointers' alignment: the same words from run to run.  Two launches.
+ *
+ * cnn_lamb_update (You et al., "Large Batch Optimization for Deep Learning"), in cnn_adam_update's arithmetic: fp32, every product,
+ * sum, quotient and root rounded separately (no FMA), quotients and roots correctly rounded, denormals kept.  Host scalars:
+ *     omb1 = 1.f - beta1, omb2 = 1.f - beta2 (fp32)     bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step))
+ *     bc1  = (float)(1.0 - pow((double)beta1, (double)step))
+ * Per element i of segment s:
+ *     gs  = grad_scale != 1 ? g * grad_scale : g
+ *     m'  = beta1 * m + omb1 * gs          v' = beta2 * v + omb2 * (gs * gs)
+ *     den = sqrt(v') / bc2s + eps          mh = m' / bc1          q = mh / den
+ *     r   = (DECAY(s) && weight_decay != 0) ? q + weight_decay * p : q                    (update[i] receives r)
+ *     w_norm[s] = norm of p (before the step) over s ;  u_norm[s] = norm of r over s
+ *     ratio[s]  = (ADAPT(s) && w_norm[s] > 0 && u_norm[s] > 0) ? w_norm[s] / u_norm[s] : 1
+ *     t = ratio[s] * r ;  p' = p - lr * t ;  previous[i] = p   (previous is nullable)
+ * exp_avg (m), exp_avg_sq (v), params are written, grads is not.  Three launches: moments + r + the partial sums of both norms in
+ * one pass (28 B per element), the finish, the apply pass (12 B per element, 16 with previous).
+ *
+ * cnn_lars_update (You et al., "Large Batch Training of Convolutional Networks") on cnn_sgd_momentum_update's arithmetic:
+ *     gs as above;  g_norm[s] = norm of g over s;  gnt = grad_scale != 1 ? g_norm[s] * grad_scale : g_norm[s]   (stored as u_norm[s])
+ *     wds = DECAY(s) ? weight_decay : 0
+ *     ratio[s] = (ADAPT(s) && w_norm[s] > 0 && gnt > 0) ? (trust_coefficient * w_norm[s]) / ((gnt + wds * w_norm[s]) + eps) : 1
+ *     d  = (DECAY(s) && weight_decay != 0) ? gs + weight_decay * p : gs ;   dl = ratio[s] * d
+ *     momentum == 0 :  u = dl        otherwise :  v' = momentum * v + dl ;  u = nesterov ? dl + momentum * v' : v'
+ *     p' = p - lr * u
+ * With no CNN_SEG_ADAPT flag in the table every ratio is exactly 1 and the result equals cnn_sgd_momentum_update's, with the DECAY
+ * segments as its ranges, bit for bit.  Three launches: the partial sums of both norms (8 B per element), the finish, the step (20 B
+ * per element, 24 with previous).
+ *
+ * Both: the host never waits and nothing is copied; pointers that are not 16-byte aligned take scalar loads and stores with the
+ * same results.  Checked before any launch: the handle, null pointers, beta1, beta2 in [0, 1), eps > 0, weight_decay >= 0,
+ * momentum >= 0, trust_coefficient > 0, step >= 1.  cnn_layerwise_stats: device pointer to 3 * n_segments floats of the latest update
+ * call -- w_norm[s], then u_norm[s], then ratio[s] (three arrays). */
+#define CNN_SEG_DECAY 1u   /* weight decay applies to this segment */
+#define CNN_SEG_ADAPT 2u   /* the trust ratio applies to this segment (otherwise its ratio is exactly 1) */
+#define CNN_SEG_CHUNK 1024
+int cnn_layerwise_create(const uint32_t* seg_bounds, const uint32_t* seg_flags, size_t n_segments, void** handle);
+int cnn_layerwise_destroy(void* handle);
+int cnn_layerwise_stats(void* handle, float** stats_dev);
+int cnn_segment_norms(void* handle, const float* x, float* norms_dev, void* stream);
+typedef struct cnn_lamb_options {
+    float lr, beta1, beta2, eps, weight_decay;
+    uint64_t step;        /* 1-based number of THIS step */
+} cnn_lamb_options;
+int cnn_lamb_update(void* handle, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* update /* n floats of scratch */,
+                    const cnn_lamb_options* opt, float grad_scale, float* previous /* nullable */, void* stream);
+typedef struct cnn_lars_options {
+    float lr, momentum, weight_decay, trust_coefficient, eps;
+    int nesterov;         /* 0 / 1 */
+} cnn_lars_options;
+int cnn_lars_update(void* handle, float* params, const float* grads, float* velocity /* NULL allowed when momentum == 0 */,
+                    const cnn_lars_options* opt, float grad_scale, float* previous /* nullable */, void* stream);
+
 /* AlexNet::grad_cam (alexnet.cpp:107-140) from the feature map of the chosen layer, [B][C][H][W] on the device:
  *   weights[b][o] = mean_i feature[b][o][i];  cam[b] = ReLU(sum_o weights[b][o] * feature[b][o]);  cam = (cam - min) / (max - min)
  * with min / max over the whole [B][H][W] tensor (:136-139).  cam: [B][H][W] floats (output).  image (nullable): H*W bytes, the 8-bit
