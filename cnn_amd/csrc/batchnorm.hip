@@ -673,8 +673,6 @@ int make_geo(int B, int C, int H, int W, Geo* q) {
     return CNN_AMD_OK;
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 #define BN_TAG "B%d C%d %dx%d", B, C, H, W

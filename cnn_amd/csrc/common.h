@@ -5,6 +5,7 @@
 
 #include <atomic>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 
 #include "cnn_amd.h"
@@ -400,6 +401,9 @@ __device__ __forceinline__ unsigned xcd_swizzle(unsigned bid, unsigned nb) {
 }
 
 inline unsigned ceil_div(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
+
+// the float4 kernels need 16-byte aligned pointers; the entries fall back to their scalar forms (or refuse) otherwise
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // grid for HBM-bound streaming kernels: enough workgroups to fill 256 CUs x 8, grid-stride the rest
 inline unsigned stream_grid(size_t work_items, int block) {

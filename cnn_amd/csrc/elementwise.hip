@@ -168,8 +168,7 @@ __global__ __launch_bounds__(kBlock) void sgdm_vec(float4* __restrict__ p, const
         const float* gs = (const float*)g;
         float* vs = (float*)v;
         const size_t i = n4 * 4 + threadIdx.x;
-        int k = a.nr ? first_open_range(r, a.nr, (uint32_t)i) : 0;
-        const bool decay = a.nr && in_range_from(r, a.nr, k, (uint32_t)i);
+        const bool decay = decays_at(r, a.nr, i);
         float vel = kMomentum ? vs[i] : 0.f;
         if (keep) ((float*)keep)[i] = ps[i];
         ps[i] = sgdm_one<kMomentum>(ps[i], gs[i], vel, a.lr, a.momentum, a.wd, a.scale, a.scaled, decay, a.nesterov);
@@ -194,8 +193,7 @@ template <bool kMomentum, class Ranges>
 __global__ __launch_bounds__(kBlock) void sgdm_scalar(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ v,
                                                       size_t begin, size_t n, const SgdmArgs a, float* __restrict__ keep, const Ranges r) {
     for (size_t i = begin + (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
-        int k = a.nr ? first_open_range(r, a.nr, (uint32_t)i) : 0;
-        const bool decay = a.nr && in_range_from(r, a.nr, k, (uint32_t)i);
+        const bool decay = decays_at(r, a.nr, i);
         float vel = kMomentum ? v[i] : 0.f;
         if (keep) keep[i] = p[i];
         p[i] = sgdm_one<kMomentum>(p[i], g[i], vel, a.lr, a.momentum, a.wd, a.scale, a.scaled, decay, a.nesterov);
@@ -395,46 +393,67 @@ __global__ __launch_bounds__(kBlock) void softmax_xent_kernel(const float* __res
     if (threadIdx.x == 0 && loss_sum) loss_sum[0] = -running;
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-// one launch of the momentum step (the scalar kernel alone when a pointer is not 16-byte aligned, like cnn_sgd_update_keep)
-template <bool kMomentum, class Ranges>
-int launch_sgdm(float* params, const float* grads, float* velocity, size_t n, const SgdmArgs& a, float* previous, const Ranges& r,
-                hipStream_t s) {
-    const bool vec = aligned16(params) && aligned16(grads) && (!kMomentum || aligned16(velocity)) &&
-                     (previous == nullptr || aligned16(previous)) && n >= 4;
-    if (vec) {
-        const size_t n4 = n / 4;
-        CNN_KLAUNCH(s, "sgdm_vec",
-                    (sgdm_vec<kMomentum, Ranges><<<stream_grid(n4, kBlock), kBlock, 0, s>>>((float4*)params, (const float4*)grads, (float4*)velocity,
-                                                                                         n4, n, a, (float4*)previous, r)),
-                    "n=%zu ranges=%d", n, a.nr);
-    } else {
-        CNN_KLAUNCH(s, "sgdm_scalar",
-                    (sgdm_scalar<kMomentum, Ranges><<<stream_grid(n, kBlock), kBlock, 0, s>>>(params, grads, velocity, 0, n, a, previous, r)),
-                    "tail n=%zu ranges=%d", n, a.nr);
+// ---- host side shared by the two arena update rules (cnn_sgd_momentum_update, cnn_adam_update) ------------------------------------
+// the decay-range table of an update entry: n fits the 32-bit table, the ranges are there, sorted, disjoint, non-empty and inside [0, n)
+int check_decay_ranges(const char* entry, size_t n, const uint32_t* decay_ranges, const uint32_t* decay_ranges_dev, size_t n_ranges) {
+    CNN_REQUIRE(n <= (size_t)0xFFFFFFFFu - 4 * kWave, "%s: n=%zu exceeds the 32-bit range table: step the arena in pieces", entry, n);
+    CNN_REQUIRE(n_ranges <= n && (n_ranges == 0 || decay_ranges), "%s: null decay_ranges / n_ranges=%zu with n=%zu", entry, n_ranges, n);
+    CNN_REQUIRE(n_ranges <= (size_t)CNN_SGD_INLINE_RANGES || decay_ranges_dev, "%s: %zu ranges (more than CNN_SGD_INLINE_RANGES) need decay_ranges_dev",
+                entry, n_ranges);
+    uint32_t prev_end = 0;
+    for (size_t k = 0; k < n_ranges; ++k) {
+        const uint32_t b = decay_ranges[2 * k], e = decay_ranges[2 * k + 1];
+        CNN_REQUIRE(b >= prev_end && b < e && (size_t)e <= n, "%s: range %zu = [%u, %u) is empty, unsorted, overlapping or beyond n=%zu", entry, k, b, e, n);
+        prev_end = e;
     }
     return CNN_AMD_OK;
 }
 
-// one launch of the Adam step (the scalar kernel alone when a pointer is not 16-byte aligned)
+// calls launch(ranges) with the first nr ranges by value in the kernel arguments, or with the device table beyond CNN_SGD_INLINE_RANGES
+template <class Launch>
+int with_ranges(int nr, const uint32_t* decay_ranges, const uint32_t* decay_ranges_dev, const Launch& launch) {
+    if (nr > CNN_SGD_INLINE_RANGES) return launch(DeviceRanges{decay_ranges_dev});
+    InlineRanges r;
+    for (int k = 0; k < 2 * CNN_SGD_INLINE_RANGES; ++k) r.be[k] = k < 2 * nr ? decay_ranges[k] : 0u;
+    return launch(r);
+}
+
+// one launch of an update rule over n elements: the float4 kernel (its scalar tail rides in workgroup 0) when every pointer is 16-byte
+// aligned, the scalar kernel alone otherwise, like cnn_sgd_update_keep.  vec(grid, n4) / scalar(grid) launch and return nothing.
+template <class Vec, class Scalar>
+int launch_update(hipStream_t s, const char* vec_name, const char* scalar_name, bool all_aligned, size_t n, int nr, const Vec& vec,
+                  const Scalar& scalar) {
+    if (all_aligned && n >= 4) {
+        const size_t n4 = n / 4;
+        CNN_KLAUNCH(s, vec_name, vec(stream_grid(n4, kBlock), n4), "n=%zu ranges=%d", n, nr);
+    } else {
+        CNN_KLAUNCH(s, scalar_name, scalar(stream_grid(n, kBlock)), "tail n=%zu ranges=%d", n, nr);
+    }
+    return CNN_AMD_OK;
+}
+
+template <bool kMomentum, class Ranges>
+int launch_sgdm(float* params, const float* grads, float* velocity, size_t n, const SgdmArgs& a, float* previous, const Ranges& r,
+                hipStream_t s) {
+    const bool aligned = aligned16(params) && aligned16(grads) && (!kMomentum || aligned16(velocity)) && (previous == nullptr || aligned16(previous));
+    return launch_update(
+        s, "sgdm_vec", "sgdm_scalar", aligned, n, a.nr,
+        [&](unsigned grid, size_t n4) {
+            sgdm_vec<kMomentum, Ranges><<<grid, kBlock, 0, s>>>((float4*)params, (const float4*)grads, (float4*)velocity, n4, n, a, (float4*)previous, r);
+        },
+        [&](unsigned grid) { sgdm_scalar<kMomentum, Ranges><<<grid, kBlock, 0, s>>>(params, grads, velocity, 0, n, a, previous, r); });
+}
+
 template <class Ranges>
 int launch_adam(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n, const AdamArgs& a, float* previous,
                 const Ranges& r, hipStream_t s) {
-    const bool vec = aligned16(params) && aligned16(grads) && aligned16(exp_avg) && aligned16(exp_avg_sq) &&
-                     (previous == nullptr || aligned16(previous)) && n >= 4;
-    if (vec) {
-        const size_t n4 = n / 4;
-        CNN_KLAUNCH(s, "adam_vec",
-                    (adam_vec<Ranges><<<stream_grid(n4, kBlock), kBlock, 0, s>>>((float4*)params, (const float4*)grads, (float4*)exp_avg,
-                                                                              (float4*)exp_avg_sq, n4, n, a, (float4*)previous, r)),
-                    "n=%zu ranges=%d", n, a.nr);
-    } else {
-        CNN_KLAUNCH(s, "adam_scalar",
-                    (adam_scalar<Ranges><<<stream_grid(n, kBlock), kBlock, 0, s>>>(params, grads, exp_avg, exp_avg_sq, 0, n, a, previous, r)),
-                    "tail n=%zu ranges=%d", n, a.nr);
-    }
-    return CNN_AMD_OK;
+    const bool aligned = aligned16(params) && aligned16(grads) && aligned16(exp_avg) && aligned16(exp_avg_sq) && (previous == nullptr || aligned16(previous));
+    return launch_update(
+        s, "adam_vec", "adam_scalar", aligned, n, a.nr,
+        [&](unsigned grid, size_t n4) {
+            adam_vec<Ranges><<<grid, kBlock, 0, s>>>((float4*)params, (const float4*)grads, (float4*)exp_avg, (float4*)exp_avg_sq, n4, n, a, (float4*)previous, r);
+        },
+        [&](unsigned grid) { adam_scalar<Ranges><<<grid, kBlock, 0, s>>>(params, grads, exp_avg, exp_avg_sq, 0, n, a, previous, r); });
 }
 
 // the scalars of one Adam step that do not depend on the element (common.h, adam_one): plain host arithmetic, every fp32 operation
@@ -600,6 +619,8 @@ int cnn_sgd_update_keep(float* params, const float* grads, size_t n, float lr, f
     return CNN_AMD_OK;
 }
 
+// (the two update entries differ in when n == 0 returns: this one returns OK before it looks at any argument, cnn_adam_update validates
+// its arguments first.  Both orders are what the entries have always done; callers may rely on either.)
 int cnn_sgd_momentum_update(float* params, const float* grads, float* velocity, size_t n, const cnn_sgd_options* opt, float grad_scale,
                             const uint32_t* decay_ranges, const uint32_t* decay_ranges_dev, size_t n_ranges, float* previous,
                             void* stream) {
@@ -608,17 +629,7 @@ int cnn_sgd_momentum_update(float* params, const float* grads, float* velocity, 
     CNN_REQUIRE(opt->momentum >= 0.f && opt->weight_decay >= 0.f, "cnn_sgd_momentum_update: momentum=%g weight_decay=%g", (double)opt->momentum,
                 (double)opt->weight_decay);
     CNN_REQUIRE(velocity || opt->momentum == 0.f, "cnn_sgd_momentum_update: null velocity with momentum=%g", (double)opt->momentum);
-    CNN_REQUIRE(n <= (size_t)0xFFFFFFFFu - 4 * kWave, "cnn_sgd_momentum_update: n=%zu exceeds the 32-bit range table: step the arena in pieces", n);
-    CNN_REQUIRE(n_ranges <= n && (n_ranges == 0 || decay_ranges), "cnn_sgd_momentum_update: null decay_ranges / n_ranges=%zu with n=%zu", n_ranges, n);
-    CNN_REQUIRE(n_ranges <= (size_t)CNN_SGD_INLINE_RANGES || decay_ranges_dev,
-                "cnn_sgd_momentum_update: %zu ranges (more than CNN_SGD_INLINE_RANGES) need decay_ranges_dev", n_ranges);
-    uint32_t prev_end = 0;
-    for (size_t k = 0; k < n_ranges; ++k) {
-        const uint32_t b = decay_ranges[2 * k], e = decay_ranges[2 * k + 1];
-        CNN_REQUIRE(b >= prev_end && b < e && (size_t)e <= n, "cnn_sgd_momentum_update: range %zu = [%u, %u) is empty, unsorted, overlapping or beyond n=%zu", k,
-                    b, e, n);
-        prev_end = e;
-    }
+    if (int rc = check_decay_ranges("cnn_sgd_momentum_update", n, decay_ranges, decay_ranges_dev, n_ranges)) return rc;
     hipStream_t s = as_stream(stream);
     SgdmArgs a;
     a.lr = opt->lr;
@@ -629,13 +640,9 @@ int cnn_sgd_momentum_update(float* params, const float* grads, float* velocity, 
     a.nesterov = opt->nesterov != 0;
     a.nr = opt->weight_decay != 0.f ? (int)n_ranges : 0;
     const bool mom = opt->momentum != 0.f;
-    if (a.nr > CNN_SGD_INLINE_RANGES) {
-        const DeviceRanges r{decay_ranges_dev};
+    return with_ranges(a.nr, decay_ranges, decay_ranges_dev, [&](const auto& r) {
         return mom ? launch_sgdm<true>(params, grads, velocity, n, a, previous, r, s) : launch_sgdm<false>(params, grads, velocity, n, a, previous, r, s);
-    }
-    InlineRanges r;
-    for (int k = 0; k < 2 * CNN_SGD_INLINE_RANGES; ++k) r.be[k] = k < 2 * a.nr ? decay_ranges[k] : 0u;
-    return mom ? launch_sgdm<true>(params, grads, velocity, n, a, previous, r, s) : launch_sgdm<false>(params, grads, velocity, n, a, previous, r, s);
+    });
 }
 
 int cnn_adam_update(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n, const cnn_adam_options* opt,
@@ -647,29 +654,14 @@ int cnn_adam_update(float* params, const float* grads, float* exp_avg, float* ex
     CNN_REQUIRE(opt->eps > 0.f, "cnn_adam_update: eps=%g must be positive", (double)opt->eps);
     CNN_REQUIRE(opt->weight_decay >= 0.f, "cnn_adam_update: weight_decay=%g", (double)opt->weight_decay);
     CNN_REQUIRE(opt->step != 0, "cnn_adam_update: step=0 (the number of this step, counted from 1)");
-    CNN_REQUIRE(n <= (size_t)0xFFFFFFFFu - 4 * kWave, "cnn_adam_update: n=%zu exceeds the 32-bit range table: step the arena in pieces", n);
-    CNN_REQUIRE(n_ranges <= n && (n_ranges == 0 || decay_ranges), "cnn_adam_update: null decay_ranges / n_ranges=%zu with n=%zu", n_ranges, n);
-    CNN_REQUIRE(n_ranges <= (size_t)CNN_SGD_INLINE_RANGES || decay_ranges_dev,
-                "cnn_adam_update: %zu ranges (more than CNN_SGD_INLINE_RANGES) need decay_ranges_dev", n_ranges);
-    uint32_t prev_end = 0;
-    for (size_t k = 0; k < n_ranges; ++k) {
-        const uint32_t b = decay_ranges[2 * k], e = decay_ranges[2 * k + 1];
-        CNN_REQUIRE(b >= prev_end && b < e && (size_t)e <= n, "cnn_adam_update: range %zu = [%u, %u) is empty, unsorted, overlapping or beyond n=%zu", k, b,
-                    e, n);
-        prev_end = e;
-    }
+    if (int rc = check_decay_ranges("cnn_adam_update", n, decay_ranges, decay_ranges_dev, n_ranges)) return rc;
     if (n == 0) return CNN_AMD_OK;
     hipStream_t s = as_stream(stream);
     AdamArgs a;
     a.s = adam_scalars(*opt, grad_scale);
     a.nr = opt->weight_decay != 0.f ? (int)n_ranges : 0;
-    if (a.nr > CNN_SGD_INLINE_RANGES) {
-        const DeviceRanges r{decay_ranges_dev};
-        return launch_adam(params, grads, exp_avg, exp_avg_sq, n, a, previous, r, s);
-    }
-    InlineRanges r;
-    for (int k = 0; k < 2 * CNN_SGD_INLINE_RANGES; ++k) r.be[k] = k < 2 * a.nr ? decay_ranges[k] : 0u;
-    return launch_adam(params, grads, exp_avg, exp_avg_sq, n, a, previous, r, s);
+    return with_ranges(a.nr, decay_ranges, decay_ranges_dev,
+                       [&](const auto& r) { return launch_adam(params, grads, exp_avg, exp_avg_sq, n, a, previous, r, s); });
 }
 
 size_t cnn_clip_grad_norm_workspace_bytes(size_t n) {

@@ -371,7 +371,6 @@ inline Layerwise* as_handle(void* h) {
     Layerwise* lw = (Layerwise*)h;
     return (lw != nullptr && lw->magic == kMagic) ? lw : nullptr;
 }
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 template <class Op>
 int launch_walk(const Layerwise* lw, const Op& op, bool vec, const char* name, hipStream_t s) {

@@ -440,9 +440,9 @@ public:
 //   * filter preparation hoisted out of the per-layer calls (cnn_conv2d_prepare_filters), redone after every parameter change;
 //   * an optional RCCL communicator (set_comm): the batch is then sharded over `world` replicas, BatchNorm2D layers
 //     normalise over the GLOBAL batch (sync-BN) and update_gradients() sums the gradient arena over the replicas first;
-//   * an optional optimizer (set_optimizer): momentum, weight decay and Nesterov on the arena instead of the reference's w -= lr * g;
-//   * Adam / AdamW (set_adam) and clipping by the global gradient norm (set_grad_clip) on the same arena;
-//   * the layer-wise optimizers LAMB (set_lamb) and LARS (set_lars): a trust ratio per parameter tensor of the arena.
+//   * an optional optimizer on the arena instead of the reference's w -= lr * g -- one of momentum SGD (set_optimizer), Adam / AdamW
+//     (set_adam), LAMB (set_lamb), LARS (set_lars); the setter called last is the active kind (OptKind, optimizer.cpp);
+//   * clipping by the global gradient norm (set_grad_clip) in front of whichever step is active.
 class Sequential {
 public:
     bool print_info = false;
@@ -488,47 +488,76 @@ protected:
     // go out on the communication stream behind an event.  Small arenas (the reference net: 445 KB, latency-bound) stay one call.
     size_t bucket_floats = (size_t)2 << 20;
     void flush_bucket(size_t lo, size_t hi);
-    // ---- optimizer (set_optimizer): the arena's step is cnn_sgd_momentum_update instead of cnn_sgd_update_keep ----
-    bool opt_active = false;           // false: the reference's plain step, every launch as without an optimizer
-    data_type opt_momentum = 0, opt_weight_decay = 0;
-    bool opt_nesterov = false, opt_decay_bias_and_norm = false;
-    data_type* velocity = nullptr;     // n_params floats, allocated (zeroed) by the first set_optimizer()
+    // ---- the optimizer (optimizer.cpp): ONE kind says which step the container takes on its arena; each kind has its options, and
+    // all of them share one block of state.  set_optimizer / set_adam / set_lamb / set_lars replace each other by assigning the kind.
+    enum class OptKind {
+        kPlain,  // the reference's w -= lr * g (cnn_sgd_update_keep): every launch as without an optimizer
+        kSgdm,   // cnn_sgd_momentum_update on arena ranges
+        kAdam,   // cnn_adam_update on arena ranges
+        kLamb,   // ONE cnn_lamb_update over the whole arena
+        kLars,   // ONE cnn_lars_update over the whole arena
+    };
+    OptKind opt_kind = OptKind::kPlain;
+    // what the call sites ask of the kind:
+    // the step is more than the front block's in-kernel plain SGD -- the fused tail steps that block with the arena kernel, no TAIL_BEHIND_BLOCK
+    bool step_beyond_plain_sgd() const { return opt_kind != OptKind::kPlain; }
+    // a trust ratio needs every gradient of a tensor before that tensor moves: one call over the whole arena, never range steps
+    bool step_needs_whole_tensors() const { return opt_kind == OptKind::kLamb || opt_kind == OptKind::kLars; }
+    // the step reads and writes exp_avg / exp_avg_sq and carries the step counter
+    bool step_uses_adam_moments() const { return opt_kind == OptKind::kAdam || opt_kind == OptKind::kLamb; }
+    // the options of each kind as the setter left them: the C ABI's options struct (lr -- and step -- are filled in per step) plus
+    // the policy bits that shape the kind's table.  A kind's options survive while another kind is active.
+    struct SgdmOptions {
+        cnn_sgd_options abi = {0, 0, 0, 0};
+        bool decay_bias_and_norm = false;
+    } sgdm_opt;  // (also what a kPlain net's state file carries: momentum 0, weight decay 0)
+    struct AdamOptions {
+        cnn_adam_options abi = {0, 0, 0, 0, 0, 0, 0};  // (abi.decoupled: Adam's L2 term or AdamW)
+        bool decay_bias_and_norm = false;
+    } adam_opt;
+    struct LambOptions {
+        cnn_lamb_options abi = {0, 0, 0, 0, 0, 0};
+        bool decay_bias_and_norm = false, adapt_bias_and_norm = false;
+    } lamb_opt;
+    struct LarsOptions {
+        cnn_lars_options abi = {0, 0, 0, 0, 0, 0};
+        bool decay_bias_and_norm = false, adapt_bias_and_norm = false;
+    } lars_opt;
     struct DecayTable {                // the decayed index ranges inside arena[lo, hi), relative to lo (begin, end pairs)
         size_t lo = 0, hi = 0;
         std::vector<uint32_t> host;
         uint32_t* dev = nullptr;       // device copy, only for tables of more than CNN_SGD_INLINE_RANGES ranges
     };
-    DecayTable decay_tables[3];        // the three ranges the container steps: the whole arena, behind the front block, the front block
+    // Every arena is n_params floats, allocated and zeroed by the first setter that needs it, never freed or zeroed by a switch.
+    struct OptState {
+        data_type* velocity = nullptr;                 // kSgdm, kLars (and allocated by set_optimizer(0, 0))
+        data_type* exp_avg = nullptr;                  // kAdam, kLamb
+        data_type* exp_avg_sq = nullptr;               // kAdam, kLamb
+        uint64_t step = 0;                             // kAdam, kLamb: container steps taken under either (the next launch carries step after its increment)
+        data_type* lamb_update = nullptr;              // kLamb: scratch, r between its two passes
+        // kSgdm, kAdam: the three ranges the container steps -- the whole arena, behind the front block, the front block; rebuilt by
+        // set_optimizer / set_adam, left alone by set_lamb / set_lars
+        DecayTable decay_tables[3];
+        void* layerwise = nullptr;                     // kLamb, kLars: cnn_layerwise_create -- the device table, the norm workspace, the statistics
+        std::vector<uint32_t> seg_bounds, seg_flags;   // ... and the segment table it was created from (host copy)
+    } opt;
+    // what every setter starts with: finalized and the 32-bit table limit (deliberately checked in every build, not asserts: they abort
+    // with the setter's name), flush_deferred, synchronize
+    void begin_optimizer_switch(const char* setter);
+    const DecayTable& decay_table_of(size_t lo, size_t hi) const;  // the table built for exactly this range; aborts when there is none
+    void ensure_state_arena(data_type*& arena);
     void build_decay_table(DecayTable& t, size_t lo, size_t hi, bool bias_and_norm);
     void build_decay_tables(bool bias_and_norm);
-    // ---- Adam / AdamW (set_adam): the arena's step is cnn_adam_update; opt_active is true as well, so the fused tail takes the
-    // momentum optimizer's route (the front block's step is the arena kernel, no TAIL_BEHIND_BLOCK) ----
-    bool adam_active = false;          // the optimizer set last was set_adam()
-    data_type adam_beta1 = 0, adam_beta2 = 0, adam_eps = 0, adam_weight_decay = 0;
-    bool adam_decoupled = false, adam_decay_bias_and_norm = false;
-    data_type* adam_m = nullptr;       // exp_avg and exp_avg_sq: n_params floats each, allocated (zeroed) by the first set_adam()
-    data_type* adam_v = nullptr;
-    uint64_t adam_t = 0;               // container steps taken under Adam (the step the next launch carries is adam_t after its increment)
-    // ---- clipping by the global gradient norm (set_grad_clip) ----
+    void build_segment_table(bool decay_bias_and_norm, bool adapt_bias_and_norm);
+    struct StateFormat;                               // one on-disk format of the optimizer state (optimizer.cpp)
+    // ---- clipping by the global gradient norm (set_grad_clip): orthogonal to the kind ----
     data_type clip_max_norm = 0;       // 0: off
     void* clip_workspace = nullptr;    // cnn_clip_grad_norm's partial sums
     size_t clip_workspace_bytes = 0;
     data_type* clip_stats = nullptr;   // [2] on the device: total norm, coefficient of the latest clipped step
-    // ---- layer-wise optimizers (set_lamb / set_lars): the arena's step is ONE cnn_lamb_update / cnn_lars_update over the whole arena ----
-    enum LayerwiseMode { kLayerwiseOff = 0, kLamb = 1, kLars = 2 };
-    LayerwiseMode lw_mode = kLayerwiseOff;  // the optimizer set last was set_lamb() / set_lars()
-    void* lw_handle = nullptr;              // cnn_layerwise_create: the device table, the norm workspace, the statistics
-    std::vector<uint32_t> lw_bounds, lw_flags;  // the segment table of lw_handle (host copy)
-    bool lw_decay_bias_and_norm = false, lw_adapt_bias_and_norm = false;
-    data_type lamb_beta1 = 0, lamb_beta2 = 0, lamb_eps = 0, lamb_weight_decay = 0;  // (state: adam_m, adam_v, adam_t)
-    data_type lars_momentum = 0, lars_weight_decay = 0, lars_trust = 0, lars_eps = 0;  // (state: velocity)
-    bool lars_nesterov = false;
-    data_type* lw_update = nullptr;         // n_params floats of scratch: LAMB's r between its two passes
-    void build_segment_table(bool decay_bias_and_norm, bool adapt_bias_and_norm);
-    void ensure_adam_state();
-    void ensure_velocity();
     size_t front_block_params() const;
-    // the SGD step on arena[lo, hi) (parameters, gradients, velocity, snapshot) on `on_stream`, plain or with the optimizer
+    // the step of the active kind on arena[lo, hi) (parameters, gradients, state, snapshot) on `on_stream`: the ONE dispatch on opt_kind.
+    // kSgdm / kAdam step the three ranges decay tables exist for; kLamb / kLars the whole arena only.
     void step_arena(size_t lo, size_t hi, data_type learning_rate, data_type grad_scale, void* on_stream);
     bool exchange_active() const;
     void wire();
@@ -574,12 +603,14 @@ public:
     // parameters with the arena kernel instead of inside its weight-gradient kernel.  Stand-alone
     // Layer::update_gradients(lr) stays the plain step.  Under set_comm the velocity is per replica and needs no exchange.
     void set_optimizer(data_type momentum, data_type weight_decay, bool nesterov = false, bool decay_bias_and_norm = false);
-    bool optimizer_active() const { return opt_active; }
-    data_type* velocity_device() const { return velocity; }  // null before the first set_optimizer()
-    // Optimizer state beside a .model checkpoint (whose format stays the reference's): magic "CNNAOPT1", n_params (uint64), momentum,
-    // weight_decay (float), nesterov, decay_bias_and_norm (uint32), then the velocity arena.  Both return 0 on success.  save: 1 =
-    // cannot write, 4 = no optimizer was ever set.  load: 1 = cannot open, 2 = not such a file / truncated, 3 = written for another
-    // n_params; nothing is changed on failure, on success the file's options are set as by set_optimizer().
+    bool optimizer_active() const { return step_beyond_plain_sgd(); }
+    data_type* velocity_device() const { return opt.velocity; }  // null before the first set_optimizer()
+    // Optimizer state beside a .model checkpoint (whose format stays the reference's).  One format per optimizer -- a header of magic,
+    // n_params, [step,] the setter's options, then the kind's state arenas; each is described once, in optimizer.cpp's format table.
+    // save writes the active kind's format (the plain step: the momentum format with momentum 0, weight decay 0); load recognises all
+    // of them and activates the optimizer the file was written for.  Both return 0 on success.  save: 1 = cannot write, 4 = no
+    // optimizer was ever set.  load: 1 = cannot open, 2 = not such a file / truncated / options out of range, 3 = written for another
+    // n_params; nothing is changed on failure, on success the file's options are set as by the setter, then its arenas and step counter.
     int save_optimizer_state(const std::filesystem::path& path);
     int load_optimizer_state(const std::filesystem::path& path);
 
@@ -593,14 +624,10 @@ public:
     // the momentum optimizer's: the front block is stepped by the arena kernel.
     void set_adam(data_type beta1 = 0.9, data_type beta2 = 0.999, data_type eps = 1e-8, data_type weight_decay = 0, bool decoupled = false,
                   bool decay_bias_and_norm = false);
-    bool adam_is_active() const { return adam_active; }
-    data_type* adam_m_device() const { return adam_m; }  // null before the first set_adam()
-    data_type* adam_v_device() const { return adam_v; }
-    uint64_t adam_step() const { return adam_t; }
-    // With Adam active save_optimizer_state writes a second format: magic "CNNAADM1", n_params (uint64), step (uint64), beta1, beta2, eps,
-    // weight_decay (float), decoupled, decay_bias_and_norm (uint32), then exp_avg, then exp_avg_sq.  load_optimizer_state recognises
-    // both magics and activates the optimizer the file was written for; the status codes are the ones above.
-    //
+    bool adam_is_active() const { return opt_kind == OptKind::kAdam; }
+    data_type* adam_m_device() const { return opt.exp_avg; }  // null before the first set_adam()
+    data_type* adam_v_device() const { return opt.exp_avg_sq; }
+    uint64_t adam_step() const { return opt.step; }
     // Clipping by the global L2 norm of the gradient arena (torch.nn.utils.clip_grad_norm_; cnn_clip_grad_norm): with max_norm > 0
     // update_gradients(lr, grad_scale) clips the whole arena -- behind the data-parallel all-reduce, in front of the step, on the same
     // stream, without a host round trip -- for the plain step, the momentum optimizer and Adam alike.  0 (the default) switches it
@@ -627,21 +654,17 @@ public:
                   bool adapt_bias_and_norm = false);
     void set_lars(data_type momentum, data_type weight_decay, data_type trust_coefficient = 1e-3, data_type eps = 1e-8, bool nesterov = false,
                   bool decay_bias_and_norm = false, bool adapt_bias_and_norm = false);
-    bool layerwise_active() const { return lw_mode != kLayerwiseOff; }
-    bool lamb_is_active() const { return lw_mode == kLamb; }
-    bool lars_is_active() const { return lw_mode == kLars; }
-    size_t segment_count() const { return lw_flags.size(); }  // 0 before the first set_lamb() / set_lars()
+    bool layerwise_active() const { return step_needs_whole_tensors(); }
+    bool lamb_is_active() const { return opt_kind == OptKind::kLamb; }
+    bool lars_is_active() const { return opt_kind == OptKind::kLars; }
+    size_t segment_count() const { return opt.seg_flags.size(); }  // 0 before the first set_lamb() / set_lars()
     void segment_table(std::vector<uint32_t>& bounds, std::vector<uint32_t>& flags) const {
-        bounds = lw_bounds;
-        flags = lw_flags;
+        bounds = opt.seg_bounds;
+        flags = opt.seg_flags;
     }
     // w_norm, u_norm, ratio of the latest layer-wise step (segment_count() values each); like last_grad_norm() it synchronises.
     // false: no layer-wise optimizer was ever set.
     bool trust_stats(std::vector<data_type>& w_norm, std::vector<data_type>& u_norm, std::vector<data_type>& ratio);
-    // With LAMB / LARS active save_optimizer_state writes two more formats.  "CNNALMB1": magic, n_params (uint64), step (uint64), beta1,
-    // beta2, eps, weight_decay (float), decay_bias_and_norm, adapt_bias_and_norm (uint32), then exp_avg, then exp_avg_sq.  "CNNALRS1":
-    // magic, n_params (uint64), momentum, weight_decay, trust_coefficient, eps (float), nesterov, decay_bias_and_norm,
-    // adapt_bias_and_norm (uint32), 4 bytes of padding, then the velocity arena.  load_optimizer_state recognises all four magics.
 
 protected:
     void invalidate_filter_images();  // (the part of parameters_changed() the container's own SGD step needs too)

@@ -177,14 +177,14 @@ Sequential::~Sequential() {
     }
     layers_sequence.clear();
     if (param_prev) cnn_device_free(param_prev);
-    if (velocity) cnn_device_free(velocity);
-    if (adam_m) cnn_device_free(adam_m);
-    if (adam_v) cnn_device_free(adam_v);
+    if (opt.velocity) cnn_device_free(opt.velocity);
+    if (opt.exp_avg) cnn_device_free(opt.exp_avg);
+    if (opt.exp_avg_sq) cnn_device_free(opt.exp_avg_sq);
     if (clip_workspace) cnn_device_free(clip_workspace);
     if (clip_stats) cnn_device_free(clip_stats);
-    if (lw_handle) cnn_layerwise_destroy(lw_handle);
-    if (lw_update) cnn_device_free(lw_update);
-    for (auto& t : decay_tables)
+    if (opt.layerwise) cnn_layerwise_destroy(opt.layerwise);
+    if (opt.lamb_update) cnn_device_free(opt.lamb_update);
+    for (auto& t : opt.decay_tables)
         if (t.dev) cnn_device_free(t.dev);
     if (defer_stream) cnn_stream_destroy(defer_stream);
     if (ev_defer_done) cnn_event_destroy(ev_defer_done);
@@ -456,458 +456,14 @@ void Sequential::update_gradients(const data_type learning_rate, const data_type
     if (clip_max_norm > 0 && n_params > 0)  // (behind the all-reduce, in front of the step; the step applies grad_scale to the clipped values)
         must(cnn_clip_grad_norm(grad_arena, n_params, clip_max_norm, grad_scale, clip_workspace, clip_workspace_bytes, clip_stats, stream),
              "cnn_clip_grad_norm");
-    if (adam_active || lw_mode == kLamb) ++adam_t;
-    if (lw_mode == kLamb && n_params > 0) {  // (a trust ratio needs the whole tensor: one call over the whole arena, never range steps)
-        const cnn_lamb_options o{learning_rate, lamb_beta1, lamb_beta2, lamb_eps, lamb_weight_decay, adam_t};
-        must(cnn_lamb_update(lw_handle, param_arena, grad_arena, adam_m, adam_v, lw_update, &o, grad_scale, param_prev, stream), "cnn_lamb_update");
-    } else if (lw_mode == kLars && n_params > 0) {
-        const cnn_lars_options o{learning_rate, lars_momentum, lars_weight_decay, lars_trust, lars_eps, lars_nesterov ? 1 : 0};
-        must(cnn_lars_update(lw_handle, param_arena, grad_arena, velocity, &o, grad_scale, param_prev, stream), "cnn_lars_update");
-    } else {
-        step_arena(0, n_params, learning_rate, grad_scale, stream);
-    }
+    if (step_uses_adam_moments()) ++opt.step;
+    step_arena(0, n_params, learning_rate, grad_scale, stream);  // (optimizer.cpp: the dispatch on the active kind)
     invalidate_filter_images();
     params_stepped = true;
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// optimizer: SGD with momentum / weight decay / Nesterov on the arena
-void Sequential::build_decay_table(DecayTable& t, size_t lo, size_t hi, const bool bias_and_norm) {
-    t.lo = lo;
-    t.hi = hi;
-    t.host.clear();
-    size_t idx = 0;
-    Layer::RangeList local;
-    for (const auto& layer : layers_sequence) {
-        const size_t off = layer_offsets[idx++];
-        local.clear();
-        layer->decay_ranges(bias_and_norm, local);
-        for (const auto& r : local) {
-            const size_t b = std::max(off + r.first, lo), e = std::min(off + r.second, hi);
-            if (b >= e) continue;
-            if (!t.host.empty() && t.host.back() == (uint32_t)(b - lo)) t.host.back() = (uint32_t)(e - lo);  // (neighbours merge)
-            else {
-                t.host.push_back((uint32_t)(b - lo));
-                t.host.push_back((uint32_t)(e - lo));
-            }
-        }
-    }
-    if (t.dev) {
-        must(cnn_device_free(t.dev), "cnn_device_free");
-        t.dev = nullptr;
-    }
-    if (t.host.size() / 2 > (size_t)CNN_SGD_INLINE_RANGES) {  // beyond what travels in the kernel arguments: the kernel reads a device copy
-        t.dev = (uint32_t*)dev_alloc(sizeof(uint32_t) * t.host.size());
-        must(cnn_memcpy_h2d(t.dev, t.host.data(), sizeof(uint32_t) * t.host.size(), stream), "cnn_memcpy_h2d");
-        must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
-    }
-}
-
 // the pool-fused front block's convolution owns arena[0, front_block_params()) (wire(): block_conv is the first layer); 0 without one
 size_t Sequential::front_block_params() const { return block_conv != nullptr ? block_conv->param_count() : 0; }
-
-void Sequential::set_optimizer(const data_type momentum, const data_type weight_decay, const bool nesterov, const bool decay_bias_and_norm) {
-    assert(finalized && "set_optimizer works on the flat arena: call finalize() first");
-    assert(momentum >= 0 && weight_decay >= 0);
-    assert(n_params < ((size_t)1 << 32) - 1024 && "set_optimizer: the decay-range table is 32-bit");
-    flush_deferred();  // (a side-stream tail of the previous step may still read the tables rebuilt below)
-    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
-    ensure_velocity();
-    lw_mode = kLayerwiseOff;
-    opt_momentum = momentum;
-    opt_weight_decay = weight_decay;
-    opt_nesterov = nesterov;
-    opt_decay_bias_and_norm = decay_bias_and_norm;
-    opt_active = momentum != 0 || weight_decay != 0;
-    adam_active = false;
-    build_decay_tables(decay_bias_and_norm);
-}
-
-void Sequential::ensure_velocity() {
-    if (velocity != nullptr) return;
-    velocity = (data_type*)dev_alloc(sizeof(data_type) * (n_params ? n_params : 1));
-    must(cnn_memset_zero(velocity, sizeof(data_type) * n_params, stream), "cnn_memset_zero");
-    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
-}
-
-void Sequential::ensure_adam_state() {
-    if (adam_m != nullptr) return;
-    adam_m = (data_type*)dev_alloc(sizeof(data_type) * (n_params ? n_params : 1));
-    adam_v = (data_type*)dev_alloc(sizeof(data_type) * (n_params ? n_params : 1));
-    must(cnn_memset_zero(adam_m, sizeof(data_type) * n_params, stream), "cnn_memset_zero");
-    must(cnn_memset_zero(adam_v, sizeof(data_type) * n_params, stream), "cnn_memset_zero");
-    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
-    adam_t = 0;
-}
-
-// the segment table of the layer-wise optimizers: every layer's param_tensors() at the layer's arena offset; DECAY where the decay
-// policy (decay_ranges) covers the tensor, ADAPT on the first tensor of a Conv2D / LinearLayer (the weights) and, with
-// adapt_bias_and_norm, wherever decay_ranges(true) reaches (biases, gamma / beta -- never the moving statistics)
-void Sequential::build_segment_table(const bool decay_bias_and_norm, const bool adapt_bias_and_norm) {
-    std::vector<uint32_t> bounds(1, 0u), flags;
-    auto covered = [](const Layer::RangeList& ranges, size_t b, size_t e) {
-        for (const auto& r : ranges)
-            if (r.first <= b && e <= r.second) return true;
-        return false;
-    };
-    size_t idx = 0;
-    Layer::RangeList tensors, decayed, weights, all;
-    for (const auto& layer : layers_sequence) {
-        const size_t off = layer_offsets[idx++];
-        tensors.clear();
-        decayed.clear();
-        weights.clear();
-        all.clear();
-        layer->param_tensors(tensors);
-        layer->decay_ranges(decay_bias_and_norm, decayed);
-        layer->decay_ranges(false, weights);
-        layer->decay_ranges(true, all);
-        size_t at = 0;
-        for (const auto& t : tensors) {
-            assert(t.first == at && t.second > t.first && "param_tensors() tiles the layer's parameter block");
-            at = t.second;
-            uint32_t f = 0;
-            if (covered(decayed, t.first, t.second)) f |= CNN_SEG_DECAY;
-            if (covered(adapt_bias_and_norm ? all : weights, t.first, t.second)) f |= CNN_SEG_ADAPT;
-            bounds.push_back((uint32_t)(off + t.second));
-            flags.push_back(f);
-        }
-        assert(at == layer->param_count() && "param_tensors() tiles the layer's parameter block");
-    }
-    assert(flags.empty() ? n_params == 0 : bounds.back() == n_params);
-    if (lw_handle != nullptr && bounds == lw_bounds && flags == lw_flags) return;
-    if (lw_handle != nullptr) {
-        must(cnn_layerwise_destroy(lw_handle), "cnn_layerwise_destroy");
-        lw_handle = nullptr;
-    }
-    lw_bounds = bounds;
-    lw_flags = flags;
-    if (!flags.empty()) must(cnn_layerwise_create(lw_bounds.data(), lw_flags.data(), lw_flags.size(), &lw_handle), "cnn_layerwise_create");
-}
-
-void Sequential::set_lamb(const data_type beta1, const data_type beta2, const data_type eps, const data_type weight_decay, const bool decay_bias_and_norm,
-                          const bool adapt_bias_and_norm) {
-    assert(finalized && "set_lamb works on the flat arena: call finalize() first");
-    assert(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1 && eps > 0 && weight_decay >= 0);
-    assert(n_params < ((size_t)1 << 32) - 1024 && "set_lamb: the segment table is 32-bit");
-    flush_deferred();  // (a side-stream tail of the previous step may still be stepping the arena)
-    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
-    ensure_adam_state();
-    if (lw_update == nullptr) lw_update = (data_type*)dev_alloc(sizeof(data_type) * (n_params ? n_params : 1));
-    build_segment_table(decay_bias_and_norm, adapt_bias_and_norm);
-    lamb_beta1 = beta1;
-    lamb_beta2 = beta2;
-    lamb_eps = eps;
-    lamb_weight_decay = weight_decay;
-    lw_decay_bias_and_norm = decay_bias_and_norm;
-    lw_adapt_bias_and_norm = adapt_bias_and_norm;
-    lw_mode = kLamb;
-    adam_active = false;
-    opt_active = true;  // (every place that asks "is the step more than the block's in-kernel plain SGD")
-}
-
-void Sequential::set_lars(const data_type momentum, const data_type weight_decay, const data_type trust_coefficient, const data_type eps,
-                          const bool nesterov, const bool decay_bias_and_norm, const bool adapt_bias_and_norm) {
-    assert(finalized && "set_lars works on the flat arena: call finalize() first");
-    assert(momentum >= 0 && weight_decay >= 0 && trust_coefficient > 0 && eps > 0);
-    assert(n_params < ((size_t)1 << 32) - 1024 && "set_lars: the segment table is 32-bit");
-    flush_deferred();
-    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
-    ensure_velocity();
-    build_segment_table(decay_bias_and_norm, adapt_bias_and_norm);
-    lars_momentum = momentum;
-    lars_weight_decay = weight_decay;
-    lars_trust = trust_coefficient;
-    lars_eps = eps;
-    lars_nesterov = nesterov;
-    lw_decay_bias_and_norm = decay_bias_and_norm;
-    lw_adapt_bias_and_norm = adapt_bias_and_norm;
-    lw_mode = kLars;
-    adam_active = false;
-    opt_active = true;
-}
-
-bool Sequential::trust_stats(std::vector<data_type>& w_norm, std::vector<data_type>& u_norm, std::vector<data_type>& ratio) {
-    if (lw_handle == nullptr) return false;
-    const size_t ns = lw_flags.size();
-    float* dev = nullptr;
-    must(cnn_layerwise_stats(lw_handle, &dev), "cnn_layerwise_stats");
-    std::vector<data_type> host(3 * ns);
-    must(cnn_memcpy_d2h(host.data(), dev, sizeof(data_type) * host.size(), stream), "cnn_memcpy_d2h");
-    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
-    w_norm.assign(host.begin(), host.begin() + ns);
-    u_norm.assign(host.begin() + ns, host.begin() + 2 * ns);
-    ratio.assign(host.begin() + 2 * ns, host.end());
-    return true;
-}
-
-void Sequential::build_decay_tables(const bool bias_and_norm) {
-    const size_t front = front_block_params();
-    build_decay_table(decay_tables[0], 0, n_params, bias_and_norm);
-    build_decay_table(decay_tables[1], front, n_params, bias_and_norm);
-    build_decay_table(decay_tables[2], 0, front, bias_and_norm);
-}
-
-void Sequential::set_adam(const data_type beta1, const data_type beta2, const data_type eps, const data_type weight_decay, const bool decoupled,
-                          const bool decay_bias_and_norm) {
-    assert(finalized && "set_adam works on the flat arena: call finalize() first");
-    assert(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1 && eps > 0 && weight_decay >= 0);
-    assert(n_params < ((size_t)1 << 32) - 1024 && "set_adam: the decay-range table is 32-bit");
-    flush_deferred();  // (a side-stream tail of the previous step may still read the tables rebuilt below)
-    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
-    ensure_adam_state();
-    lw_mode = kLayerwiseOff;
-    adam_beta1 = beta1;
-    adam_beta2 = beta2;
-    adam_eps = eps;
-    adam_weight_decay = weight_decay;
-    adam_decoupled = decoupled;
-    adam_decay_bias_and_norm = decay_bias_and_norm;
-    adam_active = true;
-    opt_active = true;  // (every place that asks "is the step more than the block's in-kernel plain SGD")
-    build_decay_tables(decay_bias_and_norm);
-}
-
-void Sequential::set_grad_clip(const data_type max_norm) {
-    assert(finalized && "set_grad_clip works on the flat arena: call finalize() first");
-    assert(max_norm >= 0);
-    flush_deferred();  // (a side-stream tail of the previous step is ordered before the first clipped step's plain sequence)
-    if (max_norm > 0 && clip_stats == nullptr) {
-        clip_workspace_bytes = cnn_clip_grad_norm_workspace_bytes(n_params);
-        clip_workspace = dev_alloc(clip_workspace_bytes);
-        clip_stats = (data_type*)dev_alloc(sizeof(data_type) * 2);
-        must(cnn_memset_zero(clip_stats, sizeof(data_type) * 2, stream), "cnn_memset_zero");
-    }
-    clip_max_norm = max_norm;
-}
-
-data_type Sequential::last_grad_norm(data_type* coef_out) {
-    assert(clip_stats != nullptr && "last_grad_norm: clipping was never switched on (set_grad_clip)");
-    data_type host[2] = {0, 0};
-    must(cnn_memcpy_d2h(host, clip_stats, sizeof(host), stream), "cnn_memcpy_d2h");
-    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
-    if (coef_out) *coef_out = host[1];
-    return host[0];
-}
-
-void Sequential::step_arena(const size_t lo, const size_t hi, const data_type learning_rate, const data_type grad_scale, void* on_stream) {
-    if (hi <= lo) return;
-    if (!opt_active) {  // the reference's w -= lr * g
-        must(cnn_sgd_update_keep(param_arena + lo, grad_arena + lo, hi - lo, learning_rate, grad_scale, param_prev + lo, on_stream),
-             "cnn_sgd_update_keep");
-        return;
-    }
-    const DecayTable* t = nullptr;
-    for (const auto& cand : decay_tables)
-        if (cand.lo == lo && cand.hi == hi) t = &cand;
-    if (t == nullptr) {  // (the container steps the three ranges set_optimizer built tables for, and no other)
-        std::fprintf(stderr, "cnn_amd host: step_arena: no decay table for arena[%zu, %zu)\n", lo, hi);
-        std::abort();
-    }
-    if (adam_active) {
-        const cnn_adam_options o{learning_rate, adam_beta1, adam_beta2, adam_eps, adam_weight_decay, adam_decoupled ? 1 : 0, adam_t};
-        must(cnn_adam_update(param_arena + lo, grad_arena + lo, adam_m + lo, adam_v + lo, hi - lo, &o, grad_scale, t->host.data(), t->dev,
-                             t->host.size() / 2, param_prev + lo, on_stream),
-             "cnn_adam_update");
-        return;
-    }
-    const cnn_sgd_options o{learning_rate, opt_momentum, opt_weight_decay, opt_nesterov ? 1 : 0};
-    must(cnn_sgd_momentum_update(param_arena + lo, grad_arena + lo, velocity + lo, hi - lo, &o, grad_scale, t->host.data(), t->dev,
-                                 t->host.size() / 2, param_prev + lo, on_stream),
-         "cnn_sgd_momentum_update");
-}
-
-namespace {
-struct OptStateHeader {
-    char magic[8];
-    uint64_t n_params;
-    float momentum, weight_decay;
-    uint32_t nesterov, decay_bias_and_norm;
-};
-const char kOptMagic[8] = {'C', 'N', 'N', 'A', 'O', 'P', 'T', '1'};
-struct AdamStateHeader {
-    char magic[8];
-    uint64_t n_params, step;
-    float beta1, beta2, eps, weight_decay;
-    uint32_t decoupled, decay_bias_and_norm;
-};
-static_assert(sizeof(AdamStateHeader) == 48, "the Adam state file's header is 48 bytes");
-const char kAdamMagic[8] = {'C', 'N', 'N', 'A', 'A', 'D', 'M', '1'};
-struct LambStateHeader {
-    char magic[8];
-    uint64_t n_params, step;
-    float beta1, beta2, eps, weight_decay;
-    uint32_t decay_bias_and_norm, adapt_bias_and_norm;
-};
-static_assert(sizeof(LambStateHeader) == 48, "the LAMB state file's header is 48 bytes");
-const char kLambMagic[8] = {'C', 'N', 'N', 'A', 'L', 'M', 'B', '1'};
-struct LarsStateHeader {
-    char magic[8];
-    uint64_t n_params;
-    float momentum, weight_decay, trust_coefficient, eps;
-    uint32_t nesterov, decay_bias_and_norm, adapt_bias_and_norm, pad;
-};
-static_assert(sizeof(LarsStateHeader) == 48, "the LARS state file's header is 48 bytes");
-const char kLarsMagic[8] = {'C', 'N', 'N', 'A', 'L', 'R', 'S', '1'};
-}  // namespace
-
-int Sequential::save_optimizer_state(const std::filesystem::path& path) {
-    assert(finalized);
-    if (lw_mode == kLamb) {
-        flush_deferred();
-        std::vector<data_type> host(2 * n_params);
-        must(cnn_memcpy_d2h(host.data(), adam_m, sizeof(data_type) * n_params, stream), "cnn_memcpy_d2h");
-        must(cnn_memcpy_d2h(host.data() + n_params, adam_v, sizeof(data_type) * n_params, stream), "cnn_memcpy_d2h");
-        must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
-        LambStateHeader h;
-        std::memcpy(h.magic, kLambMagic, 8);
-        h.n_params = n_params;
-        h.step = adam_t;
-        h.beta1 = lamb_beta1;
-        h.beta2 = lamb_beta2;
-        h.eps = lamb_eps;
-        h.weight_decay = lamb_weight_decay;
-        h.decay_bias_and_norm = lw_decay_bias_and_norm ? 1 : 0;
-        h.adapt_bias_and_norm = lw_adapt_bias_and_norm ? 1 : 0;
-        std::ofstream writer(path.c_str(), std::ios::binary);
-        writer.write((const char*)&h, sizeof(h));
-        writer.write((const char*)host.data(), sizeof(data_type) * host.size());
-        writer.close();
-        return writer.good() ? 0 : 1;
-    }
-    if (lw_mode == kLars) {
-        flush_deferred();
-        std::vector<data_type> host(n_params);
-        must(cnn_memcpy_d2h(host.data(), velocity, sizeof(data_type) * n_params, stream), "cnn_memcpy_d2h");
-        must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
-        LarsStateHeader h;
-        std::memcpy(h.magic, kLarsMagic, 8);
-        h.n_params = n_params;
-        h.momentum = lars_momentum;
-        h.weight_decay = lars_weight_decay;
-        h.trust_coefficient = lars_trust;
-        h.eps = lars_eps;
-        h.nesterov = lars_nesterov ? 1 : 0;
-        h.decay_bias_and_norm = lw_decay_bias_and_norm ? 1 : 0;
-        h.adapt_bias_and_norm = lw_adapt_bias_and_norm ? 1 : 0;
-        h.pad = 0;
-        std::ofstream writer(path.c_str(), std::ios::binary);
-        writer.write((const char*)&h, sizeof(h));
-        writer.write((const char*)host.data(), sizeof(data_type) * host.size());
-        writer.close();
-        return writer.good() ? 0 : 1;
-    }
-    if (adam_active) {
-        flush_deferred();
-        std::vector<data_type> host(2 * n_params);
-        must(cnn_memcpy_d2h(host.data(), adam_m, sizeof(data_type) * n_params, stream), "cnn_memcpy_d2h");
-        must(cnn_memcpy_d2h(host.data() + n_params, adam_v, sizeof(data_type) * n_params, stream), "cnn_memcpy_d2h");
-        must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
-        AdamStateHeader h;
-        std::memcpy(h.magic, kAdamMagic, 8);
-        h.n_params = n_params;
-        h.step = adam_t;
-        h.beta1 = adam_beta1;
-        h.beta2 = adam_beta2;
-        h.eps = adam_eps;
-        h.weight_decay = adam_weight_decay;
-        h.decoupled = adam_decoupled ? 1 : 0;
-        h.decay_bias_and_norm = adam_decay_bias_and_norm ? 1 : 0;
-        std::ofstream writer(path.c_str(), std::ios::binary);
-        writer.write((const char*)&h, sizeof(h));
-        writer.write((const char*)host.data(), sizeof(data_type) * host.size());
-        writer.close();
-        return writer.good() ? 0 : 1;
-    }
-    if (velocity == nullptr) return 4;
-    flush_deferred();
-    std::vector<data_type> host(n_params);
-    must(cnn_memcpy_d2h(host.data(), velocity, sizeof(data_type) * n_params, stream), "cnn_memcpy_d2h");
-    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
-    OptStateHeader h;
-    std::memcpy(h.magic, kOptMagic, 8);
-    h.n_params = n_params;
-    h.momentum = opt_momentum;
-    h.weight_decay = opt_weight_decay;
-    h.nesterov = opt_nesterov ? 1 : 0;
-    h.decay_bias_and_norm = opt_decay_bias_and_norm ? 1 : 0;
-    std::ofstream writer(path.c_str(), std::ios::binary);
-    writer.write((const char*)&h, sizeof(h));
-    writer.write((const char*)host.data(), sizeof(data_type) * host.size());
-    writer.close();
-    return writer.good() ? 0 : 1;
-}
-
-int Sequential::load_optimizer_state(const std::filesystem::path& path) {
-    assert(finalized);
-    std::ifstream reader(path.c_str(), std::ios::binary);
-    if (!reader.good()) return 1;
-    char magic[8] = {0};
-    reader.read(magic, 8);
-    if (reader.good() && std::memcmp(magic, kAdamMagic, 8) == 0) {
-        AdamStateHeader h;
-        std::memcpy(h.magic, magic, 8);
-        reader.read((char*)&h + 8, sizeof(h) - 8);
-        if (!reader.good()) return 2;
-        if (h.n_params != (uint64_t)n_params) return 3;
-        if (!(h.beta1 >= 0 && h.beta1 < 1) || !(h.beta2 >= 0 && h.beta2 < 1) || !(h.eps > 0) || !(h.weight_decay >= 0)) return 2;
-        std::vector<data_type> host(2 * n_params);
-        reader.read((char*)host.data(), sizeof(data_type) * host.size());
-        if ((size_t)reader.gcount() != sizeof(data_type) * host.size()) return 2;  // (nothing has been changed yet: no partial read)
-        set_adam(h.beta1, h.beta2, h.eps, h.weight_decay, h.decoupled != 0, h.decay_bias_and_norm != 0);
-        adam_t = h.step;
-        must(cnn_memcpy_h2d(adam_m, host.data(), sizeof(data_type) * n_params, stream), "cnn_memcpy_h2d");
-        must(cnn_memcpy_h2d(adam_v, host.data() + n_params, sizeof(data_type) * n_params, stream), "cnn_memcpy_h2d");
-        must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
-        return 0;
-    }
-    if (reader.good() && std::memcmp(magic, kLambMagic, 8) == 0) {
-        LambStateHeader h;
-        std::memcpy(h.magic, magic, 8);
-        reader.read((char*)&h + 8, sizeof(h) - 8);
-        if (!reader.good()) return 2;
-        if (h.n_params != (uint64_t)n_params) return 3;
-        if (!(h.beta1 >= 0 && h.beta1 < 1) || !(h.beta2 >= 0 && h.beta2 < 1) || !(h.eps > 0) || !(h.weight_decay >= 0)) return 2;
-        std::vector<data_type> host(2 * n_params);
-        reader.read((char*)host.data(), sizeof(data_type) * host.size());
-        if ((size_t)reader.gcount() != sizeof(data_type) * host.size()) return 2;  // (nothing has been changed yet: no partial read)
-        set_lamb(h.beta1, h.beta2, h.eps, h.weight_decay, h.decay_bias_and_norm != 0, h.adapt_bias_and_norm != 0);
-        adam_t = h.step;
-        must(cnn_memcpy_h2d(adam_m, host.data(), sizeof(data_type) * n_params, stream), "cnn_memcpy_h2d");
-        must(cnn_memcpy_h2d(adam_v, host.data() + n_params, sizeof(data_type) * n_params, stream), "cnn_memcpy_h2d");
-        must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
-        return 0;
-    }
-    if (reader.good() && std::memcmp(magic, kLarsMagic, 8) == 0) {
-        LarsStateHeader h;
-        std::memcpy(h.magic, magic, 8);
-        reader.read((char*)&h + 8, sizeof(h) - 8);
-        if (!reader.good()) return 2;
-        if (h.n_params != (uint64_t)n_params) return 3;
-        if (!(h.momentum >= 0) || !(h.weight_decay >= 0) || !(h.trust_coefficient > 0) || !(h.eps > 0)) return 2;
-        std::vector<data_type> host(n_params);
-        reader.read((char*)host.data(), sizeof(data_type) * host.size());
-        if ((size_t)reader.gcount() != sizeof(data_type) * host.size()) return 2;  // (nothing has been changed yet: no partial read)
-        set_lars(h.momentum, h.weight_decay, h.trust_coefficient, h.eps, h.nesterov != 0, h.decay_bias_and_norm != 0, h.adapt_bias_and_norm != 0);
-        must(cnn_memcpy_h2d(velocity, host.data(), sizeof(data_type) * n_params, stream), "cnn_memcpy_h2d");
-        must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
-        return 0;
-    }
-    reader.clear();
-    reader.seekg(0);
-    OptStateHeader h;
-    reader.read((char*)&h, sizeof(h));
-    if (!reader.good() || std::memcmp(h.magic, kOptMagic, 8) != 0) return 2;
-    if (h.n_params != (uint64_t)n_params) return 3;
-    if (!(h.momentum >= 0) || !(h.weight_decay >= 0)) return 2;
-    std::vector<data_type> host(n_params);
-    reader.read((char*)host.data(), sizeof(data_type) * host.size());
-    if ((size_t)reader.gcount() != sizeof(data_type) * host.size()) return 2;  // (nothing has been changed yet: no partial read)
-    set_optimizer(h.momentum, h.weight_decay, h.nesterov != 0, h.decay_bias_and_norm != 0);
-    must(cnn_memcpy_h2d(velocity, host.data(), sizeof(data_type) * n_params, stream), "cnn_memcpy_h2d");
-    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
-    return 0;
-}
 
 // filter images of every convolution behind the pool-fused front block, from the current parameters, on `on_stream`
 void Sequential::prepare_later_filters(void* on_stream) {
@@ -948,11 +504,11 @@ bool Sequential::fused_tail(std::vector<tensor>& delta, const data_type learning
         return false;
     if (cnn_amd_get_option("NO_FUSED_TAIL", nullptr, 0) == 0) return false;  // (A/B switch)
     if (clip_max_norm > 0) return false;  // (the norm needs every gradient of the step before any parameter moves: the plain sequence)
-    if (lw_mode != kLayerwiseOff) return false;  // (so does a trust ratio: every gradient of a tensor before that tensor moves)
+    if (step_needs_whole_tensors()) return false;  // (so does a trust ratio: every gradient of a tensor before that tensor moves)
     const size_t lo = front_block_params();  // the block's convolution owns arena[0, lo)
     const bool dp = exchange_active();
     const data_type scale = dp ? 1.f / (data_type)comm_world : 1.f;
-    if (adam_active) ++adam_t;  // (ONE container step: both range launches below carry this number)
+    if (step_uses_adam_moments()) ++opt.step;  // (ONE container step: both range launches below carry this number)
     if (ev_tail == nullptr) must(cnn_event_create(&ev_tail), "cnn_event_create");
     void* side = nullptr;
     must(cnn_amd_side_stream_get(&side), "cnn_amd_side_stream_get");
@@ -960,7 +516,7 @@ bool Sequential::fused_tail(std::vector<tensor>& delta, const data_type learning
     // weight gradient but BEHIND it, and the compute stream does not wait for them here: they overlap the next step's first
     // forward kernel, whose successor waits (train_step / flush_deferred)
     // (not with an optimizer set: the block's kernel has no momentum form, its step would be one more launch in front of the side tail)
-    const bool tail_behind = !dp && !opt_active && owns_arena && cnn_amd_get_option("TAIL_BEHIND_BLOCK", nullptr, 0) == 0;
+    const bool tail_behind = !dp && !step_beyond_plain_sgd() && owns_arena && cnn_amd_get_option("TAIL_BEHIND_BLOCK", nullptr, 0) == 0;
     if (tail_behind) {
         if (ev_side_tail == nullptr) must(cnn_event_create(&ev_side_tail), "cnn_event_create");
         pending_dgrad = block_conv->backward_weight_pooled(delta, /*fused_sgd=*/true, learning_rate, scale);
@@ -1007,7 +563,7 @@ bool Sequential::fused_tail(std::vector<tensor>& delta, const data_type learning
     prepare_later_filters(side);
     // compute stream: the block's weight gradient (+ its share of the tail)
     // (with an optimizer set the block's in-kernel step -- plain SGD only -- is not used: the route of the data-parallel branch below)
-    pending_dgrad = block_conv->backward_weight_pooled(delta, /*fused_sgd=*/!dp && !opt_active, learning_rate, scale);
+    pending_dgrad = block_conv->backward_weight_pooled(delta, /*fused_sgd=*/!dp && !step_beyond_plain_sgd(), learning_rate, scale);
     block_conv->set_delta_computed(input_gradient);
     if (!input_gradient) pending_dgrad.valid = false;  // (architectures::input_gradient: nobody wants d(loss) / d(input image))
     if (dgrad_now && pending_dgrad.valid) {
@@ -1016,7 +572,7 @@ bool Sequential::fused_tail(std::vector<tensor>& delta, const data_type learning
         pending_dgrad.valid = false;
         defer_in_flight = true;
     }
-    if (dp || opt_active) {  // bucket 2: this layer's few floats
+    if (dp || step_beyond_plain_sgd()) {  // bucket 2: this layer's few floats
         if (dp) must(cnn_allreduce_grads(comm, grad_arena, lo, stream), "cnn_allreduce_grads");
         step_arena(0, lo, learning_rate, scale, stream);
         block_conv->prepare_own_filters();

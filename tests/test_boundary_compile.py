@@ -33,6 +33,21 @@ def test_plain_list_caller_compiles_against_the_host_headers():
     assert out.returncode == 0, out.stderr[-3000:]
 
 
+@needs_gxx
+def test_optimizer_kind_accessors(tmp_path):
+    """tests/caller/optimizer_kind_check.cpp, linked against libcnn_amd_host.so and run on the host (no device is touched): optimizer_active /
+    adam_is_active / lamb_is_active / lars_is_active / layerwise_active report the active kind and only it, for all five kinds -- the C
+    handle API exposes only the last of them, so the GPU switching tests cannot ask the others"""
+    libdir = os.path.join(ROOT, "cnn_amd", "lib")
+    exe = str(tmp_path / "optimizer_kind_check")
+    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-Wno-unused-parameter", *INC, os.path.join(ROOT, "tests", "caller", "optimizer_kind_check.cpp"),
+           "-L" + libdir, "-lcnn_amd_host", "-lcnn_amd", "-Wl,-rpath," + libdir, "-o", exe]
+    out = subprocess.run(cmd, capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr[-4000:]
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0 and run.stdout.strip() == "ok", (run.returncode, run.stdout, run.stderr[-2000:])
+
+
 @pytest.mark.gpu
 @needs_gxx
 def test_plain_list_caller_drops_in_on_the_device_layers(tmp_path, golden_dir):
