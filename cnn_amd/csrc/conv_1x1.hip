@@ -9,7 +9,7 @@
 // 9-tap tile shape: 24 / 9.5 / 4.3-9.6 TFLOP/s on 128 -> 256, 28x28, stride 2 at batch 64 (profiles/NOTEBOOK.md section 9).  Here: K-chunked LDS
 // GEMMs on v_mfma_f32_16x16x4_f32, 8 waves per workgroup, the next chunk's operands prefetched into registers while the current chunk's
 // MFMAs run (one barrier pair per chunk), operand tiles padded so that both MFMA operand reads are bank-conflict free.
-#include "common.h"
+#include "conv_families.h"
 
 using namespace cnn_amd;
 

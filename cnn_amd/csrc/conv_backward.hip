@@ -2,16 +2,9 @@
 // (conv2d.cpp:117-159) and the data-gradient kernels (conv2d.cpp:168-199) only share their inputs, and for the
 // reference net's layers each of them alone is latency-bound, so they run CONCURRENTLY: fork an internal side stream
 // off the caller's stream with an event, join it back with a second event.  The pattern is capturable in a hipGraph.
-#include "common.h"
+#include "conv_families.h"
 
 using namespace cnn_amd;
-
-namespace cnn_amd {
-size_t igemm_workspace_floats(const cnn_conv2d_desc* d);  // conv_igemm.hip
-void wgrad_defer_reduce(bool on);                          // conv_wgrad.hip: with defer_join the final slab reductions of the
-int wgrad_flush_reduces(hipStream_t s);                    // weight gradients run in one launch just before the join
-bool thin_dgrad_supported(const cnn_conv2d_desc* d);       // conv_dgrad_thin.hip
-}
 
 namespace {
 struct SideStream {

@@ -20,13 +20,9 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
+#include "conv_families.h"
 
 using namespace cnn_amd;
-
-namespace cnn_amd {
-bool igemm_preferred(const cnn_conv2d_desc* d, int mode);  // conv_igemm.hip (mode 0 forward, 1 data gradient)
-}
 
 namespace {
 

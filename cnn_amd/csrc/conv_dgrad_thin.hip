@@ -15,7 +15,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
+#include "conv_families.h"
 
 using namespace cnn_amd;
 
@@ -112,7 +112,6 @@ __global__ __launch_bounds__(kThinWaves * 64) void conv_dgrad_thin_s1k3(const fl
         }
     }
 }
-
 
 // ---- Ci = 3 under a K x K filter with stride 2 and pad (K-1)/2: the data gradient of the ResNet-shaped stack's 7x7 stem -------------
 // (implicit GEMM: M = Ci = 3 of 32 MFMA rows, 17 TFLOP/s, 0.9 ms at batch 64 -- 1.2 ms beside the weight gradient.)
@@ -272,7 +271,6 @@ __global__ __launch_bounds__(kThinWaves * 64) void conv_dgrad_thin_s2(const floa
     }
 }
 
-
 // ---- the same data gradient on PACKED fp32 FMAs (round 6) ----------------------------------------------------------------------------
 // The scalar-operand kernel above spends 147 v_fma_f32 per dy channel and grid position; on gfx950 v_pk_fma_f32 does two FMAs per lane
 // in the same issue slot.  Taps c and c + 1 (c odd) of a filter row multiply the SAME dy neighbour and feed the two column parities of
@@ -415,8 +413,6 @@ __global__ __launch_bounds__(kThinWaves * 64) void conv_dgrad_thin_s2_pk7(const 
 }  // namespace
 
 namespace cnn_amd {
-
-#define CONV_TAG(d) "B%d Ci%d %dx%d Co%d k%d s%d p%d", (d)->B, (d)->Ci, (d)->H, (d)->W, (d)->Co, (d)->k, (d)->s, (d)->pad
 
 bool thin_dgrad_supported(const cnn_conv2d_desc* d) {
     const OptVal e = CNN_OPT_VAL("DGRAD_THIN");

@@ -11,7 +11,7 @@
 // Roofline: HBM.  forward 4*(B*Ci*H*W + B*Co*Ho*Wo) bytes, dgrad 4*(B*Co*Ho*Wo + B*Ci*H*W) bytes per launch.
 #include <cstdlib>
 
-#include "common.h"
+#include "conv_families.h"
 
 using namespace cnn_amd;
 
@@ -1232,14 +1232,6 @@ inline unsigned wave_grid(long long rows) {
 }  // namespace
 
 namespace cnn_amd {
-bool dgrad_rd_supported(const cnn_conv2d_desc* d);  // conv_dgrad_rd.hip (takes precedence over the packed stride-2 kernel)
-// conv_wgrad_win.hip: the window-major MFMA weight gradient of this layer (default; CNN_AMD_WG_WIN=0: the packed VALU kernel below)
-int win_wgrad_slots(const cnn_conv2d_desc* d);
-int win_wgrad_launch(const cnn_conv2d_desc* d, const float* x, const float* dy, const int32_t* mask, const float* pooled, float* slabs,
-                     hipStream_t s);
-
-#define CONV_TAG(d) "B%d Ci%d %dx%d Co%d k%d s%d p%d", (d)->B, (d)->Ci, (d)->H, (d)->W, (d)->Co, (d)->k, (d)->s, (d)->pad
-
 // returns 1 when the geometry has a direct kernel (and it was launched), 0 when the caller must use the implicit GEMM,
 // < 0 on error
 bool direct_conv_supported(const cnn_conv2d_desc* d) {
@@ -1285,7 +1277,6 @@ bool direct_conv_pool_supported(const cnn_conv2d_desc* d) {
 }
 // the packed one-byte pool mask (include/cnn_amd.h): written by conv_fwd_pool_pk<.., true>, read by the LDS-staged data gradient and
 // the window kernel only -- switches that select the older kernels of the block turn it off
-bool direct_dgrad_pk_ok(const cnn_conv2d_desc* d);
 bool direct_pool_mask_packed_ok(const cnn_conv2d_desc* d) {
     if (!direct_conv_pool_supported(d) || win_wgrad_slots(d) <= 0 || CNN_OPT_INT("DGRAD_POOL_LDS", 1) == 0) return false;
     if (CNN_OPT_INT("WG_POOL_RD", 0) != 0 || CNN_OPT_INT("POOL_MASK_PACKED", 1) == 0 || !direct_dgrad_pk_ok(d)) return false;
@@ -1461,34 +1452,20 @@ int pk_dgrad_s2(const cnn_conv2d_desc* d, const float* dy, const float* w, float
     return CNN_AMD_OK;
 }
 
-// Packs, in ONE launch, the filters of every listed layer that runs on a kernel of this file; sets bit i of *fwd_done /
-// *dgrad_done for the layers it handled (the implicit-GEMM layers are prepared by conv_igemm.hip).
-int direct_prepare_batch(int n, const cnn_conv2d_desc* descs, const float* const* w, const float* const* bias,
-                         void* const* fwd, void* const* dgrad, hipStream_t s, unsigned* fwd_done, unsigned* dgrad_done) {
+// Packs, in ONE launch, the filters of the jobs that resolved to a kernel of this file: the first layer's forward and data
+// gradient, and the packed stride-2 data gradient (conv_dispatch.hip)
+int direct_prepare_batch(int n, const ConvPrepJob* jobs, hipStream_t s) {
     PackBatch pb;
+    CNN_REQUIRE(n <= (int)(sizeof(pb.j) / sizeof(pb.j[0])), "cnn_conv2d_prepare_filters: %d packed-filter jobs in one call", n);
     pb.n = 0;
-    *fwd_done = *dgrad_done = 0;
     for (int i = 0; i < n; ++i) {
-        const cnn_conv2d_desc* d = &descs[i];
-        if (direct_conv_supported(d) && direct_fwd_pk_ok(d) && fwd && fwd[i] && pb.n < 8) {
-            pb.j[pb.n++] = PackJob{0, w[i], bias[i], (float*)fwd[i], 3, 16};
-            *fwd_done |= 1u << i;
-        }
-        if (direct_conv_supported(d) && direct_dgrad_pk_ok(d) && dgrad && dgrad[i] && pb.n < 8) {
-            pb.j[pb.n++] = PackJob{1, w[i], nullptr, (float*)dgrad[i], 3, 16};
-            *dgrad_done |= 1u << i;
-        } else if (!direct_conv_supported(d) && pk_dgrad_s2_supported(d) && !dgrad_rd_supported(d) && dgrad && dgrad[i] && pb.n < 8) {
-            pb.j[pb.n++] = PackJob{2, w[i], nullptr, (float*)dgrad[i], d->Ci, d->Co};
-            *dgrad_done |= 1u << i;
-        }
+        const cnn_conv2d_desc* d = jobs[i].d;
+        if (!direct_conv_supported(d)) pb.j[pb.n++] = PackJob{2, jobs[i].w, nullptr, jobs[i].image, d->Ci, d->Co};
+        else if (jobs[i].mode == MODE_FWD) pb.j[pb.n++] = PackJob{0, jobs[i].w, jobs[i].bias, jobs[i].image, 3, 16};
+        else pb.j[pb.n++] = PackJob{1, jobs[i].w, nullptr, jobs[i].image, 3, 16};
     }
     if (pb.n > 0) CNN_KLAUNCH(s, "pack_batch", (pack_batch<<<dim3(8, pb.n), 256, 0, s>>>(pb)), "jobs=%d", pb.n);
     return CNN_AMD_OK;
-}
-// can this layer's forward / data gradient run from prepared filters?
-bool direct_prepared_fwd_ok(const cnn_conv2d_desc* d) { return direct_conv_supported(d) && direct_fwd_pk_ok(d); }
-bool direct_prepared_dgrad_ok(const cnn_conv2d_desc* d) {
-    return (direct_conv_supported(d) && direct_dgrad_pk_ok(d)) || (!direct_conv_supported(d) && pk_dgrad_s2_supported(d) && !dgrad_rd_supported(d));
 }
 
 // number of slabs (workgroups) the packed weight-gradient kernel writes; 0 when the geometry / sizes rule it out

@@ -14,13 +14,9 @@
 // for the fused Conv+ReLU entry, max(y, 0) to the second tensor.
 #include <cstdlib>
 
-#include "common.h"
+#include "conv_families.h"
 
 using namespace cnn_amd;
-
-namespace cnn_amd {
-bool igemm_preferred(const cnn_conv2d_desc* d, int mode);  // conv_igemm.hip (mode 0 forward, 1 data gradient)
-}
 
 namespace {
 
@@ -491,40 +487,35 @@ size_t fwd_rd_prepared_floats(const cnn_conv2d_desc* d) {
     return a > b ? a : b;
 }
 
-int dgrad_rd_prepare_layout(const cnn_conv2d_desc* d, int* transposed);  // conv_dgrad_rd.hip
-
-// prepares, in ONE launch, the forward images of every layer this file covers and the data-gradient filter copies of the
-// layers conv_dgrad_rd.hip covers; sets their bits in *fdone / *ddone
-int rd_prepare_batch(int n, const cnn_conv2d_desc* descs, const float* const* w, const float* const* bias, void* const* fwd,
-                     void* const* dgrad, hipStream_t s, unsigned* fdone, unsigned* ddone) {
+// prepares, in ONE launch, the forward images of the jobs that resolved to this file's kernels and the data-gradient filter
+// copies of those that resolved to conv_dgrad_rd.hip's
+int rd_prepare_batch(int n, const ConvPrepJob* jobs, hipStream_t s) {
     FwdRdPrepBatch pb;
-    int jobs = 0;
+    CNN_REQUIRE(n <= (int)(sizeof(pb.job) / sizeof(pb.job[0])), "cnn_conv2d_prepare_filters: %d register-direct jobs in one call", n);
     size_t most = 0;
-    for (int i = 0; i < n && i < 6; ++i) {
-        FwdRdPlan pl;
-        if (fwd && fwd[i] && !(*fdone >> i & 1u) && make_plan(&descs[i], &pl)) {
-            CNN_REQUIRE(w[i] && bias[i], "cnn_conv2d_prepare_filters: filters / bias of layer %d are null", i);
-            FwdRdPrepJob& j = pb.job[jobs++];
-            j.kind = pl.m16 ? 2 : 0; j.w = w[i]; j.bias = bias[i]; j.img = (float*)fwd[i];
-            j.Co = descs[i].Co; j.Ci = descs[i].Ci; j.cb = pl.mt * 32; j.img_floats = (int)pl.img_floats; j.cgroups = pl.cgroups; j.tr = 0;
+    for (int i = 0; i < n; ++i) {
+        const cnn_conv2d_desc* d = jobs[i].d;
+        FwdRdPrepJob& j = pb.job[i];
+        j.w = jobs[i].w; j.img = jobs[i].image; j.Co = d->Co; j.Ci = d->Ci;
+        if (jobs[i].mode == MODE_FWD) {
+            FwdRdPlan pl;
+            CNN_REQUIRE(make_plan(d, &pl), "conv_fwd_rd: geometry not covered");
+            CNN_REQUIRE(jobs[i].bias, "cnn_conv2d_prepare_filters: filters / bias of layer %d are null", jobs[i].layer);
+            j.kind = pl.m16 ? 2 : 0; j.bias = jobs[i].bias;
+            j.cb = pl.mt * 32; j.img_floats = (int)pl.img_floats; j.cgroups = pl.cgroups; j.tr = 0;
             if (pl.img_floats * pl.cgroups > most) most = pl.img_floats * pl.cgroups;
-            *fdone |= 1u << i;
-        }
-        int tr = 0;
-        if (dgrad && dgrad[i] && !(*ddone >> i & 1u) && dgrad_rd_prepare_layout(&descs[i], &tr)) {
-            CNN_REQUIRE(w[i] != nullptr, "cnn_conv2d_prepare_filters: filters of layer %d are null", i);
-            FwdRdPrepJob& j = pb.job[jobs++];
-            j.kind = 1; j.w = w[i]; j.bias = nullptr; j.img = (float*)dgrad[i];
-            j.Co = descs[i].Co; j.Ci = descs[i].Ci; j.cb = 0; j.img_floats = 0; j.cgroups = 0; j.tr = tr;
-            const size_t nf = (size_t)descs[i].Co * descs[i].Ci * 9;
+        } else {
+            int tr = 0;
+            CNN_REQUIRE(dgrad_rd_prepare_layout(d, &tr), "conv_dgrad_rd: geometry not covered");
+            j.kind = 1; j.bias = nullptr; j.cb = 0; j.img_floats = 0; j.cgroups = 0; j.tr = tr;
+            const size_t nf = (size_t)d->Co * d->Ci * 9;
             if (nf > most) most = nf;
-            *ddone |= 1u << i;
         }
     }
-    if (jobs) {
+    if (n > 0) {
         unsigned gx = (unsigned)((most + 255) / 256);
         if (gx > 512) gx = 512;
-        CNN_KLAUNCH(s, "rd_prepare", (fwd_rd_prepare_kernel<<<dim3(gx, jobs), 256, 0, s>>>(pb)), "jobs=%d", jobs);
+        CNN_KLAUNCH(s, "rd_prepare", (fwd_rd_prepare_kernel<<<dim3(gx, n), 256, 0, s>>>(pb)), "jobs=%d", n);
     }
     return CNN_AMD_OK;
 }

@@ -26,7 +26,7 @@
 #include <map>
 #include <mutex>
 
-#include "common.h"
+#include "conv_families.h"
 
 using namespace cnn_amd;
 
@@ -66,8 +66,6 @@ struct IgemmParams {
     int ksplit;         // DMA kernel: blockIdx.z = one of ksplit contiguous chunk ranges; partial sums go to Y + z * zstride (split_reduce adds them)
     long long zstride;  // floats per partial output tensor
 };
-
-enum { MODE_FWD = 0, MODE_DGRAD = 1 };
 
 template <int MF>
 struct Acc;
@@ -1262,6 +1260,7 @@ std::map<TuneKey, bool>& prefer_table() {
     static std::map<TuneKey, bool> t;
     return t;
 }
+std::atomic<unsigned> g_prefer_generation{1};  // moves whenever prefer_table() is written: the route memo of conv_dispatch.hip keys on it
 thread_local int g_forced_cfg = -1;  // >= 0: make_plan must use exactly this configuration (the tuner's probe runs)
 // candidates: the rule-based default (-1) plus the tiles that won somewhere in tools/sweep_igemm.py
 // 227 (round 3): 64 output rows x 512 pixels per workgroup, every wave a 2 x 2 block of 32x32 MFMA tiles -- for M = 64 (the data
@@ -1496,8 +1495,6 @@ int make_plan(const char* who, const cnn_conv2d_desc* d, int mode, Plan* pl, boo
     return CNN_AMD_OK;
 }
 
-#define CONV_TAG(d) "B%d Ci%d %dx%d Co%d k%d s%d p%d", (d)->B, (d)->Ci, (d)->H, (d)->W, (d)->Co, (d)->k, (d)->s, (d)->pad
-
 template <int MF, int MA, int NB, int WM, int WN, int CK, bool NARROW, bool R2>
 int launch_cfg3(const Plan& pl, hipStream_t s, const cnn_conv2d_desc* d) {
     auto kern = igemm_kernel<MF, MA, NB, WM, WN, CK, NARROW, R2>;
@@ -1653,163 +1650,62 @@ int run_plan(Plan& pl, const cnn_conv2d_desc* d, const float* X, const float* w,
     }
 }
 
-int check_desc(const char* who, const cnn_conv2d_desc* d) {
-    CNN_REQUIRE(d != nullptr, "%s: desc is null", who);
-    CNN_REQUIRE(d->B > 0 && d->Ci > 0 && d->H > 0 && d->W > 0 && d->Co > 0 && d->k > 0 && d->s > 0 && d->pad >= 0,
-                "%s: bad desc B=%d Ci=%d H=%d W=%d Co=%d k=%d s=%d pad=%d", who, d->B, d->Ci, d->H, d->W, d->Co, d->k,
-                d->s, d->pad);
-    CNN_REQUIRE(d->H + 2 * d->pad >= d->k && d->W + 2 * d->pad >= d->k, "%s: kernel %d larger than padded input", who,
-                d->k);
-    CNN_REQUIRE((d->flags & ~CNN_CONV2D_POOL_MASK_PACKED) == 0, "%s: unknown desc flags 0x%x", who, (unsigned)d->flags);
-    return CNN_AMD_OK;
-}
-
 }  // namespace
 
 namespace cnn_amd {
-bool direct_conv_supported(const cnn_conv2d_desc* d);  // conv_direct.hip: thin first layers bypass the implicit GEMM
-int direct_conv_forward(const cnn_conv2d_desc* d, const float* x, const float* w, const float* bias, float* y, float* y_relu,
-                        void* ws, size_t ws_bytes, hipStream_t s, bool prepared);
-int direct_conv_dgrad(const cnn_conv2d_desc* d, const float* dy, const float* w, float* dx, void* ws, size_t ws_bytes,
-                      hipStream_t s, bool prepared);
-int direct_prepare_batch(int n, const cnn_conv2d_desc* descs, const float* const* w, const float* const* bias,
-                         void* const* fwd, void* const* dgrad, hipStream_t s, unsigned* fwd_done, unsigned* dgrad_done);
-bool direct_prepared_fwd_ok(const cnn_conv2d_desc* d);
-bool direct_prepared_dgrad_ok(const cnn_conv2d_desc* d);
-bool direct_conv_pool_supported(const cnn_conv2d_desc* d);  // conv_direct.hip: Conv -> ReLU -> MaxPool(2,2) in one kernel
-size_t direct_pool_mask_bytes(const cnn_conv2d_desc* d);
-int direct_pool_mask_unpack(const cnn_conv2d_desc* d, const void* packed, int32_t* mask, hipStream_t s);
-int direct_conv_pool_forward(const cnn_conv2d_desc* d, const float* x, const float* w, const float* bias, float* pooled,
-                             int32_t* mask, void* ws, size_t ws_bytes, hipStream_t s, bool prepared);
-int direct_conv_dgrad_pooled(const cnn_conv2d_desc* d, const float* dpool, const int32_t* mask, const float* pooled, const float* w,
-                             float* dx, void* ws, size_t ws_bytes, hipStream_t s, bool prepared);
-bool dgrad_rd_supported(const cnn_conv2d_desc* d);  // conv_dgrad_rd.hip: register-direct data gradient, 3x3 stride 2, Co 64 / 128
-size_t dgrad_rd_prepared_floats(const cnn_conv2d_desc* d);
-int dgrad_rd_backward_data(const cnn_conv2d_desc* d, const float* dy, const float* w, const float* img, const float* relu_below,
-                           float* dx, void* ws, size_t ws_bytes, hipStream_t s);
-size_t rows_workspace_floats(const cnn_conv2d_desc* d, int mode);  // conv_rows.hip (round 5): LDS-staged 3x3 / stride-1 forward and data gradient
-int rows_prepare(const cnn_conv2d_desc* d, int mode, const float* w, float* image, hipStream_t s);
-int rows_prepare_batch(int n, const cnn_conv2d_desc* const* d, const int* mode, const float* const* w, float* const* image, hipStream_t s);                                   // of wide planes
-int rows_run(const cnn_conv2d_desc* d, int mode, const float* in, const float* image, const float* bias, float* out, float* out_relu,
-             const float* relu_below, hipStream_t s);
-bool fwd_rd_supported(const cnn_conv2d_desc* d);  // conv_fwd_rd.hip: register-direct forward of the mid-size 3x3 layers
-size_t fwd_rd_prepared_floats(const cnn_conv2d_desc* d);
-int rd_prepare_batch(int n, const cnn_conv2d_desc* descs, const float* const* w, const float* const* bias, void* const* fwd,
-                     void* const* dgrad, hipStream_t s, unsigned* fdone, unsigned* ddone);
-int fwd_rd_forward(const cnn_conv2d_desc* d, const float* x, const float* w, const float* img, const float* bias, float* y,
-                   float* y_relu, hipStream_t s);
-bool fwd_rd_small(const cnn_conv2d_desc* d);           // conv_fwd_rd.hip: the small-layer kernel (never replaced)
-bool stem_fwd_supported(const cnn_conv2d_desc* d);     // conv_stem.hip: Ci = 3, 7x7, stride 2, pad 3 forward on its own MFMA kernel
-int stem_forward(const cnn_conv2d_desc* d, const float* x, const float* w, const float* bias, float* y, float* y_relu, hipStream_t s);
-bool thin_dgrad_supported(const cnn_conv2d_desc* d);   // conv_dgrad_thin.hip: VALU data gradient of thin (Ci = 3) stride-1 layers
-int thin_dgrad(const cnn_conv2d_desc* d, const float* dy, const float* w, const float* packed, const float* relu_below, float* dx, hipStream_t s);
-size_t thin_dgrad_packed_floats(const cnn_conv2d_desc* d);  // > 0: the layer's data gradient reads a packed filter image (the 7x7 stem) ...
-int thin_dgrad_pack(const cnn_conv2d_desc* d, const float* w, float* image, hipStream_t s);  // ... made by this
-bool c11_supported(const cnn_conv2d_desc* d);          // conv_1x1.hip: 1x1 convolutions (stride 1 / 2) as plain LDS-tiled GEMMs
-int c11_forward(const cnn_conv2d_desc* d, const float* x, const float* w, const float* bias, float* y, float* y_relu, hipStream_t s);
-int c11_backward_data(const cnn_conv2d_desc* d, const float* dy, const float* w, const float* relu_below, float* dx, hipStream_t s);
-bool pk_dgrad_s2_supported(const cnn_conv2d_desc* d);  // conv_direct.hip: packed VALU dgrad for small stride-2 layers
-size_t pk_dgrad_s2_workspace_floats(const cnn_conv2d_desc* d);
-int pk_dgrad_s2(const cnn_conv2d_desc* d, const float* dy, const float* w, float* dx, void* ws, hipStream_t s, bool prepared,
-                const float* relu_below);
-// scratch floats the forward / dgrad plans need (used by cnn_conv2d_workspace_bytes in conv_wgrad.hip)
 bool igemm_preferred(const cnn_conv2d_desc* d, int mode) {
     std::lock_guard<std::mutex> lk(tune_mutex());
     auto it = prefer_table().find(tune_key(d, mode));
     return it != prefer_table().end() && it->second;
 }
+unsigned igemm_prefer_generation() { return g_prefer_generation.load(std::memory_order_acquire); }
 
-size_t igemm_workspace_floats(const cnn_conv2d_desc* d) {
-    static thread_local DescMemo memo;  // (independent of what the tuner has pinned: every candidate is planned regardless)
+// (independent of what the tuner has pinned: every candidate is planned regardless; memoized by the caller, igemm_workspace_floats)
+size_t igemm_image_floats(const cnn_conv2d_desc* d, int mode) {
     size_t n = 0;
-    if (memo.find(d, &n)) return n;
-    // the largest re-arranged filter image any tile the tuner may pin would need (the caller sizes its buffers once)
-    for (int c : kTuneCandidates)
-        for (int mode = 0; mode < 2; ++mode) {
-            Plan pl;
-            g_forced_cfg = c;
-            const int rc = make_plan("ws", d, mode, &pl);
-            g_forced_cfg = -1;
-            if (rc != CNN_AMD_OK || (c >= 0 && pl.cfg != c)) continue;
-            const size_t need = pl.ksplit > 1 ? (pl.a_floats + 63) / 64 * 64 + (size_t)pl.ksplit * (size_t)pl.p.zstride : pl.a_floats;
-            if (need > n) n = need;
-        }
-    if (direct_conv_supported(d) && n < 1024) n = 1024;  // packed filter copies of the direct kernels (conv_direct.hip)
-    if (c11_supported(d) && n < (size_t)d->Co * d->Ci) n = (size_t)d->Co * d->Ci;  // (conv_1x1.hip: the prepared image is a verbatim copy)
-    if (pk_dgrad_s2_supported(d) && n < pk_dgrad_s2_workspace_floats(d)) n = pk_dgrad_s2_workspace_floats(d);
-    if (fwd_rd_prepared_floats(d) > n) n = fwd_rd_prepared_floats(d);
-    if (dgrad_rd_prepared_floats(d) > n) n = dgrad_rd_prepared_floats(d);
-    if (thin_dgrad_supported(d) && thin_dgrad_packed_floats(d) > n) n = thin_dgrad_packed_floats(d);
-    for (int mode = 0; mode < 2; ++mode)
-        if (rows_workspace_floats(d, mode) > n) n = rows_workspace_floats(d, mode);
-    memo.put(d, n);
+    for (int c : kTuneCandidates) {
+        Plan pl;
+        g_forced_cfg = c;
+        const int rc = make_plan("ws", d, mode, &pl);
+        g_forced_cfg = -1;
+        if (rc != CNN_AMD_OK || (c >= 0 && pl.cfg != c)) continue;
+        const size_t need = pl.ksplit > 1 ? (pl.a_floats + 63) / 64 * 64 + (size_t)pl.ksplit * (size_t)pl.p.zstride : pl.a_floats;
+        if (need > n) n = need;
+    }
     return n;
+}
+
+int igemm_run(const char* who, const cnn_conv2d_desc* d, int mode, const float* in, const float* w, const float* bias, float* out,
+              float* out2, void* ws, size_t ws_bytes, hipStream_t s, bool prepared) {
+    Plan pl;
+    if (int rc = make_plan(who, d, mode, &pl)) return rc;
+    return run_plan(pl, d, in, w, bias, out, out2, ws, ws_bytes, s, who, prepared);
+}
+
+// the re-arranged filter images of all jobs in one launch
+int igemm_prepare_batch(int n, const ConvPrepJob* jobs, hipStream_t s) {
+    PrepBatch pb;
+    CNN_REQUIRE(n <= (int)(sizeof(pb.q) / sizeof(pb.q[0])), "cnn_conv2d_prepare_filters: %d implicit-GEMM jobs in one call", n);
+    pb.n = 0;
+    long long most = 0;
+    for (int i = 0; i < n; ++i) {
+        Plan pl;
+        if (int rc = make_plan("cnn_conv2d_prepare_filters", jobs[i].d, jobs[i].mode, &pl)) return rc;
+        pl.q.w = jobs[i].w;
+        pl.q.A = jobs[i].image;
+        pb.q[pb.n++] = pl.q;
+        if ((long long)pl.a_floats > most) most = (long long)pl.a_floats;
+    }
+    if (pb.n > 0) {
+        unsigned pg = (unsigned)((most + 255) / 256);
+        if (pg > 1024) pg = 1024;
+        CNN_KLAUNCH(s, "igemm_prep_batch", (igemm_prep_batch<<<dim3(pg, pb.n), 256, 0, s>>>(pb)), "jobs=%d", pb.n);
+    }
+    return CNN_AMD_OK;
 }
 }  // namespace cnn_amd
 
 extern "C" {
-
-static int conv2d_forward_impl(const char* who, const cnn_conv2d_desc* d, const float* x, const float* w, const float* bias,
-                               float* y, float* y_relu, void* ws, size_t ws_bytes, void* stream, bool prepared = false) {
-    if (int rc = check_desc(who, d)) return rc;
-    // y may be NULL when only the ReLU output is wanted and the layer runs on the register-direct forward kernel
-    CNN_REQUIRE(x && (w || prepared) && bias && (y || (y_relu && !direct_conv_supported(d) && !stem_fwd_supported(d))), "%s: null pointer", who);
-    if (direct_conv_supported(d)) return direct_conv_forward(d, x, w, bias, y, y_relu, ws, ws_bytes, as_stream(stream), prepared);
-    if (c11_supported(d))  // (its "prepared" image is a verbatim copy of w)
-        return c11_forward(d, x, prepared ? (const float*)ws : w, bias, y, y_relu, as_stream(stream));
-    // (round 5) wide 3x3 / stride-1 layers: the row kernel (conv_rows.hip); the workspace / prepared buffer holds its filter image
-    if (rows_workspace_floats(d, MODE_FWD) > 0 && ws != nullptr && ws_bytes >= rows_workspace_floats(d, MODE_FWD) * sizeof(float) &&
-        (reinterpret_cast<uintptr_t>(ws) & 15) == 0) {
-        if (!prepared)
-            if (int rc = rows_prepare(d, MODE_FWD, w, (float*)ws, as_stream(stream))) return rc;
-        return rows_run(d, MODE_FWD, x, (const float*)ws, bias, y, y_relu, nullptr, as_stream(stream));
-    }
-    if (fwd_rd_supported(d))
-        return fwd_rd_forward(d, x, prepared ? nullptr : w, prepared ? (const float*)ws : nullptr, bias, y, y_relu, as_stream(stream));
-    if (stem_fwd_supported(d) && (y || y_relu))  // (its "prepared" image is a verbatim copy of w)
-        return stem_forward(d, x, prepared ? (const float*)ws : w, bias, y, y_relu, as_stream(stream));
-    Plan pl;
-    if (int rc = make_plan(who, d, MODE_FWD, &pl)) return rc;
-    return run_plan(pl, d, x, w, bias, y, y_relu, ws, ws_bytes, as_stream(stream), who, prepared);
-}
-
-// relu_below (nullable): output of the ReLU layer whose input gradient dx is -- fuses that layer's backward pass
-static int conv2d_backward_data_impl(const char* who, const cnn_conv2d_desc* d, const float* dy, const float* w, float* dx,
-                                     void* ws, size_t ws_bytes, void* stream, bool prepared, const float* relu_below = nullptr) {
-    if (int rc = check_desc(who, d)) return rc;
-    CNN_REQUIRE(dy && (w || prepared) && dx, "%s: null pointer", who);
-    if (direct_conv_supported(d)) {  // the first-layer kernels have no masked epilogue: same result from the ReLU kernel
-        const int rc = direct_conv_dgrad(d, dy, w, dx, ws, ws_bytes, as_stream(stream), prepared);
-        if (rc || !relu_below) return rc;
-        return cnn_relu_backward(relu_below, dx, (size_t)d->B * d->Ci * d->H * d->W, stream);
-    }
-    if (c11_supported(d))  // (its "prepared" image is a verbatim copy of w)
-        return c11_backward_data(d, dy, prepared ? (const float*)ws : w, relu_below, dx, as_stream(stream));
-    if (thin_dgrad_supported(d)) {
-        const size_t pk = thin_dgrad_packed_floats(d);
-        if (pk == 0)  // (the "prepared" image of such a layer is a verbatim copy of w)
-            return thin_dgrad(d, dy, prepared ? (const float*)ws : w, nullptr, relu_below, dx, as_stream(stream));
-        if (prepared) return thin_dgrad(d, dy, nullptr, (const float*)ws, relu_below, dx, as_stream(stream));  // (prepared image = the packed one)
-        if (ws == nullptr || ws_bytes < pk * sizeof(float))
-            return thin_dgrad(d, dy, w, nullptr, relu_below, dx, as_stream(stream));  // (no room for the packed image: the scalar-operand kernel)
-        if (int rc = thin_dgrad_pack(d, w, (float*)ws, as_stream(stream))) return rc;
-        return thin_dgrad(d, dy, nullptr, (const float*)ws, relu_below, dx, as_stream(stream));
-    }
-    if (rows_workspace_floats(d, MODE_DGRAD) > 0 && ws != nullptr && ws_bytes >= rows_workspace_floats(d, MODE_DGRAD) * sizeof(float) &&
-        (reinterpret_cast<uintptr_t>(ws) & 15) == 0) {
-        if (!prepared)
-            if (int rc = rows_prepare(d, MODE_DGRAD, w, (float*)ws, as_stream(stream))) return rc;
-        return rows_run(d, MODE_DGRAD, dy, (const float*)ws, nullptr, dx, nullptr, relu_below, as_stream(stream));
-    }
-    if (dgrad_rd_supported(d))
-        return dgrad_rd_backward_data(d, dy, prepared ? nullptr : w, prepared ? (const float*)ws : nullptr, relu_below, dx,
-                                      prepared ? nullptr : ws, prepared ? 0 : ws_bytes, as_stream(stream));
-    if (pk_dgrad_s2_supported(d) && ws != nullptr && ws_bytes >= pk_dgrad_s2_workspace_floats(d) * sizeof(float))
-        return pk_dgrad_s2(d, dy, w, dx, ws, as_stream(stream), prepared, relu_below);
-    Plan pl;
-    if (int rc = make_plan(who, d, MODE_DGRAD, &pl)) return rc;
-    return run_plan(pl, d, dy, w, nullptr, dx, const_cast<float*>(relu_below), ws, ws_bytes, as_stream(stream), who, prepared);
-}
 
 // floats of scratch one measurement needs: x, y, w, the implicit GEMM's workspace / prepared image, bias + per-channel scratch
 static size_t autotune_scratch_floats(const cnn_conv2d_desc* d, size_t* nx, size_t* ny, size_t* nw, size_t* na) {
@@ -1962,6 +1858,7 @@ static int autotune_impl(const cnn_conv2d_desc* d, void* scratch, size_t scratch
             // the register-direct kernel keeps its layer unless the implicit GEMM is clearly faster
             std::lock_guard<std::mutex> lk(tune_mutex());
             prefer_table()[tune_key(d, mode)] = best_ms < rd_ms * 0.97f;
+            g_prefer_generation.fetch_add(1, std::memory_order_release);
         }
         if (best >= 0) {
             std::lock_guard<std::mutex> lk(tune_mutex());
@@ -2007,195 +1904,12 @@ int cnn_conv2d_tune_import(const cnn_conv2d_desc* d, const int32_t in[4]) {
     std::lock_guard<std::mutex> lk(tune_mutex());
     for (int mode = 0; mode < 2; ++mode) {
         if (in[mode] != CNN_TUNE_NONE) tune_table()[tune_key(d, mode)] = in[mode];
-        if (in[2 + mode] != CNN_TUNE_NONE) prefer_table()[tune_key(d, mode)] = in[2 + mode] != 0;
-    }
-    return CNN_AMD_OK;
-}
-
-int cnn_conv2d_forward(const cnn_conv2d_desc* d, const float* x, const float* w, const float* bias, float* y,
-                       void* ws, size_t ws_bytes, void* stream) {
-    return conv2d_forward_impl("cnn_conv2d_forward", d, x, w, bias, y, nullptr, ws, ws_bytes, stream);
-}
-
-int cnn_conv2d_forward_relu(const cnn_conv2d_desc* d, const float* x, const float* w, const float* bias, float* y,
-                            float* y_relu, void* ws, size_t ws_bytes, void* stream) {
-    CNN_REQUIRE(y_relu, "cnn_conv2d_forward_relu: null pointer");
-    return conv2d_forward_impl("cnn_conv2d_forward_relu", d, x, w, bias, y, y_relu, ws, ws_bytes, stream);
-}
-
-int cnn_conv2d_backward_data(const cnn_conv2d_desc* d, const float* dy, const float* w, float* dx, void* ws,
-                             size_t ws_bytes, void* stream) {
-    return conv2d_backward_data_impl("cnn_conv2d_backward_data", d, dy, w, dx, ws, ws_bytes, stream, false);
-}
-
-int cnn_conv2d_relu_only_supported(const cnn_conv2d_desc* d) {
-    if (check_desc("cnn_conv2d_relu_only_supported", d)) return 0;
-    // (round 4: the implicit GEMM's fused-ReLU epilogue too -- every kernel family behind cnn_conv2d_forward except the thin first layers')
-    return (!direct_conv_supported(d) && !stem_fwd_supported(d)) ? 1 : 0;
-}
-
-/* ---- Conv2D -> ReLU -> MaxPool2D(2,2) ---- */
-int cnn_conv2d_relu_maxpool2_supported(const cnn_conv2d_desc* d) {
-    if (check_desc("cnn_conv2d_relu_maxpool2_supported", d)) return 0;
-    return direct_conv_pool_supported(d) ? 1 : 0;
-}
-
-int cnn_conv2d_pool_mask_packed_supported(const cnn_conv2d_desc* d) {
-    if (check_desc("cnn_conv2d_pool_mask_packed_supported", d)) return 0;
-    return direct_pool_mask_packed_ok(d) ? 1 : 0;
-}
-size_t cnn_conv2d_pool_mask_bytes(const cnn_conv2d_desc* d) {
-    if (check_desc("cnn_conv2d_pool_mask_bytes", d)) return 0;
-    return direct_pool_mask_bytes(d);
-}
-int cnn_conv2d_pool_mask_unpack(const cnn_conv2d_desc* d, const void* packed, int32_t* mask, void* stream) {
-    if (int rc = check_desc("cnn_conv2d_pool_mask_unpack", d)) return rc;
-    CNN_REQUIRE(packed && mask, "cnn_conv2d_pool_mask_unpack: null pointer");
-    return direct_pool_mask_unpack(d, packed, mask, as_stream(stream));
-}
-
-int cnn_conv2d_relu_maxpool2_forward(const cnn_conv2d_desc* d, const float* x, const float* w, const float* bias, float* pooled,
-                                     int32_t* mask, void* ws, size_t ws_bytes, void* stream) {
-    if (int rc = check_desc("cnn_conv2d_relu_maxpool2_forward", d)) return rc;
-    CNN_REQUIRE(x && w && bias && pooled, "cnn_conv2d_relu_maxpool2_forward: null pointer");
-    return direct_conv_pool_forward(d, x, w, bias, pooled, mask, ws, ws_bytes, as_stream(stream), false);
-}
-
-int cnn_conv2d_relu_maxpool2_forward_prepared(const cnn_conv2d_desc* d, const float* x, const void* prepared_fwd, float* pooled,
-                                              int32_t* mask, void* stream) {
-    if (int rc = check_desc("cnn_conv2d_relu_maxpool2_forward_prepared", d)) return rc;
-    CNN_REQUIRE(x && prepared_fwd && pooled, "cnn_conv2d_relu_maxpool2_forward_prepared: null pointer");
-    return direct_conv_pool_forward(d, x, nullptr, nullptr, pooled, mask, (void*)prepared_fwd, cnn_conv2d_prepared_bytes(d),
-                                    as_stream(stream), true);
-}
-
-int cnn_conv2d_backward_data_pooled2(const cnn_conv2d_desc* d, const float* dpool, const int32_t* mask, const float* pooled,
-                                     const float* w, float* dx, void* ws, size_t ws_bytes, void* stream) {
-    if (int rc = check_desc("cnn_conv2d_backward_data_pooled2", d)) return rc;
-    CNN_REQUIRE(dpool && mask && w && dx, "cnn_conv2d_backward_data_pooled2: null pointer");
-    return direct_conv_dgrad_pooled(d, dpool, mask, pooled, w, dx, ws, ws_bytes, as_stream(stream), false);
-}
-
-int cnn_conv2d_backward_data_pooled2_prepared(const cnn_conv2d_desc* d, const float* dpool, const int32_t* mask, const float* pooled,
-                                              const void* prepared_dgrad, float* dx, void* stream) {
-    if (int rc = check_desc("cnn_conv2d_backward_data_pooled2_prepared", d)) return rc;
-    CNN_REQUIRE(dpool && mask && prepared_dgrad && dx, "cnn_conv2d_backward_data_pooled2_prepared: null pointer");
-    return direct_conv_dgrad_pooled(d, dpool, mask, pooled, nullptr, dx, (void*)prepared_dgrad, cnn_conv2d_prepared_bytes(d),
-                                    as_stream(stream), true);
-}
-
-/* ---- filter preparation hoisted out of the per-layer calls ---- */
-size_t cnn_conv2d_prepared_bytes(const cnn_conv2d_desc* d) {
-    if (check_desc("cnn_conv2d_prepared_bytes", d)) return 0;
-    return (igemm_workspace_floats(d) + 64) * sizeof(float);
-}
-
-int cnn_conv2d_prepare_filters(int n, const cnn_conv2d_desc* descs, const float* const* w, const float* const* bias,
-                               void* const* fwd, void* const* dgrad, void* stream) {
-    CNN_REQUIRE(n > 0 && n <= 6 && descs && w && bias, "cnn_conv2d_prepare_filters: n=%d (1..6 layers per call)", n);
-    hipStream_t s = as_stream(stream);
-    unsigned fdone = 0, ddone = 0;
-    if (int rc = direct_prepare_batch(n, descs, w, bias, fwd, dgrad, s, &fdone, &ddone)) return rc;
-    {  // (round 5) the row kernel's layers: the per-layer entry points look for it before the register-direct kernels too (direct_prepare_batch resets the masks: it goes first); one launch for all of them
-        const cnn_conv2d_desc* rd[12];
-        int rmode[12], rn = 0;
-        const float* rw[12];
-        float* rimg[12];
-        for (int i = 0; i < n; ++i) {
-            if (check_desc("cnn_conv2d_prepare_filters", &descs[i]) || direct_conv_supported(&descs[i]) || c11_supported(&descs[i])) continue;
-            for (int mode = 0; mode < 2; ++mode) {
-                void* out = mode == MODE_FWD ? (fwd ? fwd[i] : nullptr) : (dgrad ? dgrad[i] : nullptr);
-                if (!out || rows_workspace_floats(&descs[i], mode) == 0 || (reinterpret_cast<uintptr_t>(out) & 15) != 0) continue;
-                CNN_REQUIRE(w[i] != nullptr, "cnn_conv2d_prepare_filters: filters of layer %d are null", i);
-                rd[rn] = &descs[i]; rmode[rn] = mode; rw[rn] = w[i]; rimg[rn] = (float*)out; ++rn;
-                (mode == MODE_FWD ? fdone : ddone) |= 1u << i;
-            }
-        }
-        if (rn > 0)
-            if (int rc = rows_prepare_batch(rn, rd, rmode, rw, rimg, s)) return rc;
-    }
-    if (int rc = rd_prepare_batch(n, descs, w, bias, fwd, dgrad, s, &fdone, &ddone)) return rc;
-    PrepBatch pb;
-    pb.n = 0;
-    long long most = 0;
-    for (int i = 0; i < n; ++i) {
-        if (int rc = check_desc("cnn_conv2d_prepare_filters", &descs[i])) return rc;
-        CNN_REQUIRE(w[i] != nullptr, "cnn_conv2d_prepare_filters: filters of layer %d are null", i);
-        for (int mode = 0; mode < 2; ++mode) {
-            void* out = mode == MODE_FWD ? (fwd ? fwd[i] : nullptr) : (dgrad ? dgrad[i] : nullptr);
-            if (!out || ((mode == MODE_FWD ? fdone : ddone) >> i & 1u)) continue;
-            if (!direct_conv_supported(&descs[i]) && c11_supported(&descs[i])) {
-                // conv_1x1.hip reads the reference layout in both directions: its prepared images are verbatim copies
-                CNN_HIP_CHECK(hipMemcpyAsync(out, w[i], sizeof(float) * (size_t)descs[i].Co * descs[i].Ci, hipMemcpyDeviceToDevice, s));
-                continue;
-            }
-            if (mode == MODE_FWD && !direct_conv_supported(&descs[i]) && !fwd_rd_supported(&descs[i]) && stem_fwd_supported(&descs[i])) {
-                // conv_stem.hip reads the reference layout: its prepared image is a verbatim copy
-                CNN_HIP_CHECK(hipMemcpyAsync(out, w[i], sizeof(float) * (size_t)descs[i].Co * descs[i].Ci * descs[i].k * descs[i].k,
-                                             hipMemcpyDeviceToDevice, s));
-                continue;
-            }
-            if (mode == MODE_DGRAD && !direct_conv_supported(&descs[i]) && thin_dgrad_supported(&descs[i])) {
-                if (thin_dgrad_packed_floats(&descs[i]) > 0) {  // the 7x7 stem: packed rows (conv_dgrad_thin_s2_pk7)
-                    if (int rc = thin_dgrad_pack(&descs[i], w[i], (float*)out, s)) return rc;
-                    continue;
-                }
-                // conv_dgrad_thin.hip reads the reference layout: its prepared image is a verbatim copy
-                CNN_HIP_CHECK(hipMemcpyAsync(out, w[i], sizeof(float) * (size_t)descs[i].Co * descs[i].Ci * descs[i].k * descs[i].k,
-                                             hipMemcpyDeviceToDevice, s));
-                continue;
-            }
-            CNN_REQUIRE(!direct_conv_supported(&descs[i]) && !(mode == MODE_DGRAD && pk_dgrad_s2_supported(&descs[i]) && !dgrad_rd_supported(&descs[i])),
-                        "cnn_conv2d_prepare_filters: layer %d has no prepared path for this mode", i);
-            Plan pl;
-            if (int rc = make_plan("cnn_conv2d_prepare_filters", &descs[i], mode, &pl)) return rc;
-            pl.q.w = w[i];
-            pl.q.A = (float*)out;
-            pb.q[pb.n++] = pl.q;
-            if ((long long)pl.a_floats > most) most = (long long)pl.a_floats;
+        if (in[2 + mode] != CNN_TUNE_NONE) {
+            prefer_table()[tune_key(d, mode)] = in[2 + mode] != 0;
+            g_prefer_generation.fetch_add(1, std::memory_order_release);
         }
     }
-    if (pb.n > 0) {
-        unsigned pg = (unsigned)((most + 255) / 256);
-        if (pg > 1024) pg = 1024;
-        CNN_KLAUNCH(s, "igemm_prep_batch", (igemm_prep_batch<<<dim3(pg, pb.n), 256, 0, s>>>(pb)), "jobs=%d", pb.n);
-    }
     return CNN_AMD_OK;
-}
-
-int cnn_conv2d_forward_prepared(const cnn_conv2d_desc* d, const float* x, const void* prepared_fwd, const float* bias, float* y,
-                                float* y_relu, void* stream) {
-    CNN_REQUIRE(prepared_fwd != nullptr, "cnn_conv2d_forward_prepared: null pointer");
-    if (int rc = check_desc("cnn_conv2d_forward_prepared", d)) return rc;
-    CNN_REQUIRE(!direct_conv_supported(d) || direct_prepared_fwd_ok(d), "cnn_conv2d_forward_prepared: no prepared path for this layer");
-    return conv2d_forward_impl("cnn_conv2d_forward_prepared", d, x, nullptr, bias, y, y_relu, (void*)prepared_fwd,
-                               cnn_conv2d_prepared_bytes(d), stream, true);
-}
-
-int cnn_conv2d_backward_data_relu(const cnn_conv2d_desc* d, const float* dy, const float* w, const float* relu_below, float* dx,
-                                  void* ws, size_t ws_bytes, void* stream) {
-    CNN_REQUIRE(relu_below, "cnn_conv2d_backward_data_relu: null pointer");
-    return conv2d_backward_data_impl("cnn_conv2d_backward_data_relu", d, dy, w, dx, ws, ws_bytes, stream, false, relu_below);
-}
-
-int cnn_conv2d_backward_data_relu_prepared(const cnn_conv2d_desc* d, const float* dy, const void* prepared_dgrad,
-                                           const float* relu_below, float* dx, void* stream) {
-    CNN_REQUIRE(prepared_dgrad != nullptr && relu_below != nullptr, "cnn_conv2d_backward_data_relu_prepared: null pointer");
-    if (int rc = check_desc("cnn_conv2d_backward_data_relu_prepared", d)) return rc;
-    CNN_REQUIRE(!direct_conv_supported(d) || direct_prepared_dgrad_ok(d),
-                "cnn_conv2d_backward_data_relu_prepared: no prepared path for this layer");
-    return conv2d_backward_data_impl("cnn_conv2d_backward_data_relu_prepared", d, dy, nullptr, dx, (void*)prepared_dgrad,
-                                     cnn_conv2d_prepared_bytes(d), stream, true, relu_below);
-}
-
-int cnn_conv2d_backward_data_prepared(const cnn_conv2d_desc* d, const float* dy, const void* prepared_dgrad, float* dx,
-                                      void* stream) {
-    CNN_REQUIRE(prepared_dgrad != nullptr, "cnn_conv2d_backward_data_prepared: null pointer");
-    if (int rc = check_desc("cnn_conv2d_backward_data_prepared", d)) return rc;
-    CNN_REQUIRE(!direct_conv_supported(d) || direct_prepared_dgrad_ok(d),
-                "cnn_conv2d_backward_data_prepared: no prepared path for this layer");
-    return conv2d_backward_data_impl("cnn_conv2d_backward_data_prepared", d, dy, nullptr, dx, (void*)prepared_dgrad,
-                                     cnn_conv2d_prepared_bytes(d), stream, true);
 }
 
 }  // extern "C"

@@ -5,7 +5,7 @@
 //   fwd : y[b]    = W[Co x K] * col[b][K x P] + bias          (conv2d.cpp:69-92)
 //   wgrad: gw     = (sum_b dy[b][Co x P] * col[b]^T) / divisor (conv2d.cpp:120-151), gb likewise (:153-157)
 //   dgrad: dcol[b]= W^T * dy[b]; dx = col2im(dcol) in gather form (conv2d.cpp:168-199)
-#include "common.h"
+#include "conv_families.h"
 
 using namespace cnn_amd;
 
@@ -23,17 +23,6 @@ Geo make_geo(const cnn_conv2d_desc* d) {
     g.K = d->Ci * d->k * d->k;
     g.P = g.Ho * g.Wo;
     return g;
-}
-
-int check_desc(const char* who, const cnn_conv2d_desc* d) {
-    CNN_REQUIRE(d != nullptr, "%s: desc is null", who);
-    CNN_REQUIRE(d->B > 0 && d->Ci > 0 && d->H > 0 && d->W > 0 && d->Co > 0 && d->k > 0 && d->s > 0 && d->pad >= 0,
-                "%s: bad desc B=%d Ci=%d H=%d W=%d Co=%d k=%d s=%d pad=%d", who, d->B, d->Ci, d->H, d->W, d->Co, d->k,
-                d->s, d->pad);
-    CNN_REQUIRE(d->H + 2 * d->pad >= d->k && d->W + 2 * d->pad >= d->k, "%s: kernel %d larger than padded input", who,
-                d->k);
-    CNN_REQUIRE((d->flags & ~CNN_CONV2D_POOL_MASK_PACKED) == 0, "%s: unknown desc flags 0x%x", who, (unsigned)d->flags);
-    return CNN_AMD_OK;
 }
 
 __global__ void im2col_kernel(const float* __restrict__ x, float* __restrict__ col, Geo g, int b0, int nb) {

@@ -17,7 +17,7 @@
 // Plane strides = 16 (mod 32): the four k-groups of a 16x16x4 operand read (two per 32-lane LDS access) hit disjoint bank halves.
 #include <cstdlib>
 
-#include "common.h"
+#include "conv_families.h"
 #include "rows_common.h"
 
 using namespace cnn_amd;
@@ -712,16 +712,8 @@ int launch_any(const RowsPlan& pl, const char* tag, const cnn_conv2d_desc* d, hi
 
 namespace cnn_amd {
 
-// conv_rows_s2.hip: the stride-2 sibling is served through the same four entry points (its filter image has the same layout)
-bool s2_info(const cnn_conv2d_desc* d, int mode, int* mt, int* qw, int* ck, int* nchunk, int* ntiles, size_t* wt_floats);
-int s2_run(const cnn_conv2d_desc* d, int mode, const float* in, const float* image, const float* bias, float* out, float* out_relu,
-           const float* relu_below, hipStream_t s);
-
-// conv_rows_any.hip: the runtime-width member of the family takes every 3x3 / stride-1 geometry the instances above do not
-bool any_info(const cnn_conv2d_desc* d, int mode, int* mt, int* qw, int* ck, int* nchunk, int* ntiles, size_t* wt_floats);
-int any_run(const cnn_conv2d_desc* d, int mode, const float* in, const float* image, const float* bias, float* out, float* out_relu,
-            const float* relu_below, hipStream_t s);
-
+// conv_rows_s2.hip (s2_*): the stride-2 sibling is served through the same four entry points (its filter image has the same layout);
+// conv_rows_any.hip (any_*): the runtime-width member of the family takes every 3x3 / stride-1 geometry the instances above do not.
 // the filter-image job of layer d in `mode`, whichever kernel family serves it
 static bool prep_job(const cnn_conv2d_desc* d, int mode, const float* w, float* image, RowsPrepJob* q, size_t* floats) {
     int mt, qw, ck, nchunk, ntiles;
@@ -743,7 +735,7 @@ static bool prep_job(const cnn_conv2d_desc* d, int mode, const float* w, float* 
 
 // floats of the row kernel's prepared filter image (0: geometry not covered in that mode); mode 0 = forward, 1 = data gradient
 size_t rows_workspace_floats(const cnn_conv2d_desc* d, int mode) {
-    static thread_local DescMemo memo[2];  // (called on every launch by the dispatch in conv_igemm.hip)
+    static thread_local DescMemo memo[2];  // (called on every launch by the dispatch in conv_dispatch.hip)
     size_t n = 0;
     if (memo[mode & 1].find(d, &n)) return n;
     RowsPrepJob q;
@@ -761,16 +753,17 @@ int rows_prepare(const cnn_conv2d_desc* d, int mode, const float* w, float* imag
                 "B%d Ci%d %dx%d Co%d k%d s%d p%d", d->B, d->Ci, d->H, d->W, d->Co, d->k, d->s, d->pad);
     return CNN_AMD_OK;
 }
-// the same for n (layer, mode) pairs in one launch; entries the row kernel does not cover are an error
-int rows_prepare_batch(int n, const cnn_conv2d_desc* const* d, const int* mode, const float* const* w, float* const* image, hipStream_t s) {
+// the same for n jobs in one launch; entries the row kernel does not cover are an error
+int rows_prepare_batch(int n, const ConvPrepJob* jobs, hipStream_t s) {
     for (int first = 0; first < n; first += kMaxRowsPrepJobs) {
         RowsPrepBatch b;
         const int cnt = n - first < kMaxRowsPrepJobs ? n - first : kMaxRowsPrepJobs;
         size_t most = 0;
         for (int i = 0; i < cnt; ++i) {
+            const ConvPrepJob& j = jobs[first + i];
             size_t floats = 0;
-            if (!prep_job(d[first + i], mode[first + i], w[first + i], image[first + i], &b.job[i], &floats)) return fail(CNN_AMD_E_BADARG, "conv_rows: geometry not covered");
-            CNN_REQUIRE(w[first + i] && image[first + i] && (reinterpret_cast<uintptr_t>(image[first + i]) & 15) == 0, "conv_rows: filter image must be 16-byte aligned");
+            if (!prep_job(j.d, j.mode, j.w, j.image, &b.job[i], &floats)) return fail(CNN_AMD_E_BADARG, "conv_rows: geometry not covered");
+            CNN_REQUIRE(j.w && j.image && (reinterpret_cast<uintptr_t>(j.image) & 15) == 0, "conv_rows: filter image must be 16-byte aligned");
             most = floats > most ? floats : most;
         }
         unsigned gx = (unsigned)((most + 255) / 256);

@@ -21,7 +21,7 @@
 // pad-p layer is the same kernel on dy with padding 2 - p and the transposed + flipped filter image (rows_prep mode 1).
 #include <cstdlib>
 
-#include "common.h"
+#include "conv_families.h"
 #include "rows_common.h"
 
 using namespace cnn_amd;

@@ -26,7 +26,7 @@
 // Waves: WM over channels x WP = 4 / WM over the unit's pixel blocks.
 #include <cstdlib>
 
-#include "common.h"
+#include "conv_families.h"
 #include "rows_common.h"
 
 using namespace cnn_amd;

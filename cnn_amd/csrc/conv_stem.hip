@@ -21,7 +21,7 @@
 // the next item's rows into registers behind the MFMAs, LDS-only barriers and the stores fired last (so that they drain under the
 // next item's MFMAs): 24 more live registers spill under the 128-register budget and the kernel got slower (227 us); the store
 // phase itself only reaches ~2.2 TB/s (448-byte rows: every second 128-byte segment straddles two lines); streaming stores: -2 %.
-#include "common.h"
+#include "conv_families.h"
 
 using namespace cnn_amd;
 
@@ -181,7 +181,6 @@ __global__ __launch_bounds__(SWAVES * 64, 4) void conv_stem_fwd_kernel(const Ste
     }
 }
 
-
 // ---- weight / bias gradient of the same layer (cpu/src/conv2d.cpp:117-159) ---------------------------------------------------------
 //   gw[co][ci][ky][kx] = sum_{b,oy,ox} dy[b][co][oy][ox] * x[b][ci][2oy+ky-3][2ox+kx-3],   gb[co] = sum dy[b][co][oy][ox]
 // GEMM on v_mfma_f32_16x16x4_f32: M = the 147 taps + one "tap" that reads a row of ones (its sums are the bias gradient) in ten
@@ -284,8 +283,6 @@ __global__ __launch_bounds__(GWAVES * 64, 4) void conv_stem_wgrad_kernel(const S
 }  // namespace
 
 namespace cnn_amd {
-
-#define CONV_TAG(d) "B%d Ci%d %dx%d Co%d k%d s%d p%d", (d)->B, (d)->Ci, (d)->H, (d)->W, (d)->Co, (d)->k, (d)->s, (d)->pad
 
 bool stem_fwd_supported(const cnn_conv2d_desc* d) {
     if (d->Ci != SCI || d->k != SK || d->s != SS || d->pad != SPAD || d->W % 4 != 0 || d->Co < 1) return false;

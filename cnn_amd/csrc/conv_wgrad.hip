@@ -9,34 +9,9 @@
 // Bias gradient (conv2d.cpp:153-157) is a per-channel two-stage reduction of dy.
 #include <cstdlib>
 
-#include "common.h"
+#include "conv_families.h"
 
 using namespace cnn_amd;
-
-namespace cnn_amd {
-size_t igemm_workspace_floats(const cnn_conv2d_desc* d);  // conv_igemm.hip
-int direct_wgrad_slots(const cnn_conv2d_desc* d);          // conv_direct.hip: thin first layer, packed VALU kernel
-int direct_conv_wgrad(const cnn_conv2d_desc* d, const float* x, const float* dy, float* slabs, hipStream_t s);
-bool direct_conv_pool_supported(const cnn_conv2d_desc* d);
-int direct_conv_wgrad_pooled(const cnn_conv2d_desc* d, const float* x, const float* dpool, const int32_t* mask, const float* pooled,
-                             float* slabs, hipStream_t s);
-int direct_first_layer_finish(const cnn_conv2d_desc* d, const float* slabs, int nslots, float divisor, float* gw, float* gb, float* w,
-                              float* bias, float lr, float grad_scale, void* fwd_img, void* dgrad_img, float* w_keep, float* bias_keep,
-                              hipStream_t s);
-int stem_wgrad_slots(const cnn_conv2d_desc* d);  // conv_stem.hip: 3 -> Co, 7x7, stride 2, pad 3
-int os_wgrad_slots(const cnn_conv2d_desc* d);    // conv_wgrad_os.hip: the reference net's small 3x3 / stride-2 layers, output-stationary
-int os_wgrad_launch(const cnn_conv2d_desc* d, const float* x, const float* dy, float* slabs, hipStream_t s);
-int c11_wgrad_slots(const cnn_conv2d_desc* d);   // conv_1x1.hip: 1x1 convolutions (stride 1 / 2): split-K GEMM over the sub-sampled plane
-int c11_wgrad_launch(const cnn_conv2d_desc* d, const float* x, const float* dy, float* slabs, hipStream_t s);
-int stem_wgrad_launch(const cnn_conv2d_desc* d, const float* x, const float* dy, float* slabs, hipStream_t s);
-int sp_wgrad_slots(const cnn_conv2d_desc* d);  // conv_wgrad_sp.hip: small planes (7x7 .. 56x56), 3x3 / stride 1 / pad 1, LDS-staged output-stationary
-int sp_wgrad_launch(const cnn_conv2d_desc* d, const float* x, const float* dy, float* slabs, hipStream_t s);
-int wgrad_rd_slots(const cnn_conv2d_desc* d);  // conv_wgrad_rd.hip: register-direct MFMA kernel (3x3, stride 1/2, pad 0)
-int wgrad_rd_launch(const cnn_conv2d_desc* d, const float* x, const float* dy, float* slabs, hipStream_t s);
-int wgrad_rd_pooled_slots(const cnn_conv2d_desc* d);
-int wgrad_rd_launch_pooled(const cnn_conv2d_desc* d, const float* x, const float* dpool, const int32_t* mask, const float* pooled,
-                           float* slabs, hipStream_t s);
-}
 
 namespace {
 
@@ -745,8 +720,6 @@ int make_wplan(const char* who, const cnn_conv2d_desc* d, WPlan* pl) {
     return CNN_AMD_OK;
 }
 
-#define CONV_TAG(d) "B%d Ci%d %dx%d Co%d k%d s%d p%d", (d)->B, (d)->Ci, (d)->H, (d)->W, (d)->Co, (d)->k, (d)->s, (d)->pad
-
 template <int MF, int MA, int NB, int WM, int WN, int WK, bool NARROW, bool PC>
 int launch_w2(const WPlan& pl, hipStream_t s, const cnn_conv2d_desc* d, int* nsplit_used) {
     auto kern = wgrad_kernel<MF, MA, NB, WM, WN, WK, NARROW, PC>;
@@ -806,15 +779,52 @@ bool rd_wanted(const cnn_conv2d_desc* d) {
     return wgrad_rd_slots(d) > 0;
 }
 
-int check_desc(const char* who, const cnn_conv2d_desc* d) {
-    CNN_REQUIRE(d != nullptr, "%s: desc is null", who);
-    CNN_REQUIRE(d->B > 0 && d->Ci > 0 && d->H > 0 && d->W > 0 && d->Co > 0 && d->k > 0 && d->s > 0 && d->pad >= 0,
-                "%s: bad desc B=%d Ci=%d H=%d W=%d Co=%d k=%d s=%d pad=%d", who, d->B, d->Ci, d->H, d->W, d->Co, d->k,
-                d->s, d->pad);
-    CNN_REQUIRE(d->H + 2 * d->pad >= d->k && d->W + 2 * d->pad >= d->k, "%s: kernel %d larger than padded input", who,
-                d->k);
-    CNN_REQUIRE((d->flags & ~CNN_CONV2D_POOL_MASK_PACKED) == 0, "%s: unknown desc flags 0x%x", who, (unsigned)d->flags);
-    return CNN_AMD_OK;
+// ---- the slab families: kernels that write `slots` partial slabs of [Co][Ci*taps | 1] floats (weight sums, then the bias sum of
+// the output channel) which reduce_slabs adds up.  cnn_conv2d_backward_weight takes the FIRST family that is wanted, covers the desc
+// and fits the workspace; behind the table comes the split-K kernel of this file.  cnn_conv2d_workspace_bytes sizes for all of them.
+struct SlabFamily {
+    int (*slots)(const cnn_conv2d_desc* d);  // 0: geometry not covered
+    int (*launch)(const cnn_conv2d_desc* d, const float* x, const float* dy, float* slabs, hipStream_t s);
+    int taps;                                // k*k of the geometries the family covers
+    bool (*wanted)(const cnn_conv2d_desc* d);  // nullptr: wherever it covers
+};
+const SlabFamily kSlabFamilies[] = {
+    /* direct */ {direct_wgrad_slots, direct_conv_wgrad, 9, [](const cnn_conv2d_desc* d) { return !rd_wanted(d); }},  // 3 -> 16: [16][27 | 1]
+    /* 1x1 */ {c11_wgrad_slots, c11_wgrad_launch, 1, nullptr},
+    // (the LDS-staged small-plane kernels first: for the reference net's stride-2 shapes they apply only when asked for, WGRAD_SP2=2)
+    /* sp */ {sp_wgrad_slots, sp_wgrad_launch, 9, nullptr},
+    /* os */ {os_wgrad_slots, os_wgrad_launch, 9, nullptr},
+    /* rd */ {wgrad_rd_slots, wgrad_rd_launch, 9, rd_wanted},
+    /* stem */ {stem_wgrad_slots, stem_wgrad_launch, 49, nullptr},
+};
+size_t slab_floats(const cnn_conv2d_desc* d, int taps) { return (size_t)d->Co * (d->Ci * taps + 1); }
+// slab rows a family's workspace holds: its slabs, then the stage-1 scratch of a reduction of more than 64 of them
+size_t slab_rows(int slots) { return (size_t)(slots + (slots + 63) / 64); }
+
+// sums `slots` slabs at the head of `ws` into gw / gb (the scratch lies behind them)
+int reduce_family(hipStream_t s, const cnn_conv2d_desc* d, float* ws, int slots, int taps, float* gw, float* gb, float divisor) {
+    const size_t n = slab_floats(d, taps);
+    char tag[160];
+    snprintf(tag, sizeof(tag), CONV_TAG(d));
+    return reduce_slabs(s, ws, slots, n, ws + (size_t)slots * n, gw, divisor, tag, d->Ci * taps, gb);
+}
+
+// the first block's slabs from the pooled domain (dpool, mask, pooled): the MFMA register-direct kernel where it is asked for
+// (CNN_AMD_WG_POOL_RD=1; a packed mask: window kernel only) and fits, else the window / packed VALU kernel.  Same slab layout.
+// with_scratch: the workspace must also hold the reduction's stage-1 scratch
+int pooled_slabs(const char* who, const cnn_conv2d_desc* d, const float* x, const float* dpool, const int32_t* mask, const float* pooled,
+                 void* ws, size_t ws_bytes, bool with_scratch, hipStream_t s, int* slots) {
+    const int ds = direct_wgrad_slots(d);
+    CNN_REQUIRE(ds > 0 && direct_conv_pool_supported(d), "%s: geometry not covered", who);
+    auto bytes = [&](int n) { return (with_scratch ? slab_rows(n) : (size_t)n) * slab_floats(d, 9) * sizeof(float); };
+    const int rs = (first_layer_rd() && !(d->flags & CNN_CONV2D_POOL_MASK_PACKED)) ? wgrad_rd_pooled_slots(d) : 0;
+    if (rs > 0 && ws != nullptr && ws_bytes >= bytes(rs)) {
+        *slots = rs;
+        return wgrad_rd_launch_pooled(d, x, dpool, mask, pooled, (float*)ws, s);
+    }
+    CNN_REQUIRE(ws != nullptr && ws_bytes >= bytes(ds), "%s: workspace too small (%zu < %zu bytes)", who, ws_bytes, bytes(ds));
+    *slots = ds;
+    return direct_conv_wgrad_pooled(d, x, dpool, mask, pooled, (float*)ws, s);
 }
 
 }  // namespace
@@ -839,28 +849,13 @@ size_t cnn_conv2d_workspace_bytes(const cnn_conv2d_desc* d) {
     size_t wg = 0;
     if (make_wplan("cnn_conv2d_workspace_bytes", d, &pl) == CNN_AMD_OK) wg = pl.part_floats + pl.bias_floats + pl.tmp_floats;
     const size_t ig = igemm_workspace_floats(d);
-    const int ds = direct_wgrad_slots(d);
-    const size_t dw = ds ? (size_t)(ds + (ds + 63) / 64) * 16 * 28 : 0;  // slabs + stage-1 scratch of the direct kernel
     size_t m = wg > ig ? wg : ig;
-    if (dw > m) m = dw;
-    const int rs = wgrad_rd_slots(d);
-    const size_t rw = rs ? (size_t)(rs + (rs + 63) / 64) * d->Co * (d->Ci * 9 + 1) : 0;
-    if (rw > m) m = rw;
-    const int rps = wgrad_rd_pooled_slots(d);
-    const size_t rpw = rps ? (size_t)(rps + (rps + 63) / 64) * d->Co * (d->Ci * 9 + 1) : 0;
-    if (rpw > m) m = rpw;
-    const int sts = stem_wgrad_slots(d);
-    const size_t stw = sts ? (size_t)(sts + (sts + 63) / 64) * d->Co * 148 : 0;
-    if (stw > m) m = stw;
-    const int oss = os_wgrad_slots(d);
-    const size_t osw = oss ? (size_t)(oss + (oss + 63) / 64) * d->Co * (d->Ci * 9 + 1) : 0;
-    if (osw > m) m = osw;
-    const int sps = sp_wgrad_slots(d);
-    const size_t spw = sps ? (size_t)(sps + (sps + 63) / 64) * d->Co * (d->Ci * 9 + 1) : 0;
-    if (spw > m) m = spw;
-    const int c1s = c11_wgrad_slots(d);
-    const size_t c1w = c1s ? (size_t)(c1s + (c1s + 63) / 64) * d->Co * (d->Ci + 1) : 0;
-    if (c1w > m) m = c1w;
+    auto slabs = [&](int slots, int taps) {  // (whether or not the family is wanted under the current options)
+        const size_t f = slots ? slab_rows(slots) * slab_floats(d, taps) : 0;
+        if (f > m) m = f;
+    };
+    for (const SlabFamily& f : kSlabFamilies) slabs(f.slots(d), f.taps);
+    slabs(wgrad_rd_pooled_slots(d), 9);
     memo.put(d, (m + 64) * sizeof(float));
     return (m + 64) * sizeof(float);
 }
@@ -872,24 +867,10 @@ int cnn_conv2d_backward_weight_pooled2(const cnn_conv2d_desc* d, const float* x,
     if (int rc = check_desc("cnn_conv2d_backward_weight_pooled2", d)) return rc;
     CNN_REQUIRE(x && dpool && mask && gw, "cnn_conv2d_backward_weight_pooled2: null pointer");
     CNN_REQUIRE(divisor != 0.f, "cnn_conv2d_backward_weight_pooled2: divisor is 0");
-    const int ds = direct_wgrad_slots(d);
-    CNN_REQUIRE(ds > 0 && direct_conv_pool_supported(d), "cnn_conv2d_backward_weight_pooled2: geometry not covered");
-    const size_t n = 16 * 28, need_d = (size_t)(ds + (ds + 63) / 64) * n * sizeof(float);
-    CNN_REQUIRE(ws != nullptr && ws_bytes >= need_d, "cnn_conv2d_backward_weight_pooled2: workspace too small (%zu < %zu bytes)", ws_bytes,
-                need_d);
     hipStream_t sd = as_stream(stream);
-    // MFMA register-direct kernel (CNN_AMD_WG_POOL_RD=0: the packed VALU kernel): same slab layout, [16][27 | 1]
-    const int rs = (first_layer_rd() && !(d->flags & CNN_CONV2D_POOL_MASK_PACKED)) ? wgrad_rd_pooled_slots(d) : 0;  // (packed mask: window kernel only)
-    if (rs > 0 && ws_bytes >= (size_t)(rs + (rs + 63) / 64) * n * sizeof(float)) {
-        if (int rc = wgrad_rd_launch_pooled(d, x, dpool, mask, pooled, (float*)ws, sd)) return rc;
-        char tagr[160];
-        snprintf(tagr, sizeof(tagr), CONV_TAG(d));
-        return reduce_slabs(sd, (const float*)ws, rs, n, (float*)ws + (size_t)rs * n, gw, divisor, tagr, 27, gb);
-    }
-    if (int rc = direct_conv_wgrad_pooled(d, x, dpool, mask, pooled, (float*)ws, sd)) return rc;
-    char tagd[160];
-    snprintf(tagd, sizeof(tagd), CONV_TAG(d));
-    return reduce_slabs(sd, (const float*)ws, ds, n, (float*)ws + (size_t)ds * n, gw, divisor, tagd, 27, gb);
+    int slots = 0;
+    if (int rc = pooled_slabs("cnn_conv2d_backward_weight_pooled2", d, x, dpool, mask, pooled, ws, ws_bytes, true, sd, &slots)) return rc;
+    return reduce_family(sd, d, (float*)ws, slots, 9, gw, gb, divisor);
 }
 
 int cnn_conv2d_backward_weight_pooled2_sgd(const cnn_conv2d_desc* d, const float* x, const float* dpool, const int32_t* mask,
@@ -907,20 +888,9 @@ int cnn_conv2d_backward_weight_pooled2_sgd_keep(const cnn_conv2d_desc* d, const 
     if (int rc = check_desc("cnn_conv2d_backward_weight_pooled2_sgd", d)) return rc;
     CNN_REQUIRE(x && dpool && mask && gw && gb && w && bias, "cnn_conv2d_backward_weight_pooled2_sgd: null pointer");
     CNN_REQUIRE(divisor != 0.f, "cnn_conv2d_backward_weight_pooled2_sgd: divisor is 0");
-    const int ds = direct_wgrad_slots(d);
-    CNN_REQUIRE(ds > 0 && direct_conv_pool_supported(d), "cnn_conv2d_backward_weight_pooled2_sgd: geometry not covered");
-    const size_t n = 16 * 28;
     hipStream_t sd = as_stream(stream);
-    int slots = ds;
-    const int rs = (first_layer_rd() && !(d->flags & CNN_CONV2D_POOL_MASK_PACKED)) ? wgrad_rd_pooled_slots(d) : 0;  // (packed mask: window kernel only)
-    if (rs > 0 && ws != nullptr && ws_bytes >= (size_t)rs * n * sizeof(float)) {
-        slots = rs;
-        if (int rc = wgrad_rd_launch_pooled(d, x, dpool, mask, pooled, (float*)ws, sd)) return rc;
-    } else {
-        CNN_REQUIRE(ws != nullptr && ws_bytes >= (size_t)ds * n * sizeof(float),
-                    "cnn_conv2d_backward_weight_pooled2_sgd: workspace too small (%zu < %zu bytes)", ws_bytes, (size_t)ds * n * sizeof(float));
-        if (int rc = direct_conv_wgrad_pooled(d, x, dpool, mask, pooled, (float*)ws, sd)) return rc;
-    }
+    int slots = 0;
+    if (int rc = pooled_slabs("cnn_conv2d_backward_weight_pooled2_sgd", d, x, dpool, mask, pooled, ws, ws_bytes, false, sd, &slots)) return rc;
     // (more than 512 slabs would go through a two-stage reduction in the unfused path: a different summation order)
     CNN_REQUIRE(slots <= 512, "cnn_conv2d_backward_weight_pooled2_sgd: %d slabs", slots);
     return direct_first_layer_finish(d, (const float*)ws, slots, divisor, gw, gb, w, bias, lr, grad_scale, fwd_prepared, dgrad_prepared,
@@ -935,69 +905,12 @@ int cnn_conv2d_backward_weight(const cnn_conv2d_desc* d, const float* x, const f
     CNN_REQUIRE(x && dy && gw, "cnn_conv2d_backward_weight: null pointer");
     CNN_REQUIRE(divisor != 0.f, "cnn_conv2d_backward_weight: divisor is 0");
     CNN_REQUIRE(ws != nullptr, "cnn_conv2d_backward_weight: workspace is null");
-    if (const int ds = rd_wanted(d) ? 0 : direct_wgrad_slots(d)) {
-        const size_t n = 16 * 28, need_d = (size_t)(ds + (ds + 63) / 64) * n * sizeof(float);
-        if (ws_bytes >= need_d) {
-            hipStream_t sd = as_stream(stream);
-            if (int rc = direct_conv_wgrad(d, x, dy, (float*)ws, sd)) return rc;
-            char tagd[160];
-            snprintf(tagd, sizeof(tagd), CONV_TAG(d));
-            float gb_dummy_unused = 0.f;
-            (void)gb_dummy_unused;
-            return reduce_slabs(sd, (const float*)ws, ds, n, (float*)ws + (size_t)ds * n, gw, divisor, tagd, 27, gb);
-        }
-    }
-    if (const int c1s = c11_wgrad_slots(d)) {
-        const size_t n = (size_t)d->Co * (d->Ci + 1), need_c = (size_t)(c1s + (c1s + 63) / 64) * n * sizeof(float);
-        if (ws_bytes >= need_c) {
-            hipStream_t sc = as_stream(stream);
-            if (int rc = c11_wgrad_launch(d, x, dy, (float*)ws, sc)) return rc;
-            char tagc[160];
-            snprintf(tagc, sizeof(tagc), CONV_TAG(d));
-            return reduce_slabs(sc, (const float*)ws, c1s, n, (float*)ws + (size_t)c1s * n, gw, divisor, tagc, d->Ci, gb);
-        }
-    }
-    // (the LDS-staged small-plane kernels first: for the reference net's stride-2 shapes they apply only when asked for, WGRAD_SP2=2)
-    if (const int sps = sp_wgrad_slots(d)) {
-        const size_t n = (size_t)d->Co * (d->Ci * 9 + 1), need_p = (size_t)(sps + (sps + 63) / 64) * n * sizeof(float);
-        if (ws_bytes >= need_p) {
-            hipStream_t sp = as_stream(stream);
-            if (int rc = sp_wgrad_launch(d, x, dy, (float*)ws, sp)) return rc;
-            char tagp[160];
-            snprintf(tagp, sizeof(tagp), CONV_TAG(d));
-            return reduce_slabs(sp, (const float*)ws, sps, n, (float*)ws + (size_t)sps * n, gw, divisor, tagp, d->Ci * 9, gb);
-        }
-    }
-    if (const int oss = os_wgrad_slots(d)) {
-        const size_t n = (size_t)d->Co * (d->Ci * 9 + 1), need_o = (size_t)(oss + (oss + 63) / 64) * n * sizeof(float);
-        if (ws_bytes >= need_o) {
-            hipStream_t so = as_stream(stream);
-            if (int rc = os_wgrad_launch(d, x, dy, (float*)ws, so)) return rc;
-            char tago[160];
-            snprintf(tago, sizeof(tago), CONV_TAG(d));
-            return reduce_slabs(so, (const float*)ws, oss, n, (float*)ws + (size_t)oss * n, gw, divisor, tago, d->Ci * 9, gb);
-        }
-    }
-    if (rd_wanted(d)) {
-        const int rs = wgrad_rd_slots(d);
-        const size_t n = (size_t)d->Co * (d->Ci * 9 + 1), need_r = (size_t)(rs + (rs + 63) / 64) * n * sizeof(float);
-        if (rs > 0 && ws_bytes >= need_r) {
-            hipStream_t sr = as_stream(stream);
-            if (int rc = wgrad_rd_launch(d, x, dy, (float*)ws, sr)) return rc;
-            char tagr[160];
-            snprintf(tagr, sizeof(tagr), CONV_TAG(d));
-            return reduce_slabs(sr, (const float*)ws, rs, n, (float*)ws + (size_t)rs * n, gw, divisor, tagr, d->Ci * 9, gb);
-        }
-    }
-    if (const int sts = stem_wgrad_slots(d)) {
-        const size_t n = (size_t)d->Co * 148, need_s = (size_t)(sts + (sts + 63) / 64) * n * sizeof(float);
-        if (ws_bytes >= need_s) {
-            hipStream_t ss = as_stream(stream);
-            if (int rc = stem_wgrad_launch(d, x, dy, (float*)ws, ss)) return rc;
-            char tags[160];
-            snprintf(tags, sizeof(tags), CONV_TAG(d));
-            return reduce_slabs(ss, (const float*)ws, sts, n, (float*)ws + (size_t)sts * n, gw, divisor, tags, 147, gb);
-        }
+    for (const SlabFamily& f : kSlabFamilies) {
+        if (f.wanted && !f.wanted(d)) continue;
+        const int slots = f.slots(d);
+        if (slots <= 0 || ws_bytes < slab_rows(slots) * slab_floats(d, f.taps) * sizeof(float)) continue;
+        if (int rc = f.launch(d, x, dy, (float*)ws, as_stream(stream))) return rc;
+        return reduce_family(as_stream(stream), d, (float*)ws, slots, f.taps, gw, gb, divisor);
     }
     WPlan pl;
     if (int rc = make_wplan("cnn_conv2d_backward_weight", d, &pl)) return rc;

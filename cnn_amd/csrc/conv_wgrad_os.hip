@@ -20,7 +20,7 @@
 // Output: slabs[blockIdx.x][Co][Ci*9 + 1] like the register-direct kernel (reduce_slabs adds them in a fixed order).
 #include <cstdlib>
 
-#include "common.h"
+#include "conv_families.h"
 
 using namespace cnn_amd;
 

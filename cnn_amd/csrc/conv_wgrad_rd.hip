@@ -32,7 +32,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
+#include "conv_families.h"
 
 using namespace cnn_amd;
 
@@ -569,8 +569,6 @@ int wgrad_rd_slots(const cnn_conv2d_desc* d) {
     RdPlan pl;
     return make_rd_plan(d, &pl) ? pl.kblocks : 0;
 }
-
-#define CONV_TAG(d) "B%d Ci%d %dx%d Co%d k%d s%d p%d", (d)->B, (d)->Ci, (d)->H, (d)->W, (d)->Co, (d)->k, (d)->s, (d)->pad
 
 int wgrad_rd_launch(const cnn_conv2d_desc* d, const float* x, const float* dy, float* slabs, hipStream_t s) {
     RdPlan pl;

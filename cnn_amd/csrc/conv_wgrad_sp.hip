@@ -29,7 +29,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
+#include "conv_families.h"
 
 using namespace cnn_amd;
 
@@ -432,13 +432,8 @@ int launch_sp(const SpPlan& pl, const cnn_conv2d_desc* d, hipStream_t s) {
 
 namespace cnn_amd {
 
-// conv_wgrad_sp2.hip: the stride-2 sibling is served through the same two entry points
-int sp2_wgrad_slots(const cnn_conv2d_desc* d);
-int sp2_wgrad_launch(const cnn_conv2d_desc* d, const float* x, const float* dy, float* slabs, hipStream_t s);
-
-// conv_wgrad_sp_any.hip: the runtime-size member of the family takes every 3x3 / stride-1 geometry the instances here do not
-int spa_wgrad_slots(const cnn_conv2d_desc* d);
-int spa_wgrad_launch(const cnn_conv2d_desc* d, const float* x, const float* dy, float* slabs, hipStream_t s);
+// conv_wgrad_sp2.hip (sp2_*): the stride-2 sibling is served through the same two entry points;
+// conv_wgrad_sp_any.hip (spa_*): the runtime-size member of the family takes every 3x3 / stride-1 geometry the instances here do not
 
 // number of partial slabs ([Co][Ci*9 + 1] floats each) the kernel writes, 0 when the geometry is not covered
 int sp_wgrad_slots(const cnn_conv2d_desc* d) {

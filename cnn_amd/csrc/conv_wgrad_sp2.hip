@@ -21,7 +21,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
+#include "conv_families.h"
 
 using namespace cnn_amd;
 

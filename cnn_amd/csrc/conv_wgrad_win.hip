@@ -25,7 +25,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
+#include "conv_families.h"
 
 using namespace cnn_amd;
 
@@ -618,8 +618,6 @@ __global__ __launch_bounds__((kWaves + (SPEC ? kProd : 0)) * 64) void conv_wgrad
 }  // namespace
 
 namespace cnn_amd {
-
-#define CONV_TAG(d) "B%d Ci%d %dx%d Co%d k%d s%d p%d", (d)->B, (d)->Ci, (d)->H, (d)->W, (d)->Co, (d)->k, (d)->s, (d)->pad
 
 namespace {
 bool make_win_params(const cnn_conv2d_desc* d, WinParams* p, int* grid) {
