@@ -17,6 +17,7 @@
 extern "C" {
 #include "cnn_amd.h"
 }
+#include "layer_parts.h"
 
 namespace architectures {
 
@@ -56,20 +57,22 @@ public:
 class BatchBuffer {
 public:
     BatchBuffer() = default;
-    ~BatchBuffer();
     BatchBuffer(const BatchBuffer&) = delete;
     BatchBuffer& operator=(const BatchBuffer&) = delete;
-    void allocate(int B, int C, int H, int W, const std::string& name);
+    void allocate(int B, int C, int H, int W, const std::string& name);  // (again: the old views are dropped, the memory only grows)
     bool empty() const { return views.empty(); }
-    data_type* base = nullptr;
+    cnn_amd_host::Workspace mem;
+    data_type* base = nullptr;  // == mem.ptr
     size_t sample_len = 0;
     std::vector<tensor> views;
 };
 
 // returns the device base pointer of a batch: zero-copy when the tensors are consecutive views of one arena,
 // otherwise uploads / gathers them into `staging` (host tensors, or views from different arenas)
-const data_type* batch_device_pointer(const std::vector<tensor>& batch, BatchBuffer& staging, const std::string& who);
-data_type* batch_device_pointer_mut(std::vector<tensor>& batch, BatchBuffer& staging, const std::string& who);
+data_type* batch_device_pointer_mut(const std::vector<tensor>& batch, BatchBuffer& staging, const std::string& who);
+inline const data_type* batch_device_pointer(const std::vector<tensor>& batch, BatchBuffer& staging, const std::string& who) {
+    return batch_device_pointer_mut(batch, staging, who);
+}
 
 class Layer {
 public:
@@ -84,7 +87,8 @@ public:
     virtual void update_gradients(const data_type learning_rate = 1e-4) {}
     virtual void save_weights(std::ofstream& writer) const {}
     virtual void load_weights(std::ifstream& reader) {}
-    // host-readable copy of the last forward's output (alexnet.cpp:97,105 contract): syncs device -> host
+    // host-readable copy of the last forward's output (alexnet.cpp:97,105 contract): syncs device -> host.  As many tensors as that
+    // pass was given (last_B), not the whole buffer's views
     virtual std::vector<tensor> get_output() const;
     // ---- additions: flat parameter arena support (one SGD kernel, one all-reduce per step) ----
     virtual size_t param_count() const { return 0; }
@@ -97,6 +101,31 @@ public:
     // addition (Sequential::set_lamb / set_lars): the tensors inside this layer's parameter block as [begin, end) offsets that tile the
     // whole block, in checkpoint order -- Conv2D / LinearLayer: weights, bias; BatchNorm2D: gamma, beta, moving_mean, moving_var.
     virtual void param_tensors(RangeList& out) const {}
+    // ---- additions: what a container tells "whoever cares" (no-ops by default) ----
+    // the parameters the last forward pass used are gone (written from outside, or stepped twice without a forward pass in between):
+    // an output that pass did not write can no longer be re-computed -- get_output() of it then fails loudly instead of returning a
+    // tensor the pass never produced (ADVICE r3)
+    virtual void params_of_last_forward_lost() {}
+    virtual void set_param_snapshot(const data_type* snap, const bool* active) {}  // see ParamBlock
+    virtual void join_pending(void* on_stream) {}   // work of this layer that still runs beside `on_stream` is ordered into it
+    virtual void invalidate_prepared() {}           // the parameters changed: copies derived from them are stale
+    // data parallelism (Sequential::set_comm): the communicator of the gradient exchange, the one for statistics over the global batch
+    virtual void set_comm(void* grads_comm, void* stats_comm, int world, int rank) {}
+
+protected:
+    typedef cnn_amd_host::Mark Mark;
+    typedef cnn_amd_host::Workspace Workspace;
+    typedef cnn_amd_host::ParamBlock ParamBlock;
+    // The shape-static contract (conv2d.cpp:47-60): the output buffer is sized by the first forward's batch; later batches may be
+    // smaller, never larger, and have the first one's sample shape.
+    struct Shape { int C, H, W; };
+    Shape in{0, 0, 0};  // sample shape of the first forward's input (0 = not known yet)
+    int batch = 0;      // ... and its batch size: the capacity of every buffer
+    int last_B = 0;     // batch size of the latest forward pass
+    // first call: allocates out_buf [B] x out and sets `output` (returns true).  Every call: B <= batch, `now` == `in` (fatal: abort() with a
+    // message naming the layer and both shapes -- a different shape would overrun device memory; otherwise an assert), last_B = B.
+    bool static_output(BatchBuffer& out_buf, int B, Shape now, Shape out, bool fatal);
+    void require_recomputable(const ParamBlock& pb, const char* what) const;  // throws when pb.lost
 };
 
 class ReLU;
@@ -111,18 +140,14 @@ private:
     bool publish_backward = false;
     MaxPool2D* pool_below = nullptr;  // the MaxPool2D whose output is this layer's input, when that pool closes a fusable
                                       // Conv2D -> ReLU -> MaxPool2D(2,2) block (fuse_pool_block): see backward()
-    bool pool_fused_pass = false;     // this pass' forward went through the pooled kernel: backward receives d(pool output)
+    Mark pool_fused_pass;             // (backward mark) this pass' forward went through the pooled kernel: backward receives d(pool output)
     void* prep_fwd = nullptr;    // prepared filters (forward / data gradient layouts)
     void* prep_dgrad = nullptr;
     void* prep_dgrad_alt = nullptr;   // second data-gradient image: a DEFERRED data gradient keeps reading the filters of its own step
     // ---- re-materialisation of an output tensor the pass did not write (fuse_pool_block) ----
     mutable bool out_valid = true;    // out_buf holds the last forward's output
-    bool recompute_lost = false;      // see params_of_last_forward_lost()
     bool delta_valid = true;          // see delta_computed()
     const data_type* last_x = nullptr;  // device pointer of the last forward's input (recorded even under no_grad)
-    int last_B = 0;
-    const data_type* snapshot = nullptr;   // the container's copy of this layer's parameters BEFORE its latest SGD step ...
-    const bool* snapshot_active = nullptr;  // ... and whether that step came after the last forward pass
     bool prepared_active = false;
     void* prep_event = nullptr;  // see wait_before_forward
     const int in_channels, out_channels, kernel_size, stride;
@@ -130,23 +155,21 @@ private:
     const int padding;  // extension: the reference has no padding (conv2d.cpp:41-42 keeps it at 0)
     std::default_random_engine seed;
     // device state: weights [Co][Ci][k][k] then bias [Co], same order as the checkpoint (conv2d.cpp:220-226)
-    data_type* params = nullptr;
-    data_type* grads = nullptr;
-    bool owns_params = true;
+    ParamBlock pb;
     bool grads_ready = false;
     BatchBuffer out_buf, delta_buf, in_stage, delta_stage;
     const data_type* saved_input = nullptr;  // device pointer of the last forward's input (the reference keeps __input)
     std::vector<tensor> saved_input_tensors;  // keeps host-uploaded inputs alive like conv2d.cpp:62
-    int in_H = 0, in_W = 0, batch = 0;
-    void* workspace = nullptr;
-    size_t workspace_bytes = 0;
+    Workspace workspace;
     void ensure_workspace(int B, int H, int W);
+    cnn_conv2d_desc backward_prelude(int B);  // what backward() and backward_weight_pooled() start with: desc, delta buffer, workspace
     // data parallelism (Sequential::set_comm): rank 0 measures the implicit-GEMM tile of this geometry, every replica pins ITS choice
     void* comm = nullptr;
     int comm_world = 1, comm_rank = 0;
     void tune_geometry(const cnn_conv2d_desc& d0);
-    data_type* w_dev() const { return params; }
-    data_type* b_dev() const { return params + (size_t)out_channels * params_for_one_kernel; }
+    data_type* w_dev() const { return pb.params; }
+    data_type* b_dev() const { return pb.params + (size_t)out_channels * params_for_one_kernel; }
+    data_type* gb_dev() const { return pb.grads + (size_t)out_channels * params_for_one_kernel; }
 
 public:
     // (the trailing _padding argument is an extension for VGG / ResNet-shaped stacks; default = the reference's 0)
@@ -160,7 +183,7 @@ public:
     void load_weights(std::ifstream& reader) override;
     int get_params_num() const;
     void set_fused_relu(ReLU* relu) { fused_relu = relu; }  // addition (see architectures::fuse_layers)
-    void set_comm(void* rccl_comm, int world, int rank) { comm = rccl_comm; comm_world = world; comm_rank = rank; }
+    void set_comm(void* grads_comm, void* stats_comm, int world, int rank) override { comm = grads_comm; comm_world = world; comm_rank = rank; }
     void set_fused_pool(MaxPool2D* pool) { fused_pool = pool; }
     void set_relu_below(ReLU* relu) { relu_below = relu; }
     void set_pool_below(MaxPool2D* pool) { pool_below = pool; }
@@ -170,11 +193,12 @@ public:
     // additions: filter re-layout hoisted out of forward / backward (cnn_conv2d_prepare_filters); the container prepares
     // all layers with one call after every parameter change and switches the layers to the *_prepared entry points
     bool shape_known() const { return batch > 0; }
-    cnn_conv2d_desc current_desc() const { return cnn_conv2d_desc{batch, in_channels, in_H, in_W, out_channels, kernel_size, stride, padding, 0}; }
-    const data_type* filters_dev() const { return params; }
+    cnn_conv2d_desc current_desc() const { return cnn_conv2d_desc{batch, in_channels, in.H, in.W, out_channels, kernel_size, stride, padding, 0}; }
+    const data_type* filters_dev() const { return pb.params; }
     const data_type* bias_dev() const { return b_dev(); }
     void prepared_buffers(void** fwd, void** dgrad);  // allocated on first use
     void set_prepared(bool on) { prepared_active = on; }
+    void invalidate_prepared() override { prepared_active = false; }
     // the prepared images of this layer (and of every later one) are written on another stream: the next forward call waits
     void wait_before_forward(void* event) { prep_event = event; }
     size_t param_count() const override { return (size_t)get_params_num(); }
@@ -191,11 +215,8 @@ public:
     // alexnet.cpp:97,105: the output of the last forward, also when that pass fused it away (see architectures::fuse_pool_block)
     std::vector<tensor> get_output() const override;
     void materialize() const;  // writes the missing output tensor(s) of the last forward pass now (no-op when present)
-    void set_param_snapshot(const data_type* snap, const bool* active) { snapshot = snap; snapshot_active = active; }
-    // the parameters the last forward pass used are gone (written from outside, or stepped twice without a forward pass in between):
-    // an output that pass did not write can no longer be re-computed -- get_output() of it then fails loudly instead of returning a
-    // tensor the pass never produced (ADVICE r3)
-    void params_of_last_forward_lost() { recompute_lost = true; }
+    void set_param_snapshot(const data_type* snap, const bool* active) override { pb.snapshot = snap; pb.snapshot_active = active; }
+    void params_of_last_forward_lost() override { pb.lost = true; }
     // The pieces of Conv2D::backward a container schedules itself for the pool-fused FIRST block of a network (nothing consumes
     // that layer's data gradient, conv2d.cpp:168-199 / alexnet.cpp:55):
     struct DeferredDgrad {   // everything the data gradient of one pass needs, valid until that pass' buffers are rewritten
@@ -207,7 +228,7 @@ public:
         int flags = 0;  // cnn_conv2d_desc.flags of the forward call that wrote the mask
         bool valid = false;
     };
-    bool pool_fused_pending() const { return pool_fused_pass; }
+    bool pool_fused_pending() const { return pool_fused_pass.armed(); }
     // will forward() of a batch of B samples run the Conv2D -> ReLU -> MaxPool2D(2,2) kernel (the pool then writes the set of
     // buffers a deferred data gradient of the previous pass does NOT read)?  Otherwise the unfused MaxPool2D::forward rewrites set 0.
     bool next_pass_pool_fused(int B) const;
@@ -238,11 +259,11 @@ private:
     int* mask_alt = nullptr;
     bool alternate = false;
     int cur_set = 0;
-    int in_C = 0, in_H = 0, in_W = 0, batch = 0;
     ReLU* fused_relu_below = nullptr;  // the ReLU layer whose output is this pool's input (set by the container), or null
     BatchNorm2D* fused_bn_below = nullptr;  // ... and the BatchNorm2D in front of THAT (BatchNorm2D -> ReLU -> this pool), or null
-    bool forward_done = false;       // this pass' output + mask were written by the producing Conv2D kernel
-    bool backward_passthrough = false;  // ... and the delta stays in the pooled domain for that Conv2D's backward
+    Mark forward_done;            // (forward mark) this pass' output + mask were written by the producer's kernel ...
+    Mark delta_to_producer;       // (forward mark, armed with forward_done) ... whose backward kernels consume the pooled-domain delta
+    Mark backward_passthrough;    // (backward mark, armed by this layer's forward() of such a pass) the delta passes through untouched
 
 public:
     MaxPool2D(std::string _name, const int _kernel_size = 2, const int _step = 2)
@@ -250,11 +271,11 @@ public:
     ~MaxPool2D() override;
     void set_fused_relu_below(ReLU* relu) { fused_relu_below = relu; }  // addition (see architectures::fuse_layers)
     void set_fused_bn_below(BatchNorm2D* bn) { fused_bn_below = bn; }   // addition: the three layers' backward passes as two kernels
-    void own_backward() { backward_passthrough = false; }  // (a fused forward whose producer is NOT a Conv2D: backward() runs here)
     bool plain_2x2() const { return kernel_size == 2 && step == 2 && padding == 0; }
     // additions used by Conv2D when the container fused Conv2D -> ReLU -> this pool into one kernel
     bool fusable_2x2() const { return kernel_size == 2 && step == 2; }
-    void fused_forward_target(int B, int C, int H, int W, bool record, data_type** pooled, int** mask_out);  // arms forward_done
+    // arms forward_done; takes_delta: backward() of this pass hands the delta through to the producer (false: it runs here)
+    void fused_forward_target(int B, int C, int H, int W, bool record, bool takes_delta, data_type** pooled, int** mask_out);
     const data_type* pooled_dev() const { return cur_set ? out_buf_alt.base : out_buf.base; }
     const int* mask_dev() const { return cur_set ? mask_alt : mask; }
     void enable_alternate_sets() { alternate = true; }
@@ -263,7 +284,8 @@ public:
     // output equals the pooled value and everywhere else the delta is 0 either way -- is carried by the mask itself: the fused
     // forward kernel sets bit 31 of a window's mask entry when its pooled value is <= 0, and the pooled-domain gradient kernels
     // then never match that window.
-    bool passthrough_armed() const { return backward_passthrough; }
+    void fused_forward_none() { forward_done.clear(); delta_to_producer.clear(); }  // the producer says that this pass' forward() runs here
+    bool passthrough_armed() const { return backward_passthrough.armed(); }
     std::vector<tensor> forward(const std::vector<tensor>& input) override;
     std::vector<tensor> backward(std::vector<tensor>& delta) override;
 };
@@ -271,8 +293,8 @@ public:
 class ReLU : public Layer {
 private:
     BatchBuffer out_buf, in_stage, delta_stage;
-    bool forward_done = false;   // this pass' output was already written by the producing Conv2D kernel
-    bool backward_done = false;  // this pass' delta was already masked by the consuming MaxPool2D kernel
+    Mark forward_done;           // (forward mark) this pass' output was already written by the producing Conv2D / BatchNorm2D kernel
+    Mark backward_done;          // (backward mark) this pass' delta was already masked by the consuming layer's kernel
     bool out_valid = true;       // false: the pool-fused pass did not write this layer's output (get_output re-computes it)
     const Conv2D* producer = nullptr;  // the convolution whose kernel writes this layer's output when fused
     const BatchNorm2D* bn_producer = nullptr;  // ... or the normalisation (BatchNorm2D -> ReLU -> MaxPool2D in one apply pass)
@@ -283,11 +305,11 @@ public:
     bool output_valid() const { return out_valid; }
     void set_producer(const Conv2D* conv) { producer = conv; }
     void set_bn_producer(const BatchNorm2D* bn) { bn_producer = bn; }
-    data_type* rematerialize_target() { out_valid = true; return out_buf.base; }
-    data_type* rematerialize_target_const() const { const_cast<ReLU*>(this)->out_valid = true; return out_buf.base; }
+    data_type* rematerialize_target() const { const_cast<ReLU*>(this)->out_valid = true; return out_buf.base; }
     // additions used by Conv2D / MaxPool2D when the container fused this layer into their kernels
     data_type* fused_forward_target(int B, int C, int H, int W);  // output arena (allocated on first use); arms forward_done
-    void fused_backward_done() { backward_done = true; }
+    void fused_forward_none() { forward_done.clear(); }        // ... or says that this pass' forward() runs here
+    void fused_backward(bool done) { backward_done.set(done); }  // the consumer's backward states whether it masked the delta
     void fused_forward_skipped(int B, int C, int H, int W);  // pool-fused pass: the output is never materialised
     std::vector<tensor> forward(const std::vector<tensor>& input) override;
     std::vector<tensor> backward(std::vector<tensor>& delta) override;
@@ -296,18 +318,15 @@ public:
 class LinearLayer : public Layer {
 private:
     const int in_channels, out_channels;
-    data_type* params = nullptr;  // W [in][out] then bias [out] (linear.cpp:105-108)
-    data_type* grads = nullptr;
-    bool owns_params = true;
+    ParamBlock pb;  // W [in][out] then bias [out] (linear.cpp:105-108)
     bool grads_ready = false;
     std::tuple<int, int, int> delta_shape;
     BatchBuffer out_buf, delta_buf, in_stage, delta_stage;
     const data_type* saved_input = nullptr;
     std::vector<tensor> saved_input_tensors;
-    int batch = 0;
     ReLU* relu_below = nullptr;  // the ReLU layer whose output is this layer's input: its backward pass is fused in
     bool publish_backward = false;
-    bool head_dx_done = false;   // this pass' data gradient was written by the loss-head kernel (forward_loss_head(with_dx))
+    Mark head_dx_done;           // (backward mark) this pass' data gradient was written by the loss-head kernel (forward_loss_head(with_dx))
     void* ev_head = nullptr;
     void* own_stream = nullptr;  // the weight / bias gradient of such a pass runs here, beside everything else ...
     void* ev_wb = nullptr;
@@ -318,7 +337,7 @@ public:
     void set_publish_backward(bool on) { publish_backward = on; }  // (see Conv2D::set_publish_backward)
     // the weight / bias gradient of a loss-head pass may still be running on the layer's own stream: `on_stream` waits for it
     // (containers call this before they read the gradient arena; update_gradients() of a stand-alone layer does it itself)
-    void join_pending(void* on_stream);
+    void join_pending(void* on_stream) override;
     // addition: forward + softmax + cross-entropy delta in ONE kernel (cnn_linear_forward_softmax_xent, out_channels <= 8):
     // labels_dev int32 [B]; delta_dev [B][out] receives p - onehot (func.cpp:56-73), loss_terms_dev [B] log p[label]
     bool loss_head_supported() const { return out_channels <= 8; }
@@ -355,18 +374,14 @@ private:
     const int out_channels;
     const data_type eps;
     const data_type momentum;
-    data_type* params = nullptr;
-    data_type* grads = nullptr;
-    bool owns_params = true;
+    ParamBlock pb;
     bool grads_ready = false;
-    bool backward_done_by_pool = false;  // this pass' backward() already ran inside the pool's (see backward_pooled)
+    Mark backward_done_by_pool;  // (backward mark) this pass' backward() already ran inside the pool's (see backward_pooled)
     data_type* saved_stats = nullptr;  // batch mean [C] then batch variance [C] (buffer_mean / buffer_var)
     BatchBuffer out_buf, in_stage, delta_stage;
     const data_type* saved_input = nullptr;
     std::vector<tensor> saved_input_tensors;
-    int in_H = 0, in_W = 0, batch = 0;
-    void* workspace = nullptr;
-    size_t workspace_bytes = 0;
+    Workspace workspace;
     void* comm = nullptr;        // RCCL communicator: statistics over the GLOBAL batch (sync-BN), see Sequential::set_comm
     int comm_world = 1;
     data_type* sync_sums = nullptr;  // [C] + [C] + [C][4] all-reduce operands
@@ -375,13 +390,9 @@ private:
     // ---- fuse_pool_block: a training pass with a fused ReLU behind this layer writes ONLY the ReLU output (round 4); get_output() of
     // this layer re-computes the normalised tensor from the recorded input, the saved batch statistics and the gamma / beta of that pass
     mutable bool out_valid = true;
-    bool recompute_lost = false;
-    int last_B = 0;
-    const data_type* snapshot = nullptr;    // the container's copy of this layer's parameters BEFORE its latest SGD step ...
-    const bool* snapshot_active = nullptr;  // ... and whether that step came after the last forward pass
 
 public:
-    void set_comm(void* rccl_comm, int world) { comm = rccl_comm; comm_world = world; }
+    void set_comm(void* grads_comm, void* stats_comm, int world, int rank) override { comm = stats_comm; comm_world = world; }
     void set_fused_relu(ReLU* relu) { fused_relu = relu; }
     void set_fused_pool(MaxPool2D* pool) { fused_pool = pool; }  // addition: BatchNorm2D -> ReLU -> MaxPool2D(2, 2) in one apply pass
     void materialize_relu() const;  // the ReLU output of a pass that wrote only the pooled tensor (ReLU::get_output)
@@ -389,10 +400,11 @@ public:
     // layer's from the pooled domain (cnn_batchnorm2d_backward_pooled: bit-identical) and arms the pass-through of backward()
     bool backward_pooled_possible(int B) const;
     void backward_pooled(const data_type* dpool, const int* mask, const data_type* pooled, data_type* dx, int B);
+    void backward_not_pooled() { backward_done_by_pool.clear(); }  // the pool's backward of this pass did not take that path
     std::vector<tensor> get_output() const override;
     void materialize() const;
-    void set_param_snapshot(const data_type* snap, const bool* active) { snapshot = snap; snapshot_active = active; }
-    void params_of_last_forward_lost() { recompute_lost = true; }
+    void set_param_snapshot(const data_type* snap, const bool* active) override { pb.snapshot = snap; pb.snapshot_active = active; }
+    void params_of_last_forward_lost() override { pb.lost = true; }
     BatchNorm2D(std::string _name, const int _out_channels, const data_type _eps = 1e-5, const data_type _momentum = 0.1);
     ~BatchNorm2D() override;
     std::vector<tensor> forward(const std::vector<tensor>& input) override;
@@ -422,7 +434,6 @@ private:
     std::default_random_engine drop;
     std::vector<int> mask;
     BatchBuffer out_buf, in_stage, delta_stage;
-    int in_C = 0, in_H = 0, in_W = 0;
 
 public:
     Dropout(std::string _name, const data_type _p = 0.5) : Layer(_name), p(_p), drop(1314) {}

@@ -24,6 +24,7 @@ static std::vector<tensor> first_n(const std::vector<tensor>& v, int B) {
 using namespace architectures;
 using cnn_amd_host::dev_alloc;
 using cnn_amd_host::must;
+using cnn_amd_host::write_back_staged;
 
 data_type architectures::random_times = 10.f;  // architectures.cpp:6
 bool architectures::no_grad = false;           // architectures.cpp:8
@@ -34,14 +35,11 @@ bool architectures::lazy_host_sync = false;
 bool architectures::input_gradient = true;
 
 // ---------------------------------------------------------------------------------------------------------------
-BatchBuffer::~BatchBuffer() {
-    views.clear();
-    if (base) cnn_device_free(base);
-}
-
 void BatchBuffer::allocate(int B, int C, int H, int W, const std::string& name) {
     sample_len = (size_t)C * H * W;
-    base = (data_type*)dev_alloc(sizeof(data_type) * sample_len * B);
+    views.clear();
+    mem.reserve(sizeof(data_type) * sample_len * B);
+    base = (data_type*)mem.ptr;
     views.reserve(B);
     for (int b = 0; b < B; ++b)
         views.emplace_back(Tensor3D::device_view(C, H, W, base + sample_len * b, name + "_" + std::to_string(b)));
@@ -58,12 +56,7 @@ bool is_contiguous_device_batch(const std::vector<tensor>& batch) {
 data_type* stage_batch(const std::vector<tensor>& batch, BatchBuffer& staging, const std::string& who) {
     const int B = (int)batch.size();
     const size_t len = (size_t)batch[0]->get_length();
-    if (staging.empty() || staging.views.size() < (size_t)B || staging.sample_len != len) {
-        staging.views.clear();
-        if (staging.base) cnn_device_free(staging.base);
-        staging.base = nullptr;
-        staging.allocate(B, batch[0]->C, batch[0]->H, batch[0]->W, who + "_staging");
-    }
+    if (staging.views.size() < (size_t)B || staging.sample_len != len) staging.allocate(B, batch[0]->C, batch[0]->H, batch[0]->W, who + "_staging");
     bool all_host = true;
     for (const auto& t : batch) all_host = all_host && !t->on_device();
     if (all_host) {
@@ -86,23 +79,45 @@ data_type* stage_batch(const std::vector<tensor>& batch, BatchBuffer& staging, c
 }
 }  // namespace
 
-const data_type* architectures::batch_device_pointer(const std::vector<tensor>& batch, BatchBuffer& staging,
-                                                     const std::string& who) {
-    assert(!batch.empty());
-    if (is_contiguous_device_batch(batch)) return batch[0]->dev;
-    return stage_batch(batch, staging, who);
-}
-
-data_type* architectures::batch_device_pointer_mut(std::vector<tensor>& batch, BatchBuffer& staging,
-                                                   const std::string& who) {
+data_type* architectures::batch_device_pointer_mut(const std::vector<tensor>& batch, BatchBuffer& staging, const std::string& who) {
     assert(!batch.empty());
     if (is_contiguous_device_batch(batch)) return batch[0]->dev;
     return stage_batch(batch, staging, who);
 }
 
 std::vector<tensor> Layer::get_output() const {
-    for (const auto& t : output) t->sync_to_host();
-    return output;
+    std::vector<tensor> out = first_n(output, last_B);
+    for (const auto& t : out) t->sync_to_host();
+    return out;
+}
+
+bool Layer::static_output(BatchBuffer& out_buf, int B, Shape now, Shape out, bool fatal) {
+    const bool first = out_buf.empty();
+    if (first) {  // conv2d.cpp:47-52: buffers are sized by the first batch
+        out_buf.allocate(B, out.C, out.H, out.W, name + "_output");
+        output = out_buf.views;
+        batch = B;
+    }
+    assert(B <= batch && "batch larger than the first forward's (conv2d.cpp:47 has the same restriction)");
+    const bool same = (!in.C || in.C == now.C) && (!in.H || in.H == now.H) && (!in.W || in.W == now.W);
+    if (fatal && !same) {
+        std::fprintf(stderr, "cnn_amd host: %s: input %dx%dx%d after a first forward with %dx%dx%d (layers are shape-static)\n", name.c_str(), now.C,
+                     now.H, now.W, in.C, in.H, in.W);
+        std::abort();
+    }
+    assert(same && "input shape changed after the first forward (layers are shape-static)");
+    in = now;
+    last_B = B;
+    return first;
+}
+
+// (an exception, not abort(): inspecting a layer after load_weights() must not kill the process.  The C wrapper
+// cnnh_net_layer_output turns it into a return code.)
+void Layer::require_recomputable(const ParamBlock& pb, const char* what) const {
+    if (pb.lost)
+        throw std::runtime_error("cnn_amd host: " + name + ": get_output() of " + what + " the last forward pass did not write, after the parameters "
+                                 "that pass used were overwritten (set from outside, or stepped twice): call forward() again, or set "
+                                 "architectures::fuse_pool_block = false");
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -112,26 +127,19 @@ Conv2D::Conv2D(std::string _name, const int _in_channels, const int _out_channel
     : Layer(_name), in_channels(_in_channels), out_channels(_out_channels), kernel_size(_kernel_size), stride(_stride),
       params_for_one_kernel(_in_channels * _kernel_size * _kernel_size), padding(_padding) {
     assert(_kernel_size >= 1 && _in_channels > 0 && _out_channels > 0 && _stride > 0 && _padding >= 0);
-    const size_t n = param_count();
-    params = (data_type*)dev_alloc(sizeof(data_type) * n);
-    grads = (data_type*)dev_alloc(sizeof(data_type) * n);
+    in.C = in_channels;
+    pb.allocate(param_count());
     // same generator, seed and draw order as conv2d.cpp:23-30 (bias first, then the filters), stored weights-then-bias
-    std::vector<data_type> host(n);
+    std::vector<data_type> host(pb.n);
     this->seed.seed(212);
     std::normal_distribution<float> engine(0.0, 1.0);
     data_type* bias = host.data() + (size_t)out_channels * params_for_one_kernel;
     for (int o = 0; o < out_channels; ++o) bias[o] = engine(this->seed) / random_times;
     for (size_t i = 0; i < (size_t)out_channels * params_for_one_kernel; ++i) host[i] = engine(this->seed) / random_times;
-    must(cnn_memcpy_h2d(params, host.data(), sizeof(data_type) * n, stream), "cnn_memcpy_h2d");
-    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
+    pb.upload(host.data());
 }
 
 Conv2D::~Conv2D() {
-    if (owns_params) {
-        cnn_device_free(params);
-        cnn_device_free(grads);
-    }
-    if (workspace) cnn_device_free(workspace);
     if (prep_fwd) cnn_device_free(prep_fwd);
     if (prep_dgrad) cnn_device_free(prep_dgrad);
     if (prep_dgrad_alt) cnn_device_free(prep_dgrad_alt);
@@ -149,15 +157,7 @@ void Conv2D::prepared_buffers(void** fwd, void** dgrad) {
 }
 
 void Conv2D::bind_arena(data_type* params_dev, data_type* grads_dev) {
-    must(cnn_memcpy_d2d(params_dev, params, sizeof(data_type) * param_count(), stream), "cnn_memcpy_d2d");
-    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
-    if (owns_params) {
-        cnn_device_free(params);
-        cnn_device_free(grads);
-    }
-    params = params_dev;
-    grads = grads_dev;
-    owns_params = false;
+    pb.adopt(params_dev, grads_dev, /*zero_grads=*/false);
     prepared_active = false;
 }
 
@@ -165,11 +165,7 @@ void Conv2D::ensure_workspace(int B, int H, int W) {
     cnn_conv2d_desc d{B, in_channels, H, W, out_channels, kernel_size, stride, padding, 0};
     const size_t need = cnn_conv2d_workspace_bytes(&d);
     if (need == 0) must(1, "cnn_conv2d_workspace_bytes");
-    if (need > workspace_bytes) {
-        if (workspace) cnn_device_free(workspace);
-        workspace = dev_alloc(need);
-        workspace_bytes = need;
-    }
+    workspace.reserve(need);
 }
 
 // cnn_conv2d_autotune for a geometry this layer sees for the first time -- with the CALLER's scratch (include/cnn_amd.h: "no allocation
@@ -212,25 +208,14 @@ std::vector<tensor> Conv2D::forward(const std::vector<tensor>& input) {
     const int H = input[0]->H, W = input[0]->W;
     const int out_H = cnn_conv2d_out_dim(H, kernel_size, stride, padding);
     const int out_W = cnn_conv2d_out_dim(W, kernel_size, stride, padding);
-    if (out_buf.empty()) {  // shape-static like conv2d.cpp:47-52: buffers are sized by the first batch
-        out_buf.allocate(B, out_channels, out_H, out_W, name + "_output");
-        output = out_buf.views;
-        batch = B;
+    // shape-static like the reference (conv2d.cpp:47-60 caches its offsets on the first call): the buffers and the prepared
+    // filters were sized for the first input shape -- a different one would overrun DEVICE memory, so it is fatal here
+    if (static_output(out_buf, B, Shape{input[0]->C, H, W}, Shape{out_channels, out_H, out_W}, /*fatal=*/true)) {
         // the shape is known now: let the library measure which tile its implicit-GEMM kernels should use for it (once per
         // geometry and process, before any filter preparation)
         cnn_conv2d_desc d0{B, in_channels, H, W, out_channels, kernel_size, stride, padding, 0};
         tune_geometry(d0);
     }
-    assert(B <= batch && "batch larger than the first forward's (conv2d.cpp:47 has the same restriction)");
-    // shape-static like the reference (conv2d.cpp:47-60 caches its offsets on the first call): the buffers and the prepared
-    // filters were sized for the first input shape -- a different one would overrun DEVICE memory, so it is fatal here
-    if ((in_H && in_H != H) || (in_W && in_W != W) || input[0]->C != in_channels) {
-        std::fprintf(stderr, "cnn_amd host: %s: input %dx%dx%d after a first forward with %dx%dx%d (layers are shape-static)\n", name.c_str(),
-                     input[0]->C, H, W, in_channels, in_H, in_W);
-        std::abort();
-    }
-    in_H = H;
-    in_W = W;
     ensure_workspace(B, H, W);
     if (prep_event != nullptr) {  // this layer's filter images come from the side stream (Sequential::prepare_filters)
         must(cnn_stream_wait_event(stream, prep_event), "cnn_stream_wait_event");
@@ -242,12 +227,14 @@ std::vector<tensor> Conv2D::forward(const std::vector<tensor>& input) {
         saved_input_tensors = input;
     }
     last_x = x;  // (a pointer, not a copy: get_output() of a fused-away tensor re-computes it from here)
-    last_B = B;
     out_valid = true;
-    recompute_lost = false;
+    pb.lost = false;
     cnn_conv2d_desc d{B, in_channels, H, W, out_channels, kernel_size, stride, padding, 0};
     const bool prepared = prepared_active && fuse_layers && B == batch;
-    pool_fused_pass = false;
+    pool_fused_pass.clear();                               // (mark rule 2)
+    // (mark rule 3: armed again below where this pass writes their outputs)
+    if (fused_relu != nullptr) fused_relu->fused_forward_none();
+    if (fused_pool != nullptr) fused_pool->fused_forward_none();
     if (prepared && fuse_pool_block && fused_relu != nullptr && fused_pool != nullptr && fused_pool->fusable_2x2() &&
         cnn_conv2d_relu_maxpool2_supported(&d)) {
         // Conv2D -> ReLU -> MaxPool2D(2,2) in one kernel: only the pool's output and mask are written; this layer's and the
@@ -256,10 +243,10 @@ std::vector<tensor> Conv2D::forward(const std::vector<tensor>& input) {
         int* pmask = nullptr;
         d.flags = cnn_conv2d_pool_mask_packed_supported(&d) ? CNN_CONV2D_POOL_MASK_PACKED : 0;  // (the mask buffer fits either form)
         pool_mask_flags = d.flags;
-        fused_pool->fused_forward_target(B, out_channels, out_H, out_W, !no_grad, &pooled, &pmask);
+        fused_pool->fused_forward_target(B, out_channels, out_H, out_W, !no_grad, /*takes_delta=*/!no_grad, &pooled, &pmask);
         fused_relu->fused_forward_skipped(B, out_channels, out_H, out_W);
         must(cnn_conv2d_relu_maxpool2_forward_prepared(&d, x, prep_fwd, pooled, pmask, stream), "cnn_conv2d_relu_maxpool2_forward_prepared");
-        pool_fused_pass = !no_grad;
+        pool_fused_pass.set(!no_grad);
         out_valid = false;  // (re-computed by get_output() if anybody asks)
         return output;
     }
@@ -273,12 +260,12 @@ std::vector<tensor> Conv2D::forward(const std::vector<tensor>& input) {
             must(cnn_conv2d_forward_prepared(&d, x, prep_fwd, b_dev(), relu_only ? nullptr : out_buf.base, y_relu, stream),
                  "cnn_conv2d_forward_prepared");
         else
-            must(cnn_conv2d_forward_relu(&d, x, w_dev(), b_dev(), out_buf.base, y_relu, workspace, workspace_bytes, stream),
+            must(cnn_conv2d_forward_relu(&d, x, w_dev(), b_dev(), out_buf.base, y_relu, workspace.ptr, workspace.bytes, stream),
                  "cnn_conv2d_forward_relu");
     } else if (prepared) {
         must(cnn_conv2d_forward_prepared(&d, x, prep_fwd, b_dev(), out_buf.base, nullptr, stream), "cnn_conv2d_forward_prepared");
     } else {
-        must(cnn_conv2d_forward(&d, x, w_dev(), b_dev(), out_buf.base, workspace, workspace_bytes, stream), "cnn_conv2d_forward");
+        must(cnn_conv2d_forward(&d, x, w_dev(), b_dev(), out_buf.base, workspace.ptr, workspace.bytes, stream), "cnn_conv2d_forward");
     }
     return first_n(output, B);
 }
@@ -287,38 +274,37 @@ bool Conv2D::next_pass_pool_fused(int B) const {
     if (!(prepared_active && fuse_layers && B == batch && fuse_pool_block && fused_relu != nullptr && fused_pool != nullptr &&
           fused_pool->fusable_2x2()))
         return false;
-    cnn_conv2d_desc d{B, in_channels, in_H, in_W, out_channels, kernel_size, stride, padding, 0};
+    cnn_conv2d_desc d{B, in_channels, in.H, in.W, out_channels, kernel_size, stride, padding, 0};
     return cnn_conv2d_relu_maxpool2_supported(&d) != 0;
+}
+
+cnn_conv2d_desc Conv2D::backward_prelude(int B) {
+    assert(saved_input != nullptr && "backward without a recorded forward (no_grad?)");
+    cnn_conv2d_desc d{B, in_channels, in.H, in.W, out_channels, kernel_size, stride, padding, 0};
+    if (delta_buf.empty()) delta_buf.allocate(batch, in_channels, in.H, in.W, name + "_delta");
+    workspace.reserve(cnn_conv2d_backward_workspace_bytes(&d));
+    return d;
 }
 
 std::vector<tensor> Conv2D::backward(std::vector<tensor>& delta) {
     Tensor3D::device_work_enqueued();  // host copies of device views made before this call are stale from here on
     const int B = (int)delta.size();
-    assert(saved_input != nullptr && "backward without a recorded forward (no_grad?)");
+    cnn_conv2d_desc d = backward_prelude(B);
     const data_type* dy = batch_device_pointer(delta, delta_stage, name + "_dy");
-    cnn_conv2d_desc d{B, in_channels, in_H, in_W, out_channels, kernel_size, stride, padding, 0};
     // conv2d.cpp:117-199: weight/bias gradients (recomputed, not accumulated, averaged over the batch) and the data
     // gradient in one call; the library overlaps the two on an internal side stream
-    if (delta_buf.empty()) delta_buf.allocate(batch, in_channels, in_H, in_W, name + "_delta");
     BatchBuffer& dbuf = delta_buf;
-    const size_t need = cnn_conv2d_backward_workspace_bytes(&d);
-    if (need > workspace_bytes) {
-        if (workspace) cnn_device_free(workspace);
-        workspace = dev_alloc(need);
-        workspace_bytes = need;
-    }
-    if (pool_fused_pass) {
+    if (relu_below != nullptr) relu_below->fused_backward(false);  // (mark rule 3: armed below where the data gradient masks for it)
+    if (pool_fused_pass.take()) {
         // dy is the delta of the POOL output (the pool and the ReLU passed it through untouched)
         assert(prepared_active && fused_pool != nullptr && B == batch);
         // (pooled = NULL: the fused forward kernel marked the windows whose pooled value is <= 0 in the mask itself -- bit 31 --, so
         // the block's ReLU::backward needs no tensor of its own here)
         const data_type* pooled = nullptr;
         d.flags = pool_mask_flags;
-        must(cnn_conv2d_backward_pooled2_prepared(&d, saved_input, dy, fused_pool->mask_dev(), pooled, prep_dgrad, grads,
-                                                  grads + (size_t)out_channels * params_for_one_kernel, dbuf.base, (float)B,
-                                                  workspace, workspace_bytes, stream, /*defer_join=*/1),
+        must(cnn_conv2d_backward_pooled2_prepared(&d, saved_input, dy, fused_pool->mask_dev(), pooled, prep_dgrad, pb.grads, gb_dev(), dbuf.base,
+                                                  (float)B, workspace.ptr, workspace.bytes, stream, /*defer_join=*/1),
              "cnn_conv2d_backward_pooled2_prepared");
-        pool_fused_pass = false;
     } else if (prepared_active && fuse_layers && B == batch) {
         // relu_below: this layer's input IS that ReLU's output, so its backward mask is applied in the data-gradient epilogue.
         // pool_below in a pool-fused pass: this layer's input is the POOL output and its delta stays in the pooled domain,
@@ -327,14 +313,13 @@ std::vector<tensor> Conv2D::backward(std::vector<tensor>& delta) {
         const bool pooled_pass = relu_below == nullptr && pool_below != nullptr && pool_below->passthrough_armed();
         const data_type* rb = relu_below != nullptr ? saved_input : nullptr;
         if (publish_backward && (rb != nullptr || pooled_pass)) must(cnn_amd_publish_next_kernel(stream), "cnn_amd_publish_next_kernel");
-        must(cnn_conv2d_backward_prepared_relu(&d, saved_input, dy, prep_dgrad, rb, grads,
-                                               grads + (size_t)out_channels * params_for_one_kernel, dbuf.base, (float)B,
-                                               workspace, workspace_bytes, stream, /*defer_join=*/1),
+        must(cnn_conv2d_backward_prepared_relu(&d, saved_input, dy, prep_dgrad, rb, pb.grads, gb_dev(), dbuf.base, (float)B, workspace.ptr,
+                                               workspace.bytes, stream, /*defer_join=*/1),
              "cnn_conv2d_backward_prepared_relu");
-        if (rb && relu_below) relu_below->fused_backward_done();
+        if (relu_below != nullptr) relu_below->fused_backward(true);
     } else
-        must(cnn_conv2d_backward(&d, saved_input, dy, w_dev(), grads, grads + (size_t)out_channels * params_for_one_kernel,
-                                 dbuf.base, (float)B, workspace, workspace_bytes, stream, /*defer_join=*/1),
+        must(cnn_conv2d_backward(&d, saved_input, dy, w_dev(), pb.grads, gb_dev(), dbuf.base, (float)B, workspace.ptr, workspace.bytes, stream,
+                                 /*defer_join=*/1),
              "cnn_conv2d_backward");  // joined in update_gradients / AlexNet::backward
     grads_ready = true;
     delta_valid = true;
@@ -346,25 +331,18 @@ void Conv2D::materialize() const {
     const bool relu_missing = fused_relu != nullptr && !fused_relu->output_valid();
     if (out_valid && !relu_missing) return;
     assert(last_x != nullptr && "get_output() of a fused-away tensor before any forward pass");
-    if (recompute_lost) {
-        // (an exception, not abort(): inspecting a layer after load_weights() must not kill the process.  The C wrapper
-        // cnnh_net_layer_output turns it into a return code.)
-        throw std::runtime_error("cnn_amd host: " + name + ": get_output() of a tensor the last forward pass did not write, after the parameters that pass "
-                                 "used were overwritten (set from outside, or stepped twice): call forward() again, or set "
-                                 "architectures::fuse_pool_block = false");
-    }
-    // the parameters the last forward pass used: the container's snapshot when its SGD step has run since
-    const data_type* w = (snapshot != nullptr && snapshot_active != nullptr && *snapshot_active) ? snapshot : params;
+    require_recomputable(pb, "a tensor");
+    const data_type* w = pb.of_last_forward();
     const data_type* b = w + (size_t)out_channels * params_for_one_kernel;
     Conv2D* self = const_cast<Conv2D*>(this);
-    self->ensure_workspace(last_B, in_H, in_W);
-    cnn_conv2d_desc d{last_B, in_channels, in_H, in_W, out_channels, kernel_size, stride, padding, 0};
+    self->ensure_workspace(last_B, in.H, in.W);
+    cnn_conv2d_desc d{last_B, in_channels, in.H, in.W, out_channels, kernel_size, stride, padding, 0};
     // the unprepared entry points re-arrange the filters themselves: bit-identical to the prepared kernels the pass would have run
     if (fused_relu != nullptr && fuse_layers)
-        must(cnn_conv2d_forward_relu(&d, last_x, w, b, out_buf.base, fused_relu->rematerialize_target(), workspace, workspace_bytes, stream),
+        must(cnn_conv2d_forward_relu(&d, last_x, w, b, out_buf.base, fused_relu->rematerialize_target(), workspace.ptr, workspace.bytes, stream),
              "cnn_conv2d_forward_relu");
     else
-        must(cnn_conv2d_forward(&d, last_x, w, b, out_buf.base, workspace, workspace_bytes, stream), "cnn_conv2d_forward");
+        must(cnn_conv2d_forward(&d, last_x, w, b, out_buf.base, workspace.ptr, workspace.bytes, stream), "cnn_conv2d_forward");
     out_valid = true;
 }
 
@@ -376,20 +354,15 @@ std::vector<tensor> Conv2D::get_output() const {
 Conv2D::DeferredDgrad Conv2D::backward_weight_pooled(std::vector<tensor>& delta, bool fused_sgd, data_type learning_rate, data_type grad_scale) {
     Tensor3D::device_work_enqueued();
     const int B = (int)delta.size();
-    assert(pool_fused_pass && prepared_active && fused_pool != nullptr && B == batch && saved_input != nullptr);
+    const bool armed = pool_fused_pass.take();  // (a piece of backward(): it consumes the mark like backward() does)
+    assert(armed && prepared_active && fused_pool != nullptr && B == batch);
+    (void)armed;
+    cnn_conv2d_desc d = backward_prelude(B);
     const data_type* dy = batch_device_pointer(delta, delta_stage, name + "_dy");  // d(pool output)
-    cnn_conv2d_desc d{B, in_channels, in_H, in_W, out_channels, kernel_size, stride, padding, 0};
-    if (delta_buf.empty()) delta_buf.allocate(batch, in_channels, in_H, in_W, name + "_delta");
-    const size_t need = cnn_conv2d_backward_workspace_bytes(&d);
-    if (need > workspace_bytes) {
-        if (workspace) cnn_device_free(workspace);
-        workspace = dev_alloc(need);
-        workspace_bytes = need;
-    }
     if (prep_dgrad_alt == nullptr) prep_dgrad_alt = dev_alloc(cnn_conv2d_prepared_bytes(&d));
     const data_type* pooled = nullptr;  // (the ReLU mask rides in bit 31 of the pool mask, see Conv2D::backward)
-    data_type* gw = grads;
-    data_type* gb = grads + (size_t)out_channels * params_for_one_kernel;
+    data_type* gw = pb.grads;
+    data_type* gb = gb_dev();
     DeferredDgrad job;
     job.prepared = prep_dgrad;  // the filters of THIS step
     job.dpool = dy;
@@ -402,18 +375,17 @@ Conv2D::DeferredDgrad Conv2D::backward_weight_pooled(std::vector<tensor>& delta,
     if (fused_sgd) {
         // window kernel + ONE small launch: slab reduction, gw / gb, this layer's SGD step (old values -> snapshot) and the filter
         // images of the updated filters: forward in place, data gradient into the OTHER buffer (job.prepared stays intact)
-        data_type* snap_w = const_cast<data_type*>(snapshot);
+        data_type* snap_w = const_cast<data_type*>(pb.snapshot);
         must(cnn_conv2d_backward_weight_pooled2_sgd_keep(&d, saved_input, dy, job.mask, pooled, gw, gb, (float)B, w_dev(), b_dev(), learning_rate,
                                                          grad_scale, prep_fwd, prep_dgrad_alt, snap_w,
-                                                         snap_w ? snap_w + (size_t)out_channels * params_for_one_kernel : nullptr, workspace,
-                                                         workspace_bytes, stream),
+                                                         snap_w ? snap_w + (size_t)out_channels * params_for_one_kernel : nullptr, workspace.ptr,
+                                                         workspace.bytes, stream),
              "cnn_conv2d_backward_weight_pooled2_sgd_keep");
         std::swap(prep_dgrad, prep_dgrad_alt);
     } else {
-        must(cnn_conv2d_backward_weight_pooled2(&d, saved_input, dy, job.mask, pooled, gw, gb, (float)B, workspace, workspace_bytes, stream),
+        must(cnn_conv2d_backward_weight_pooled2(&d, saved_input, dy, job.mask, pooled, gw, gb, (float)B, workspace.ptr, workspace.bytes, stream),
              "cnn_conv2d_backward_weight_pooled2");
     }
-    pool_fused_pass = false;
     grads_ready = true;
     return job;
 }
@@ -433,7 +405,7 @@ void Conv2D::prepare_own_filters() {
 void Conv2D::launch_deferred_dgrad(const DeferredDgrad& job, void* on_stream) {
     assert(job.valid);
     delta_valid = true;
-    cnn_conv2d_desc d{job.B, in_channels, in_H, in_W, out_channels, kernel_size, stride, padding, job.flags};
+    cnn_conv2d_desc d{job.B, in_channels, in.H, in.W, out_channels, kernel_size, stride, padding, job.flags};
     must(cnn_conv2d_backward_data_pooled2_prepared(&d, job.dpool, job.mask, job.pooled, job.prepared, delta_buf.base, on_stream),
          "cnn_conv2d_backward_data_pooled2_prepared");
 }
@@ -441,24 +413,16 @@ void Conv2D::launch_deferred_dgrad(const DeferredDgrad& job, void* on_stream) {
 void Conv2D::update_gradients(const data_type learning_rate) {
     assert(grads_ready);  // conv2d.cpp:206
     must(cnn_amd_side_stream_join(stream), "cnn_amd_side_stream_join");
-    must(cnn_sgd_update(params, grads, param_count(), learning_rate, 1.f, stream), "cnn_sgd_update");
+    must(cnn_sgd_update(pb.params, pb.grads, param_count(), learning_rate, 1.f, stream), "cnn_sgd_update");
     prepared_active = false;
 }
 
 // checkpoint layout conv2d.cpp:220-226: Co filters then Co biases == the device layout, one contiguous block
-void Conv2D::save_weights(std::ofstream& writer) const {
-    std::vector<data_type> host(param_count());
-    must(cnn_memcpy_d2h(host.data(), params, sizeof(data_type) * host.size(), stream), "cnn_memcpy_d2h");
-    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
-    writer.write(reinterpret_cast<const char*>(host.data()), static_cast<std::streamsize>(sizeof(data_type) * host.size()));
-}
+void Conv2D::save_weights(std::ofstream& writer) const { pb.save(writer); }
 
 void Conv2D::load_weights(std::ifstream& reader) {
     prepared_active = false;
-    std::vector<data_type> host(param_count());
-    reader.read(reinterpret_cast<char*>(host.data()), static_cast<std::streamsize>(sizeof(data_type) * host.size()));
-    must(cnn_memcpy_h2d(params, host.data(), sizeof(data_type) * host.size(), stream), "cnn_memcpy_h2d");
-    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
+    pb.load(reader);
 }
 
 int Conv2D::get_params_num() const { return (params_for_one_kernel + 1) * out_channels; }
@@ -470,15 +434,9 @@ MaxPool2D::~MaxPool2D() {
     if (mask_alt) cnn_device_free(mask_alt);
 }
 
-void MaxPool2D::fused_forward_target(int B, int C, int H, int W, bool record, data_type** pooled, int** mask_out) {
+void MaxPool2D::fused_forward_target(int B, int C, int H, int W, bool record, bool takes_delta, data_type** pooled, int** mask_out) {
     const int out_H = cnn_maxpool2d_out_dim(H, kernel_size, step), out_W = cnn_maxpool2d_out_dim(W, kernel_size, step);
-    if (out_buf.empty()) {
-        out_buf.allocate(B, C, out_H, out_W, name + "_output");
-        output = out_buf.views;
-        batch = B;
-    }
-    assert(B <= batch);
-    in_C = C; in_H = H; in_W = W;
+    static_output(out_buf, B, Shape{C, H, W}, Shape{C, out_H, out_W}, /*fatal=*/false);
     // (sized for the int32 form; the packed one-byte form of the fused block needs at most (out_W + 3) bytes per row + 64)
     if (record && mask == nullptr) mask = (int*)dev_alloc(sizeof(int) * (size_t)batch * C * out_H * out_W + 64);
     if (alternate) {  // the deferred data gradient of the previous pass still reads the other set
@@ -489,35 +447,25 @@ void MaxPool2D::fused_forward_target(int B, int C, int H, int W, bool record, da
     }
     *pooled = cur_set ? out_buf_alt.base : out_buf.base;
     *mask_out = record ? (cur_set ? mask_alt : mask) : nullptr;
-    forward_done = true;
-    backward_passthrough = record;
+    forward_done.arm();
+    delta_to_producer.set(takes_delta);
 }
 
 std::vector<tensor> MaxPool2D::forward(const std::vector<tensor>& input) {
     Tensor3D::device_work_enqueued();  // host copies of device views made before this call are stale from here on
-    if (forward_done) {  // written by the producing convolution's / BatchNorm2D's kernel in this pass
-        forward_done = false;
-        return first_n(output, (int)input.size());
-    }
-    backward_passthrough = false;
+    const bool fused = forward_done.take();  // written by the producing convolution's / BatchNorm2D's kernel in this pass
+    const bool hand_through = delta_to_producer.take();
+    backward_passthrough.set(fused && hand_through);  // (mark rule 2: this pass' value, whatever an earlier pass left)
+    if (fused) return first_n(output, (int)input.size());
     const int B = (int)input.size();
     const int C = input[0]->C, H = input[0]->H, W = input[0]->W;
     const int out_H = cnn_maxpool2d_out_dim(H, kernel_size, step), out_W = cnn_maxpool2d_out_dim(W, kernel_size, step);
-    if (out_buf.empty()) {
-        out_buf.allocate(B, C, out_H, out_W, name + "_output");
-        output = out_buf.views;
-        batch = B;
-    }
+    // (the output / mask buffers were sized by the first shape)
+    static_output(out_buf, B, Shape{C, H, W}, Shape{C, out_H, out_W}, /*fatal=*/true);
     if (cur_set != 0) {  // (an unfused pass always uses the first set)
         cur_set = 0;
         output = out_buf.views;
     }
-    assert(B <= batch);
-    if (in_C && (in_C != C || in_H != H || in_W != W)) {  // (the output / mask buffers were sized by the first shape)
-        std::fprintf(stderr, "cnn_amd host: %s: input shape changed after the first forward (layers are shape-static)\n", name.c_str());
-        std::abort();
-    }
-    in_C = C; in_H = H; in_W = W;
     if (!no_grad && mask == nullptr)  // pool2d.cpp:23-31 (allocated lazily so a no_grad first call is not fatal)
         mask = (int*)dev_alloc(sizeof(int) * (size_t)batch * C * out_H * out_W + 64);
     const data_type* x = batch_device_pointer(input, in_stage, name);
@@ -528,29 +476,31 @@ std::vector<tensor> MaxPool2D::forward(const std::vector<tensor>& input) {
 
 std::vector<tensor> MaxPool2D::backward(std::vector<tensor>& delta) {
     Tensor3D::device_work_enqueued();  // host copies of device views made before this call are stale from here on
-    if (backward_passthrough) {  // the producing Conv2D's backward kernels consume the pooled-domain delta directly
-        backward_passthrough = false;
-        if (fused_relu_below != nullptr) fused_relu_below->fused_backward_done();
+    // (mark rule 3: what this call does for the two layers in front is stated anew on every call)
+    if (fused_bn_below != nullptr) fused_bn_below->backward_not_pooled();
+    if (fused_relu_below != nullptr) fused_relu_below->fused_backward(false);
+    if (backward_passthrough.take()) {  // the producing Conv2D's backward kernels consume the pooled-domain delta directly
+        if (fused_relu_below != nullptr) fused_relu_below->fused_backward(true);
         return delta;
     }
     const int B = (int)delta.size();
     assert(mask != nullptr && "backward without a recorded forward (no_grad?)");
-    if (delta_buf.empty()) delta_buf.allocate(batch, in_C, in_H, in_W, name + "_delta");
+    if (delta_buf.empty()) delta_buf.allocate(batch, in.C, in.H, in.W, name + "_delta");
     const data_type* dy = batch_device_pointer(delta, delta_stage, name + "_dy");
     if (fused_bn_below != nullptr && fused_relu_below != nullptr && fuse_layers && fusable_2x2() && padding == 0 &&
         fused_bn_below->backward_pooled_possible(B)) {
         // BatchNorm2D -> ReLU -> this pool: the three backward passes as two kernels that rebuild the delta between them from the pooled
         // domain (bit-identical to the sequence; neither this layer's nor the ReLU's input gradient is materialised)
         fused_bn_below->backward_pooled(dy, mask_dev(), pooled_dev(), delta_buf.base, B);
-        fused_relu_below->fused_backward_done();
+        fused_relu_below->fused_backward(true);
         return first_n(delta_buf.views, B);
     }
     if (fused_relu_below != nullptr && fuse_layers) {  // also applies the ReLU::backward of the layer in front
-        must(cnn_maxpool2d_backward_relu(dy, mask_dev(), pooled_dev(), delta_buf.base, B, in_C, in_H, in_W, kernel_size, step, stream),
+        must(cnn_maxpool2d_backward_relu(dy, mask_dev(), pooled_dev(), delta_buf.base, B, in.C, in.H, in.W, kernel_size, step, stream),
              "cnn_maxpool2d_backward_relu");
-        fused_relu_below->fused_backward_done();
+        fused_relu_below->fused_backward(true);
     } else {
-        must(cnn_maxpool2d_backward(dy, mask_dev(), delta_buf.base, B, in_C, in_H, in_W, kernel_size, step, stream),
+        must(cnn_maxpool2d_backward(dy, mask_dev(), delta_buf.base, B, in.C, in.H, in.W, kernel_size, step, stream),
              "cnn_maxpool2d_backward");
     }
     return first_n(delta_buf.views, B);
@@ -559,12 +509,8 @@ std::vector<tensor> MaxPool2D::backward(std::vector<tensor>& delta) {
 // ---------------------------------------------------------------------------------------------------------------
 // ReLU
 data_type* ReLU::fused_forward_target(int B, int C, int H, int W) {
-    if (out_buf.empty()) {
-        out_buf.allocate(B, C, H, W, name + "_output");
-        output = out_buf.views;
-    }
-    assert((size_t)B <= out_buf.views.size() && out_buf.sample_len == (size_t)C * H * W);
-    forward_done = true;
+    static_output(out_buf, B, Shape{C, H, W}, Shape{C, H, W}, /*fatal=*/false);
+    forward_done.arm();
     out_valid = true;
     return out_buf.base;
 }
@@ -584,19 +530,9 @@ std::vector<tensor> ReLU::get_output() const {
 std::vector<tensor> ReLU::forward(const std::vector<tensor>& input) {
     Tensor3D::device_work_enqueued();  // host copies of device views made before this call are stale from here on
     const int B = (int)input.size();
-    if (forward_done) {  // written by the producing convolution's kernel in this pass
-        forward_done = false;
-        return first_n(output, B);
-    }
-    if (out_buf.empty()) {
-        out_buf.allocate(B, input[0]->C, input[0]->H, input[0]->W, name + "_output");
-        output = out_buf.views;
-    }
-    assert((size_t)B <= out_buf.views.size());
-    if (out_buf.sample_len != (size_t)input[0]->get_length()) {
-        std::fprintf(stderr, "cnn_amd host: %s: input shape changed after the first forward (layers are shape-static)\n", name.c_str());
-        std::abort();
-    }
+    backward_done.clear();  // (mark rule 2)
+    if (forward_done.take()) return first_n(output, B);  // written by the producing convolution's / BatchNorm2D's kernel in this pass
+    static_output(out_buf, B, Shape{input[0]->C, input[0]->H, input[0]->W}, Shape{input[0]->C, input[0]->H, input[0]->W}, /*fatal=*/true);
     const data_type* x = batch_device_pointer(input, in_stage, name);
     out_valid = true;
     must(cnn_relu_forward(x, out_buf.base, out_buf.sample_len * B, stream), "cnn_relu_forward");
@@ -607,24 +543,11 @@ std::vector<tensor> ReLU::forward(const std::vector<tensor>& input) {
 std::vector<tensor> ReLU::backward(std::vector<tensor>& delta) {
     Tensor3D::device_work_enqueued();  // host copies of device views made before this call are stale from here on
     const int B = (int)delta.size();
-    if (backward_done) {  // masked by the pool's backward kernel in this pass
-        backward_done = false;
-        for (int b = 0; b < B; ++b) delta[b]->name = name + "_delta_" + std::to_string(b);
-        return delta;
-    }
-    const bool in_place = delta[0]->on_device();
-    data_type* d = batch_device_pointer_mut(delta, delta_stage, name + "_dy");
-    must(cnn_relu_backward(out_buf.base, d, out_buf.sample_len * B, stream), "cnn_relu_backward");
-    if (!in_place || d == delta_stage.base) {  // host (or scattered) deltas were staged: write the result back
-        for (int b = 0; b < B; ++b) {
-            if (delta[b]->on_device())
-                must(cnn_memcpy_d2d(delta[b]->dev, d + out_buf.sample_len * b, sizeof(data_type) * out_buf.sample_len, stream),
-                     "cnn_memcpy_d2d");
-            else
-                must(cnn_memcpy_d2h(delta[b]->data, d + out_buf.sample_len * b, sizeof(data_type) * out_buf.sample_len, stream),
-                     "cnn_memcpy_d2h");
-        }
-        must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
+    if (!backward_done.take()) {  // (taken: masked by the consuming layer's backward kernel in this pass)
+        const bool in_place = delta[0]->on_device();
+        data_type* d = batch_device_pointer_mut(delta, delta_stage, name + "_dy");
+        must(cnn_relu_backward(out_buf.base, d, out_buf.sample_len * B, stream), "cnn_relu_backward");
+        write_back_staged(delta, d, out_buf.sample_len, B, !in_place || d == delta_stage.base);
     }
     for (int b = 0; b < B; ++b) delta[b]->name = name + "_delta_" + std::to_string(b);
     return delta;
@@ -635,39 +558,22 @@ std::vector<tensor> ReLU::backward(std::vector<tensor>& delta) {
 BatchNorm2D::BatchNorm2D(std::string _name, const int _out_channels, const data_type _eps, const data_type _momentum)
     : Layer(_name), out_channels(_out_channels), eps(_eps), momentum(_momentum) {
     assert(_out_channels > 0);
-    const size_t n = param_count();
-    params = (data_type*)dev_alloc(sizeof(data_type) * n);
-    grads = (data_type*)dev_alloc(sizeof(data_type) * n);
+    pb.allocate(param_count());
     saved_stats = (data_type*)dev_alloc(sizeof(data_type) * 2 * out_channels);
-    std::vector<data_type> host(n, 0);  // batchnorm2d.cpp:18-20: gamma = 1, beta = 0, moving_mean = moving_var = 0
+    std::vector<data_type> host(pb.n, 0);  // batchnorm2d.cpp:18-20: gamma = 1, beta = 0, moving_mean = moving_var = 0
     for (int o = 0; o < out_channels; ++o) host[o] = 1;
-    must(cnn_memcpy_h2d(params, host.data(), sizeof(data_type) * n, stream), "cnn_memcpy_h2d");
-    must(cnn_memset_zero(grads, sizeof(data_type) * n, stream), "cnn_memset_zero");
-    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
+    must(cnn_memset_zero(pb.grads, sizeof(data_type) * pb.n, stream), "cnn_memset_zero");
+    pb.upload(host.data());
 }
 
 BatchNorm2D::~BatchNorm2D() {
-    if (owns_params) {
-        cnn_device_free(params);
-        cnn_device_free(grads);
-    }
     cnn_device_free(saved_stats);
     if (sync_sums) cnn_device_free(sync_sums);
-    if (workspace) cnn_device_free(workspace);
 }
 
 void BatchNorm2D::bind_arena(data_type* params_dev, data_type* grads_dev) {
-    must(cnn_memcpy_d2d(params_dev, params, sizeof(data_type) * param_count(), stream), "cnn_memcpy_d2d");
     // the moving_* half of the gradient block must be (and stay) zero: the arena-wide SGD step runs over it
-    must(cnn_memset_zero(grads_dev, sizeof(data_type) * param_count(), stream), "cnn_memset_zero");
-    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
-    if (owns_params) {
-        cnn_device_free(params);
-        cnn_device_free(grads);
-    }
-    params = params_dev;
-    grads = grads_dev;
-    owns_params = false;
+    pb.adopt(params_dev, grads_dev, /*zero_grads=*/true);
 }
 
 std::vector<tensor> BatchNorm2D::forward(const std::vector<tensor>& input) {
@@ -675,24 +581,9 @@ std::vector<tensor> BatchNorm2D::forward(const std::vector<tensor>& input) {
     const int B = (int)input.size();
     const int H = input[0]->H, W = input[0]->W;
     assert(input[0]->C == out_channels);
-    if (out_buf.empty()) {  // batchnorm2d.cpp:30-35
-        out_buf.allocate(B, out_channels, H, W, name + "_output");
-        output = out_buf.views;
-        batch = B;
-    }
-    assert(B <= batch);
-    if ((in_H && in_H != H) || (in_W && in_W != W)) {
-        std::fprintf(stderr, "cnn_amd host: %s: input shape changed after the first forward (layers are shape-static)\n", name.c_str());
-        std::abort();
-    }
-    in_H = H;
-    in_W = W;
-    const size_t need = cnn_batchnorm2d_workspace_bytes(B, out_channels, H, W);
-    if (need > workspace_bytes) {
-        if (workspace) cnn_device_free(workspace);
-        workspace = dev_alloc(need);
-        workspace_bytes = need;
-    }
+    backward_done_by_pool.clear();  // (mark rule 2)
+    static_output(out_buf, B, Shape{out_channels, H, W}, Shape{out_channels, H, W}, /*fatal=*/true);  // batchnorm2d.cpp:30-35
+    workspace.reserve(cnn_batchnorm2d_workspace_bytes(B, out_channels, H, W));
     const data_type* x = batch_device_pointer(input, in_stage, name);
     if (!no_grad) {  // batchnorm2d.cpp:42
         saved_input = x;
@@ -700,6 +591,9 @@ std::vector<tensor> BatchNorm2D::forward(const std::vector<tensor>& input) {
     }
     const int C = out_channels;
     // the ReLU behind this layer gets its output from the same apply pass (both outputs are written)
+    // (mark rule 3: armed again below where this pass writes their outputs)
+    if (fused_relu != nullptr) fused_relu->fused_forward_none();
+    if (fused_pool != nullptr) fused_pool->fused_forward_none();
     data_type* y_relu = (fused_relu != nullptr && fuse_layers) ? fused_relu->fused_forward_target(B, C, H, W) : nullptr;
     // fuse_pool_block: a training pass does not write the normalised tensor when the ReLU output comes from the same kernel -- nothing in a
     // train step reads it (ReLU::backward masks by its own output, backward() below recomputes from x and the saved statistics: 589 MB of
@@ -707,8 +601,7 @@ std::vector<tensor> BatchNorm2D::forward(const std::vector<tensor>& input) {
     const bool relu_only = y_relu != nullptr && !no_grad && fuse_pool_block;
     data_type* y_out = relu_only ? nullptr : out_buf.base;
     out_valid = !relu_only;
-    recompute_lost = false;
-    last_B = B;
+    pb.lost = false;
     if (!no_grad && comm != nullptr && comm_world > 1) {
         // the batch is sharded over comm_world replicas: the reference normalises over the WHOLE batch (batchnorm2d.cpp:46-63),
         // so the per-channel sums are exchanged (two [C] all-reduces: mean first, then the squared deviations around the
@@ -717,16 +610,16 @@ std::vector<tensor> BatchNorm2D::forward(const std::vector<tensor>& input) {
         const float count = (float)((double)B * comm_world * H * W);
         data_type* s1 = sync_sums;
         data_type* s2 = sync_sums + C;
-        must(cnn_batchnorm2d_partial_sums(x, nullptr, 0.f, s1, B, C, H, W, workspace, workspace_bytes, stream), "cnn_batchnorm2d_partial_sums");
+        must(cnn_batchnorm2d_partial_sums(x, nullptr, 0.f, s1, B, C, H, W, workspace.ptr, workspace.bytes, stream), "cnn_batchnorm2d_partial_sums");
         must(cnn_allreduce_grads(comm, s1, (size_t)C, stream), "cnn_allreduce_grads");
-        must(cnn_batchnorm2d_partial_sums(x, s1, count, s2, B, C, H, W, workspace, workspace_bytes, stream), "cnn_batchnorm2d_partial_sums");
+        must(cnn_batchnorm2d_partial_sums(x, s1, count, s2, B, C, H, W, workspace.ptr, workspace.bytes, stream), "cnn_batchnorm2d_partial_sums");
         must(cnn_allreduce_grads(comm, s2, (size_t)C, stream), "cnn_allreduce_grads");
         if (y_relu)
-            must(cnn_batchnorm2d_forward_from_sums_relu(x, y_out, y_relu, params, params + C, params + 2 * C, params + 3 * C,
+            must(cnn_batchnorm2d_forward_from_sums_relu(x, y_out, y_relu, pb.params, pb.params + C, pb.params + 2 * C, pb.params + 3 * C,
                                                         saved_stats, saved_stats + C, s1, s2, count, B, C, H, W, eps, momentum, stream),
                  "cnn_batchnorm2d_forward_from_sums_relu");
         else
-            must(cnn_batchnorm2d_forward_from_sums(x, out_buf.base, params, params + C, params + 2 * C, params + 3 * C, saved_stats,
+            must(cnn_batchnorm2d_forward_from_sums(x, out_buf.base, pb.params, pb.params + C, pb.params + 2 * C, pb.params + 3 * C, saved_stats,
                                                    saved_stats + C, s1, s2, count, B, C, H, W, eps, momentum, stream),
                  "cnn_batchnorm2d_forward_from_sums");
         return first_n(output, B);
@@ -737,24 +630,23 @@ std::vector<tensor> BatchNorm2D::forward(const std::vector<tensor>& input) {
         // both stay observable: get_output() re-computes them from the statistics this pass saved
         data_type* pooled = nullptr;
         int* pmask = nullptr;
-        fused_pool->fused_forward_target(B, C, H, W, /*record=*/!no_grad, &pooled, &pmask);
-        fused_pool->own_backward();
+        fused_pool->fused_forward_target(B, C, H, W, /*record=*/!no_grad, /*takes_delta=*/false, &pooled, &pmask);
         if (relu_only) {
             fused_relu->fused_forward_skipped(B, C, H, W);
             fused_relu->set_bn_producer(this);
             y_relu = nullptr;
         }
-        must(cnn_batchnorm2d_forward_relu_pool(x, y_out, y_relu, pooled, pmask, params, params + C, params + 2 * C, params + 3 * C, saved_stats,
-                                               saved_stats + C, B, C, H, W, eps, momentum, no_grad ? 0 : 1, workspace, workspace_bytes, stream),
+        must(cnn_batchnorm2d_forward_relu_pool(x, y_out, y_relu, pooled, pmask, pb.params, pb.params + C, pb.params + 2 * C, pb.params + 3 * C, saved_stats,
+                                               saved_stats + C, B, C, H, W, eps, momentum, no_grad ? 0 : 1, workspace.ptr, workspace.bytes, stream),
              "cnn_batchnorm2d_forward_relu_pool");
     } else if (y_relu)
-        must(cnn_batchnorm2d_forward_relu(x, y_out, y_relu, params, params + C, params + 2 * C, params + 3 * C, saved_stats,
-                                          saved_stats + C, B, C, H, W, eps, momentum, no_grad ? 0 : 1, workspace, workspace_bytes,
+        must(cnn_batchnorm2d_forward_relu(x, y_out, y_relu, pb.params, pb.params + C, pb.params + 2 * C, pb.params + 3 * C, saved_stats,
+                                          saved_stats + C, B, C, H, W, eps, momentum, no_grad ? 0 : 1, workspace.ptr, workspace.bytes,
                                           stream),
              "cnn_batchnorm2d_forward_relu");
     else
-        must(cnn_batchnorm2d_forward(x, out_buf.base, params, params + C, params + 2 * C, params + 3 * C, saved_stats,
-                                     saved_stats + C, B, C, H, W, eps, momentum, no_grad ? 0 : 1, workspace, workspace_bytes,
+        must(cnn_batchnorm2d_forward(x, out_buf.base, pb.params, pb.params + C, pb.params + 2 * C, pb.params + 3 * C, saved_stats,
+                                     saved_stats + C, B, C, H, W, eps, momentum, no_grad ? 0 : 1, workspace.ptr, workspace.bytes,
                                      stream),
              "cnn_batchnorm2d_forward");
     return first_n(output, B);
@@ -766,17 +658,11 @@ std::vector<tensor> BatchNorm2D::forward(const std::vector<tensor>& input) {
 void BatchNorm2D::materialize() const {
     if (out_valid) return;
     assert(saved_input != nullptr && "get_output() of a fused-away tensor before any forward pass");
-    if (recompute_lost) {
-        // (an exception, not abort(): inspecting a layer after load_weights() must not kill the process.  The C wrapper
-        // cnnh_net_layer_output turns it into a return code.)
-        throw std::runtime_error("cnn_amd host: " + name + ": get_output() of a tensor the last forward pass did not write, after the parameters that pass "
-                                 "used were overwritten (set from outside, or stepped twice): call forward() again, or set "
-                                 "architectures::fuse_pool_block = false");
-    }
+    require_recomputable(pb, "a tensor");
     const int C = out_channels;
-    const data_type* gb = (snapshot != nullptr && snapshot_active != nullptr && *snapshot_active) ? snapshot : params;
-    must(cnn_batchnorm2d_forward(saved_input, out_buf.base, gb, gb + C, saved_stats, saved_stats + C, nullptr, nullptr, last_B, C, in_H, in_W, eps,
-                                 momentum, 0, workspace, workspace_bytes, stream),
+    const data_type* gb = pb.of_last_forward();
+    must(cnn_batchnorm2d_forward(saved_input, out_buf.base, gb, gb + C, saved_stats, saved_stats + C, nullptr, nullptr, last_B, C, in.H, in.W, eps,
+                                 momentum, 0, workspace.ptr, workspace.bytes, stream),
          "cnn_batchnorm2d_forward");
     out_valid = true;
 }
@@ -786,13 +672,11 @@ void BatchNorm2D::materialize() const {
 void BatchNorm2D::materialize_relu() const {
     if (fused_relu == nullptr || fused_relu->output_valid()) return;
     assert(saved_input != nullptr && "get_output() of a fused-away tensor before any forward pass");
-    if (recompute_lost)
-        throw std::runtime_error("cnn_amd host: " + name + ": get_output() of the ReLU output the last forward pass did not write, after the parameters that "
-                                 "pass used were overwritten: call forward() again, or set architectures::fuse_pool_block = false");
+    require_recomputable(pb, "the ReLU output");
     const int C = out_channels;
-    const data_type* gb = (snapshot != nullptr && snapshot_active != nullptr && *snapshot_active) ? snapshot : params;
-    must(cnn_batchnorm2d_forward_relu(saved_input, nullptr, fused_relu->rematerialize_target_const(), gb, gb + C, saved_stats, saved_stats + C, nullptr,
-                                      nullptr, last_B, C, in_H, in_W, eps, momentum, 0, workspace, workspace_bytes, stream),
+    const data_type* gb = pb.of_last_forward();
+    must(cnn_batchnorm2d_forward_relu(saved_input, nullptr, fused_relu->rematerialize_target(), gb, gb + C, saved_stats, saved_stats + C, nullptr,
+                                      nullptr, last_B, C, in.H, in.W, eps, momentum, 0, workspace.ptr, workspace.bytes, stream),
          "cnn_batchnorm2d_forward_relu");
 }
 
@@ -805,21 +689,20 @@ std::vector<tensor> BatchNorm2D::get_output() const {
 // IN PLACE into the caller's delta, which is handed back
 bool BatchNorm2D::backward_pooled_possible(int B) const {
     return saved_input != nullptr && !(comm != nullptr && comm_world > 1) && B == last_B &&
-           cnn_batchnorm2d_backward_pooled_supported(B, out_channels, in_H, in_W) != 0;
+           cnn_batchnorm2d_backward_pooled_supported(B, out_channels, in.H, in.W) != 0;
 }
 
 void BatchNorm2D::backward_pooled(const data_type* dpool, const int* mask, const data_type* pooled, data_type* dx, int B) {
     const int C = out_channels;
-    must(cnn_batchnorm2d_backward_pooled(saved_input, dpool, mask, pooled, dx, params, saved_stats, saved_stats + C, grads, grads + C, B, C, in_H,
-                                         in_W, eps, workspace, workspace_bytes, stream),
+    must(cnn_batchnorm2d_backward_pooled(saved_input, dpool, mask, pooled, dx, pb.params, saved_stats, saved_stats + C, pb.grads, pb.grads + C, B, C, in.H,
+                                         in.W, eps, workspace.ptr, workspace.bytes, stream),
          "cnn_batchnorm2d_backward_pooled");
-    backward_done_by_pool = true;
+    backward_done_by_pool.arm();
 }
 
 std::vector<tensor> BatchNorm2D::backward(std::vector<tensor>& delta) {
     Tensor3D::device_work_enqueued();  // host copies of device views made before this call are stale from here on
-    if (backward_done_by_pool) {  // (the pool behind this layer's ReLU ran this pass from the pooled domain: delta already is dx)
-        backward_done_by_pool = false;
+    if (backward_done_by_pool.take()) {  // (the pool behind this layer's ReLU ran this pass from the pooled domain: delta already is dx)
         grads_ready = true;
         return delta;
     }
@@ -831,52 +714,32 @@ std::vector<tensor> BatchNorm2D::backward(std::vector<tensor>& delta) {
     if (comm != nullptr && comm_world > 1) {
         // sync-BN: one [C][4] all-reduce; gamma / beta gradients come out as the FULL-batch sums on every replica (the arena
         // all-reduce + the 1/world of the SGD step leave them unchanged: world * sum / world)
-        const float count = (float)((double)B * comm_world * in_H * in_W);
+        const float count = (float)((double)B * comm_world * in.H * in.W);
         data_type* s4 = sync_sums + 2 * C;
-        must(cnn_batchnorm2d_backward_sums(saved_input, d, params, saved_stats, saved_stats + C, s4, B, C, in_H, in_W, eps, workspace,
-                                           workspace_bytes, stream),
+        must(cnn_batchnorm2d_backward_sums(saved_input, d, pb.params, saved_stats, saved_stats + C, s4, B, C, in.H, in.W, eps, workspace.ptr,
+                                           workspace.bytes, stream),
              "cnn_batchnorm2d_backward_sums");
         must(cnn_allreduce_grads(comm, s4, (size_t)4 * C, stream), "cnn_allreduce_grads");
-        must(cnn_batchnorm2d_backward_from_sums(saved_input, d, params, saved_stats, saved_stats + C, s4, count, grads, grads + C, B, C,
-                                                in_H, in_W, eps, stream),
+        must(cnn_batchnorm2d_backward_from_sums(saved_input, d, pb.params, saved_stats, saved_stats + C, s4, count, pb.grads, pb.grads + C, B, C,
+                                                in.H, in.W, eps, stream),
              "cnn_batchnorm2d_backward_from_sums");
     } else
-        must(cnn_batchnorm2d_backward(saved_input, d, params, saved_stats, saved_stats + C, grads, grads + C, B, C, in_H, in_W,
-                                      eps, workspace, workspace_bytes, stream),
+        must(cnn_batchnorm2d_backward(saved_input, d, pb.params, saved_stats, saved_stats + C, pb.grads, pb.grads + C, B, C, in.H, in.W,
+                                      eps, workspace.ptr, workspace.bytes, stream),
              "cnn_batchnorm2d_backward");
-    if (!in_place || d == delta_stage.base) {  // host (or scattered) deltas were staged: write the result back
-        const size_t len = out_buf.sample_len;
-        for (int b = 0; b < B; ++b) {
-            if (delta[b]->on_device())
-                must(cnn_memcpy_d2d(delta[b]->dev, d + len * b, sizeof(data_type) * len, stream), "cnn_memcpy_d2d");
-            else
-                must(cnn_memcpy_d2h(delta[b]->data, d + len * b, sizeof(data_type) * len, stream), "cnn_memcpy_d2h");
-        }
-        must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
-    }
+    write_back_staged(delta, d, out_buf.sample_len, B, !in_place || d == delta_stage.base);
     grads_ready = true;
     return delta;
 }
 
 void BatchNorm2D::update_gradients(const data_type learning_rate) {  // batchnorm2d.cpp:160-166: gamma and beta only
     assert(grads_ready);
-    must(cnn_sgd_update(params, grads, (size_t)2 * out_channels, learning_rate, 1.f, stream), "cnn_sgd_update");
+    must(cnn_sgd_update(pb.params, pb.grads, (size_t)2 * out_channels, learning_rate, 1.f, stream), "cnn_sgd_update");
 }
 
 // batchnorm2d.cpp:168-182: gamma, beta, moving_mean, moving_var == the device block
-void BatchNorm2D::save_weights(std::ofstream& writer) const {
-    std::vector<data_type> host(param_count());
-    must(cnn_memcpy_d2h(host.data(), params, sizeof(data_type) * host.size(), stream), "cnn_memcpy_d2h");
-    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
-    writer.write(reinterpret_cast<const char*>(host.data()), static_cast<std::streamsize>(sizeof(data_type) * host.size()));
-}
-
-void BatchNorm2D::load_weights(std::ifstream& reader) {
-    std::vector<data_type> host(param_count());
-    reader.read(reinterpret_cast<char*>(host.data()), static_cast<std::streamsize>(sizeof(data_type) * host.size()));
-    must(cnn_memcpy_h2d(params, host.data(), sizeof(data_type) * host.size(), stream), "cnn_memcpy_h2d");
-    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
-}
+void BatchNorm2D::save_weights(std::ofstream& writer) const { pb.save(writer); }
+void BatchNorm2D::load_weights(std::ifstream& reader) { pb.load(reader); }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Dropout (dropout.cpp)
@@ -890,11 +753,8 @@ std::vector<tensor> Dropout::forward(const std::vector<tensor>& input) {
         selected_num = int(p * C);
         assert(C > selected_num);
         mask.assign(C, 0);
-        out_buf.allocate(B, C, H, W, name + "_output");
-        output = out_buf.views;
-        in_C = C; in_H = H; in_W = W;
     }
-    assert((size_t)B <= out_buf.views.size() && C == in_C && H == in_H && W == in_W);
+    static_output(out_buf, B, Shape{C, H, W}, Shape{C, H, W}, /*fatal=*/false);
     std::shuffle(sequence.begin(), sequence.end(), drop);  // dropout.cpp:26 (the draw happens in both modes)
     if (!no_grad)
         for (int i = 0; i < C; ++i) mask[i] = i >= selected_num ? sequence[i] : -1;  // dropout.cpp:31-33
@@ -910,18 +770,9 @@ std::vector<tensor> Dropout::backward(std::vector<tensor>& delta) {
     const bool in_place = delta[0]->on_device();
     data_type* d = batch_device_pointer_mut(delta, delta_stage, name + "_dy");
     int dropped = 0;
-    for (int o = 0; o < in_C; ++o) dropped += mask[o] == -1;  // (= selected_num after a training forward, 0 before any)
-    must(cnn_dropout_backward(d, B, in_C, in_H, in_W, dropped, stream), "cnn_dropout_backward");
-    if (!in_place || d == delta_stage.base) {  // host (or scattered) deltas were staged: write the result back
-        const size_t len = out_buf.sample_len;
-        for (int b = 0; b < B; ++b) {
-            if (delta[b]->on_device())
-                must(cnn_memcpy_d2d(delta[b]->dev, d + len * b, sizeof(data_type) * len, stream), "cnn_memcpy_d2d");
-            else
-                must(cnn_memcpy_d2h(delta[b]->data, d + len * b, sizeof(data_type) * len, stream), "cnn_memcpy_d2h");
-        }
-        must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
-    }
+    for (int o = 0; o < in.C; ++o) dropped += mask[o] == -1;  // (= selected_num after a training forward, 0 before any)
+    must(cnn_dropout_backward(d, B, in.C, in.H, in.W, dropped, stream), "cnn_dropout_backward");
+    write_back_staged(delta, d, out_buf.sample_len, B, !in_place || d == delta_stage.base);
     return delta;
 }
 
@@ -929,17 +780,15 @@ std::vector<tensor> Dropout::backward(std::vector<tensor>& delta) {
 // LinearLayer
 LinearLayer::LinearLayer(std::string _name, const int _in_channels, const int _out_channels)
     : Layer(_name), in_channels(_in_channels), out_channels(_out_channels) {
-    const size_t n = param_count();
-    params = (data_type*)dev_alloc(sizeof(data_type) * n);
-    grads = (data_type*)dev_alloc(sizeof(data_type) * n);
-    std::vector<data_type> host(n);
+    in = Shape{in_channels, 1, 1};  // (any input of that length)
+    pb.allocate(param_count());
+    std::vector<data_type> host(pb.n);
     std::default_random_engine e(1998);  // linear.cpp:14-18: bias first, then the matrix
     std::normal_distribution<float> engine(0.0, 1.0);
     data_type* bias = host.data() + (size_t)in_channels * out_channels;
     for (int i = 0; i < out_channels; ++i) bias[i] = engine(e) / random_times;
     for (size_t i = 0; i < (size_t)in_channels * out_channels; ++i) host[i] = engine(e) / random_times;
-    must(cnn_memcpy_h2d(params, host.data(), sizeof(data_type) * n, stream), "cnn_memcpy_h2d");
-    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
+    pb.upload(host.data());
 }
 
 LinearLayer::~LinearLayer() {
@@ -949,41 +798,22 @@ LinearLayer::~LinearLayer() {
     }
     if (ev_wb) cnn_event_destroy(ev_wb);
     if (ev_head) cnn_event_destroy(ev_head);
-    if (owns_params) {
-        cnn_device_free(params);
-        cnn_device_free(grads);
-    }
 }
 
-void LinearLayer::bind_arena(data_type* params_dev, data_type* grads_dev) {
-    must(cnn_memcpy_d2d(params_dev, params, sizeof(data_type) * param_count(), stream), "cnn_memcpy_d2d");
-    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
-    if (owns_params) {
-        cnn_device_free(params);
-        cnn_device_free(grads);
-    }
-    params = params_dev;
-    grads = grads_dev;
-    owns_params = false;
-}
+void LinearLayer::bind_arena(data_type* params_dev, data_type* grads_dev) { pb.adopt(params_dev, grads_dev, /*zero_grads=*/false); }
 
 std::vector<tensor> LinearLayer::forward(const std::vector<tensor>& input) {
     Tensor3D::device_work_enqueued();  // host copies of device views made before this call are stale from here on
     const int B = (int)input.size();
     delta_shape = input[0]->get_shape();  // linear.cpp:25
-    assert(input[0]->get_length() == in_channels);
-    if (out_buf.empty()) {
-        out_buf.allocate(B, out_channels, 1, 1, name + "_output");
-        output = out_buf.views;
-        batch = B;
-    }
-    assert(B <= batch);
+    static_output(out_buf, B, Shape{input[0]->get_length(), 1, 1}, Shape{out_channels, 1, 1}, /*fatal=*/false);
+    head_dx_done.clear();  // (mark rule 2)
     const data_type* x = batch_device_pointer(input, in_stage, name);
     if (!no_grad) {
         saved_input = x;
         saved_input_tensors = input;
     }
-    must(cnn_linear_forward(x, params, params + (size_t)in_channels * out_channels, out_buf.base, B, in_channels,
+    must(cnn_linear_forward(x, pb.params, pb.params + (size_t)in_channels * out_channels, out_buf.base, B, in_channels,
                             out_channels, stream),
          "cnn_linear_forward");
     if (lazy_host_sync) return first_n(output, B);  // materialised on demand (Layer::get_output / Tensor3D::sync_to_host)
@@ -1004,30 +834,25 @@ std::vector<tensor> LinearLayer::forward_loss_head(const std::vector<tensor>& in
     Tensor3D::device_work_enqueued();  // host copies of device views made before this call are stale from here on
     const int B = (int)input.size();
     delta_shape = input[0]->get_shape();
-    assert(input[0]->get_length() == in_channels && loss_head_supported());
-    if (out_buf.empty()) {
-        out_buf.allocate(B, out_channels, 1, 1, name + "_output");
-        output = out_buf.views;
-        batch = B;
-    }
-    assert(B <= batch);
+    assert(loss_head_supported());
+    static_output(out_buf, B, Shape{input[0]->get_length(), 1, 1}, Shape{out_channels, 1, 1}, /*fatal=*/false);
     const data_type* x = batch_device_pointer(input, in_stage, name);
     saved_input = x;
     saved_input_tensors = input;
-    head_dx_done = false;
+    head_dx_done.clear();  // (mark rule 2)
     if (with_dx && B == batch) {
         if (delta_buf.empty())
             delta_buf.allocate(batch, std::get<0>(delta_shape), std::get<1>(delta_shape), std::get<2>(delta_shape), "linear_delta");
         // (this kernel is now the last one in front of the next layer's weight-gradient fork: it carries the event)
         if (publish_backward) must(cnn_amd_publish_next_kernel(stream), "cnn_amd_publish_next_kernel");
-        must(cnn_linear_forward_softmax_xent_dx(x, params, params + (size_t)in_channels * out_channels, labels_dev, out_buf.base, probs_dev,
+        must(cnn_linear_forward_softmax_xent_dx(x, pb.params, pb.params + (size_t)in_channels * out_channels, labels_dev, out_buf.base, probs_dev,
                                                 delta_dev, loss_terms_dev, delta_buf.base, (relu_below != nullptr && fuse_layers) ? 1 : 0, B,
                                                 in_channels, out_channels, stream),
              "cnn_linear_forward_softmax_xent_dx");
-        head_dx_done = true;
+        head_dx_done.arm();
         return first_n(output, B);
     }
-    must(cnn_linear_forward_softmax_xent(x, params, params + (size_t)in_channels * out_channels, labels_dev, out_buf.base, probs_dev,
+    must(cnn_linear_forward_softmax_xent(x, pb.params, pb.params + (size_t)in_channels * out_channels, labels_dev, out_buf.base, probs_dev,
                                          delta_dev, loss_terms_dev, B, in_channels, out_channels, stream),
          "cnn_linear_forward_softmax_xent");
     return first_n(output, B);
@@ -1041,11 +866,11 @@ std::vector<tensor> LinearLayer::backward(std::vector<tensor>& delta) {
     if (delta_buf.empty())
         delta_buf.allocate(batch, std::get<0>(delta_shape), std::get<1>(delta_shape), std::get<2>(delta_shape),
                            "linear_delta");
-    if (head_dx_done) {
+    if (relu_below != nullptr) relu_below->fused_backward(fuse_layers);  // (mark rule 3: every branch below masks for it under fuse_layers)
+    if (head_dx_done.take()) {
         // the data gradient (and the ReLU::backward in front) came out of the loss-head kernel; what is left needs every sample's
         // delta and nobody on the critical path waits for it: weight / bias gradient on the library's side stream, like the
         // convolutions' (ordered before the join / the step's tail)
-        head_dx_done = false;
         void* side = nullptr;
         if (cnn_amd_get_option("LINEAR_WB_OWN_STREAM", nullptr, 0) != 0) {
             // default: the library's side stream, in front of the convolutions' weight gradients (measured: 588-598 k images/s
@@ -1066,25 +891,23 @@ std::vector<tensor> LinearLayer::backward(std::vector<tensor>& delta) {
             must(cnn_event_record(ev_head, stream), "cnn_event_record");
             must(cnn_stream_wait_event(side, ev_head), "cnn_stream_wait_event");
         }
-        must(cnn_linear_backward(saved_input, dy, params, grads, grads + (size_t)in_channels * out_channels, nullptr, B, in_channels,
+        must(cnn_linear_backward(saved_input, dy, pb.params, pb.grads, pb.grads + (size_t)in_channels * out_channels, nullptr, B, in_channels,
                                  out_channels, (float)B, side),
              "cnn_linear_backward");
         if (side == own_stream) {
             must(cnn_event_record(ev_wb, own_stream), "cnn_event_record");
             wb_pending = true;
         }
-        if (relu_below != nullptr && fuse_layers) relu_below->fused_backward_done();
         grads_ready = true;
         return first_n(delta_buf.views, B);
     }
     if (relu_below != nullptr && fuse_layers) {  // the input IS that ReLU's output: its backward mask in the same kernel
         if (publish_backward) must(cnn_amd_publish_next_kernel(stream), "cnn_amd_publish_next_kernel");
-        must(cnn_linear_backward_relu(saved_input, dy, params, grads, grads + (size_t)in_channels * out_channels, delta_buf.base, B,
+        must(cnn_linear_backward_relu(saved_input, dy, pb.params, pb.grads, pb.grads + (size_t)in_channels * out_channels, delta_buf.base, B,
                                       in_channels, out_channels, (float)B, stream),
              "cnn_linear_backward_relu");
-        relu_below->fused_backward_done();
     } else {
-        must(cnn_linear_backward(saved_input, dy, params, grads, grads + (size_t)in_channels * out_channels, delta_buf.base, B,
+        must(cnn_linear_backward(saved_input, dy, pb.params, pb.grads, pb.grads + (size_t)in_channels * out_channels, delta_buf.base, B,
                                  in_channels, out_channels, (float)B, stream),
              "cnn_linear_backward");
     }
@@ -1101,19 +924,8 @@ void LinearLayer::join_pending(void* on_stream) {
 void LinearLayer::update_gradients(const data_type learning_rate) {
     assert(grads_ready);  // linear.cpp:97
     join_pending(stream);
-    must(cnn_sgd_update(params, grads, param_count(), learning_rate, 1.f, stream), "cnn_sgd_update");
+    must(cnn_sgd_update(pb.params, pb.grads, param_count(), learning_rate, 1.f, stream), "cnn_sgd_update");
 }
 
-void LinearLayer::save_weights(std::ofstream& writer) const {
-    std::vector<data_type> host(param_count());
-    must(cnn_memcpy_d2h(host.data(), params, sizeof(data_type) * host.size(), stream), "cnn_memcpy_d2h");
-    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
-    writer.write(reinterpret_cast<const char*>(host.data()), static_cast<std::streamsize>(sizeof(data_type) * host.size()));
-}
-
-void LinearLayer::load_weights(std::ifstream& reader) {
-    std::vector<data_type> host(param_count());
-    reader.read(reinterpret_cast<char*>(host.data()), static_cast<std::streamsize>(sizeof(data_type) * host.size()));
-    must(cnn_memcpy_h2d(params, host.data(), sizeof(data_type) * host.size(), stream), "cnn_memcpy_h2d");
-    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
-}
+void LinearLayer::save_weights(std::ofstream& writer) const { pb.save(writer); }
+void LinearLayer::load_weights(std::ifstream& reader) { pb.load(reader); }

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <iostream>
 #include <iterator>
 
@@ -128,8 +129,7 @@ void Sequential::bind(data_type* p, data_type* g) {
         if (n) layer->bind_arena(p + off, g + off);
         // fuse_pool_block: Conv2D::get_output() of a fused-away tensor needs the parameters of the last forward pass -- the
         // container keeps them across its SGD step (cnn_sgd_update_keep / ..._sgd_keep write them here)
-        if (auto* conv = dynamic_cast<Conv2D*>(layer.get())) conv->set_param_snapshot(param_prev + off, &params_stepped);
-        if (auto* bn = dynamic_cast<BatchNorm2D*>(layer.get())) bn->set_param_snapshot(param_prev + off, &params_stepped);
+        layer->set_param_snapshot(param_prev + off, &params_stepped);
         off += n;
     }
     if (block_conv != nullptr) {
@@ -204,6 +204,24 @@ Sequential::~Sequential() {
     if (ev_comm) cnn_event_destroy(ev_comm);
 }
 
+// one cnn_conv2d_prepare_filters call per run of at most six consecutive layers that share a stream
+static void prepare_chunked(const std::vector<Conv2D*>& convs, const std::function<void*(size_t)>& stream_for) {
+    for (size_t first = 0, n; first < convs.size(); first += n) {
+        for (n = 1; n < 6 && first + n < convs.size() && stream_for(first + n) == stream_for(first);) ++n;
+        std::vector<cnn_conv2d_desc> descs;
+        std::vector<const float*> w, b;
+        std::vector<void*> f(n), g(n);
+        for (size_t i = 0; i < n; ++i) {
+            Conv2D* c = convs[first + i];
+            descs.push_back(c->current_desc());
+            w.push_back(c->filters_dev());
+            b.push_back(c->bias_dev());
+            c->prepared_buffers(&f[i], &g[i]);
+        }
+        must(cnn_conv2d_prepare_filters((int)n, descs.data(), w.data(), b.data(), f.data(), g.data(), stream_for(first)), "cnn_conv2d_prepare_filters");
+    }
+}
+
 // cnn_conv2d_prepare_filters for all convolutions (instead of one small re-layout launch inside every forward and backward
 // call), at most 6 layers per call; possible once every layer has seen its input shape, i.e. from the second forward pass on.
 void Sequential::prepare_filters() {
@@ -229,21 +247,7 @@ void Sequential::prepare_filters() {
         must(cnn_event_record(ev_prep_fork, stream), "cnn_event_record");  // behind the SGD step / the load that changed the parameters
         must(cnn_stream_wait_event(side, ev_prep_fork), "cnn_stream_wait_event");
     }
-    for (size_t first = 0; first < convs.size(); first += (async && first == 0) ? 1 : 6) {
-        const size_t n = (async && first == 0) ? 1 : std::min<size_t>(6, convs.size() - first);
-        std::vector<cnn_conv2d_desc> descs;
-        std::vector<const float*> w, b;
-        std::vector<void*> f(n), g(n);
-        for (size_t i = 0; i < n; ++i) {
-            Conv2D* c = convs[first + i];
-            descs.push_back(c->current_desc());
-            w.push_back(c->filters_dev());
-            b.push_back(c->bias_dev());
-            c->prepared_buffers(&f[i], &g[i]);
-        }
-        must(cnn_conv2d_prepare_filters((int)n, descs.data(), w.data(), b.data(), f.data(), g.data(), (async && first > 0) ? side : stream),
-             "cnn_conv2d_prepare_filters");
-    }
+    prepare_chunked(convs, [&](size_t i) { return (async && i > 0) ? side : stream; });
     if (async) {
         must(cnn_event_record(ev_prep, side), "cnn_event_record");
         convs[1]->wait_before_forward(ev_prep);
@@ -284,8 +288,7 @@ void Sequential::flush_deferred() {
 // gradients [lo, hi) of the arena are final in `stream` order: send them off on the communication stream
 void Sequential::flush_bucket(size_t lo, size_t hi) {
     if (hi <= lo) return;
-    for (auto& layer : layers_sequence)
-        if (auto* lin = dynamic_cast<LinearLayer*>(layer.get())) lin->join_pending(stream);
+    for (auto& layer : layers_sequence) layer->join_pending(stream);
     must(cnn_amd_side_stream_join(stream), "cnn_amd_side_stream_join");  // (weight gradients of light layers run on the side stream)
     must(cnn_event_record(ev_grads, stream), "cnn_event_record");
     must(cnn_stream_wait_event(comm_stream, ev_grads), "cnn_stream_wait_event");
@@ -308,8 +311,7 @@ void Sequential::backward(std::vector<tensor>& delta_start) {
         }
     }
     grads_reduced = false;
-    for (auto& layer : layers_sequence)
-        if (auto* lin = dynamic_cast<LinearLayer*>(layer.get())) lin->join_pending(stream);
+    for (auto& layer : layers_sequence) layer->join_pending(stream);
     if (bucketed) {
         flush_bucket(0, pending_hi);
         must(cnn_event_record(ev_comm, comm_stream), "cnn_event_record");
@@ -359,17 +361,13 @@ std::vector<uchar> Sequential::grad_cam(const std::string& layer_name, std::vect
 
 void Sequential::invalidate_filter_images() {
     filters_prepared = false;  // re-prepared at the start of the next forward pass
-    for (auto& layer : layers_sequence)
-        if (auto* c = dynamic_cast<Conv2D*>(layer.get())) c->set_prepared(false);
+    for (auto& layer : layers_sequence) layer->invalidate_prepared();
 }
 
 void Sequential::parameters_changed() {
     params_stepped = false;    // (an outside write: there is no snapshot of what the last forward pass used)
     invalidate_filter_images();
-    for (auto& layer : layers_sequence) {
-        if (auto* c = dynamic_cast<Conv2D*>(layer.get())) c->params_of_last_forward_lost();
-        if (auto* bn = dynamic_cast<BatchNorm2D*>(layer.get())) bn->params_of_last_forward_lost();
-    }
+    for (auto& layer : layers_sequence) layer->params_of_last_forward_lost();
 }
 
 void Sequential::set_comm(void* rccl_comm, int world) {
@@ -398,10 +396,7 @@ void Sequential::set_comm(void* rccl_comm, int world) {
     char text[8] = {0};
     const bool own = cnn_amd_get_option("BN_OWN_COMM", text, sizeof(text)) == 0 && std::atoi(text) != 0;
     if (comm != nullptr && has_bn && own && cnn_comm_split(comm, 0, rank, &bn_comm) != CNN_AMD_OK) bn_comm = nullptr;
-    for (auto& layer : layers_sequence) {
-        if (auto* bn = dynamic_cast<BatchNorm2D*>(layer.get())) bn->set_comm(bn_comm ? bn_comm : comm, comm_world);
-        if (auto* conv = dynamic_cast<Conv2D*>(layer.get())) conv->set_comm(comm, comm_world, rank);
-    }
+    for (auto& layer : layers_sequence) layer->set_comm(comm, bn_comm ? bn_comm : comm, comm_world, rank);
     if (comm && !comm_stream) {
         must(cnn_stream_create(&comm_stream), "cnn_stream_create");
         must(cnn_event_create(&ev_grads), "cnn_event_create");
@@ -449,10 +444,7 @@ void Sequential::update_gradients(const data_type learning_rate, const data_type
     assert(finalized && "the grad_scale form works on the flat arena: call finalize()");
     // (the old values go to the snapshot: Conv2D::get_output() of a fused-away tensor re-computes it with them)
     if (params_stepped)  // a second step without a forward pass in between: the snapshot would now receive already-stepped values
-        for (auto& layer : layers_sequence) {
-            if (auto* c = dynamic_cast<Conv2D*>(layer.get())) c->params_of_last_forward_lost();
-            if (auto* bn = dynamic_cast<BatchNorm2D*>(layer.get())) bn->params_of_last_forward_lost();
-        }
+        for (auto& layer : layers_sequence) layer->params_of_last_forward_lost();
     if (clip_max_norm > 0 && n_params > 0)  // (behind the all-reduce, in front of the step; the step applies grad_scale to the clipped values)
         must(cnn_clip_grad_norm(grad_arena, n_params, clip_max_norm, grad_scale, clip_workspace, clip_workspace_bytes, clip_stats, stream),
              "cnn_clip_grad_norm");
@@ -471,20 +463,7 @@ void Sequential::prepare_later_filters(void* on_stream) {
     for (auto& layer : layers_sequence)
         if (auto* c = dynamic_cast<Conv2D*>(layer.get()))
             if (c != block_conv) later.push_back(c);
-    for (size_t first = 0; first < later.size(); first += 6) {
-        const size_t n = std::min<size_t>(6, later.size() - first);
-        std::vector<cnn_conv2d_desc> descs;
-        std::vector<const float*> w, b;
-        std::vector<void*> f(n), g(n);
-        for (size_t i = 0; i < n; ++i) {
-            Conv2D* c = later[first + i];
-            descs.push_back(c->current_desc());
-            w.push_back(c->filters_dev());
-            b.push_back(c->bias_dev());
-            c->prepared_buffers(&f[i], &g[i]);
-        }
-        must(cnn_conv2d_prepare_filters((int)n, descs.data(), w.data(), b.data(), f.data(), g.data(), on_stream), "cnn_conv2d_prepare_filters");
-    }
+    prepare_chunked(later, [&](size_t) { return on_stream; });
 }
 
 // The end of a train step whose first block ran pool-fused (profiles/NOTEBOOK.md section 4.13), called where the backward walk reaches that
@@ -524,8 +503,7 @@ bool Sequential::fused_tail(std::vector<tensor>& delta, const data_type learning
         if (!input_gradient) pending_dgrad.valid = false;
         must(cnn_event_record(ev_tail, stream), "cnn_event_record");
         must(cnn_stream_wait_event(side, ev_tail), "cnn_stream_wait_event");
-        for (auto& layer : layers_sequence)
-            if (auto* lin = dynamic_cast<LinearLayer*>(layer.get())) lin->join_pending(side);
+        for (auto& layer : layers_sequence) layer->join_pending(side);
         must(cnn_amd_flush_reduces(side), "cnn_amd_flush_reduces");
         step_arena(lo, n_params, learning_rate, scale, side);
         prepare_later_filters(side);
@@ -552,8 +530,7 @@ bool Sequential::fused_tail(std::vector<tensor>& delta, const data_type learning
         if (cnn_amd_published_is_last(stream)) must(cnn_amd_wait_published(defer_stream), "cnn_amd_wait_published");
         else must(cnn_stream_wait_event(defer_stream, ev_tail), "cnn_stream_wait_event");
     }
-    for (auto& layer : layers_sequence)  // (a loss-head pass: the linear layer's weight / bias gradient runs on its own stream)
-        if (auto* lin = dynamic_cast<LinearLayer*>(layer.get())) lin->join_pending(side);
+    for (auto& layer : layers_sequence) layer->join_pending(side);  // (a loss-head pass: the linear layer's weight / bias gradient runs on its own stream)
     must(cnn_amd_flush_reduces(side), "cnn_amd_flush_reduces");
     if (n_params > lo) {
         // bucket 1 of the exchange: everything behind the block is final ~one weight-gradient kernel before the step ends
@@ -694,8 +671,7 @@ void Sequential::train_step(const std::vector<tensor>& input, const int* labels_
             if (print_info) delta[0]->print_shape();
         }
         grads_reduced = false;
-        for (auto& layer : layers_sequence)
-            if (auto* lin = dynamic_cast<LinearLayer*>(layer.get())) lin->join_pending(stream);
+        for (auto& layer : layers_sequence) layer->join_pending(stream);
         must(cnn_amd_side_stream_join(stream), "cnn_amd_side_stream_join");
         update_gradients(learning_rate);  // (flush_deferred() inside: a deferred kernel still in flight is ordered here)
         return;
