@@ -16,6 +16,7 @@ import torch
 
 from cnn_amd import capi
 from oracle import pyoracle as O
+from tests import guarded as G
 
 widths = "widths" in sys.argv[1:]
 batches = "batches" in sys.argv[1:]  # square BASELINE planes (7 / 14 / 28 / 56, pad 1, stride 1 / 2) at batches of 1 .. 140: units per workgroup, ragged last units, tall units
@@ -99,17 +100,19 @@ for it in range(n_cases):
     if os.environ.get("FUZZ_AUTOTUNE"):  # let the library measure and pin the implicit-GEMM tile of this geometry first (cnn_conv2d_autotune)
         conv.autotune()
     xd, wd, bd, dyd = (torch.from_numpy(t).cuda() for t in (x, w, b, dy))
-    # every output lives between two guard zones of a larger allocation: a kernel that stores outside its tensor shows up there
-    GUARD, CANARY = 4096, -12345.5
+    # every output lives between two poisoned guard zones of a larger allocation (tests/guarded.py), and so does the workspace, at exactly the
+    # size the query promises: a kernel that stores outside its tensor or its scratch shows up there, one that reads scratch nobody wrote
+    # carries a NaN into its result
     guards = []
 
     MIS = int(os.environ.get("FUZZ_MISALIGN", "0"))  # every tensor MIS floats off a 16-byte boundary: plain pointers are all the C ABI asks for
 
     def guarded(shape):
-        n = int(np.prod(shape))
-        big = torch.full((n + 2 * GUARD + MIS,), CANARY, dtype=torch.float32, device="cuda")
-        guards.append((big[MIS:], n))
-        return big[GUARD + MIS:GUARD + MIS + n].view(*shape)
+        return G.output(shape, G.NAN, guards, shift_bytes=4 * MIS)
+
+    ws = G.scratch(conv.ws_bytes, poison=G.NAN, name="ws")
+    guards.append(ws)
+    conv.ws = ws.view
 
     if MIS:
         def shifted(t):
@@ -129,18 +132,21 @@ for it in range(n_cases):
     conv.backward_data_relu(dyd, wd, relu_in, dxm)
     gw, gb = conv.backward_weight(xd, dyd, float(B), gw=guarded((Co, Ci, k, k)), gb=guarded((Co,)))
     torch.cuda.synchronize()
-    overrun = sum(int((big[:GUARD] != CANARY).sum().item()) + int((big[GUARD + n:] != CANARY).sum().item()) for big, n in guards)
+    reports = [g.intact() for g in guards]
+    overrun = sum(r.front + r.behind for r in reports)
     names = [k.split("|")[0] for k in capi.kernel_timing_report() if not any(t in k for t in ("prep", "reduce", "relu_f", "pack"))]
     capi.kernel_timing(0)
     errs = {"y": rel(y.cpu().numpy(), y_ref), "dx": rel(dx.cpu().numpy(), dx_ref),
             "dx_relu": rel(dxm.cpu().numpy(), np.where(relu_in.cpu().numpy() <= 0, np.float32(0), dx_ref)),
             "gw": rel(gw.cpu().numpy(), gw_ref), "gb": rel(gb.cpu().numpy(), gb_ref)}
     if overrun:
-        errs["STORES OUTSIDE AN OUTPUT TENSOR (guard floats changed)"] = float(overrun)
-    e = max(errs.values())
-    worst = max(worst, e)
-    flag = "" if e <= 1e-4 else "   <-- FAIL " + str({k: f"{v:.2e}" for k, v in errs.items() if v > 1e-4})
-    bad += e > 1e-4
+        errs["STORES OUTSIDE AN OUTPUT TENSOR OR THE WORKSPACE (" + "; ".join(str(r) for r in reports if not r) + ")"] = float(overrun)
+    # (a NaN -- an output element nobody stored, or poisoned scratch that reached a result -- is a failure: `not v <= tol`, never `v > tol`)
+    fail = {k: f"{v:.2e}" for k, v in errs.items() if not v <= 1e-4}
+    e = float("nan") if any(v != v for v in errs.values()) else max(errs.values())
+    worst = worst if worst != worst else (e if e != e else max(worst, e))  # (a NaN stays)
+    flag = "   <-- FAIL " + str(fail) if fail else ""
+    bad += bool(fail)
     print(f"{str(case):42s} {e:.2e}  {' '.join(sorted(set(names)))}{flag}")
 print(f"FUZZ {'OK' if bad == 0 else 'FAILED'}: {n_cases} geometries, worst tensor-normalised error {worst:.2e}, {bad} above 1e-4")
 sys.exit(1 if bad else 0)

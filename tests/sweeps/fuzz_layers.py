@@ -17,6 +17,7 @@ import torch
 
 from cnn_amd import capi
 from oracle import pyoracle as O
+from tests import guarded as G
 
 what = sys.argv[1] if len(sys.argv) > 1 else "all"
 n_cases = int(sys.argv[2]) if len(sys.argv) > 2 else 40
@@ -32,7 +33,6 @@ def rel(a, ref):
 
 
 MIS = int(os.environ.get("FUZZ_MISALIGN", "0"))  # every input tensor MIS elements off its allocation's start (plain pointers are all the C ABI asks for)
-GUARD, CANARY = 2048, -12345.5
 _guards = []
 
 
@@ -46,25 +46,29 @@ def dev(a):
 
 
 def guarded(shape):
-    """an fp32 output between two guard zones of a larger allocation: a store outside the tensor changes a canary"""
-    n = int(np.prod(shape))
-    big = torch.full((n + 2 * GUARD + MIS,), CANARY, dtype=torch.float32, device="cuda")
-    _guards.append((big[MIS:], n))
-    return big[GUARD + MIS:GUARD + MIS + n].view(*shape)
+    """an fp32 output between two poisoned guard zones of a larger allocation (tests/guarded.py): a store outside the tensor changes a canary"""
+    return G.output(shape, G.NAN, _guards, shift_bytes=4 * MIS)
+
+
+def guarded_ws(n_bytes, name):
+    """a workspace of exactly the size its query promises, NaN-poisoned, between guard zones -> the uint8 tensor to hand over"""
+    g = G.scratch(n_bytes, poison=G.NAN, name=name)
+    _guards.append(g)
+    return g.view
 
 
 def overruns():
-    torch.cuda.synchronize()
-    bad_ = sum(int((b[:GUARD] != CANARY).sum().item()) + int((b[GUARD + n:] != CANARY).sum().item()) for b, n in _guards)
+    reports = [r for r in (g.intact() for g in _guards) if not r]
     _guards.clear()
-    return {"STORES OUTSIDE AN OUTPUT TENSOR": float(bad_)} if bad_ else {}
+    return {"STORES OUTSIDE AN OUTPUT TENSOR OR A WORKSPACE (" + "; ".join(str(r) for r in reports) + ")": float(sum(r.front + r.behind for r in reports))} if reports else {}
 
 
 def report(tag, errs, names=""):
     global bad, worst
-    e = max(errs.values())
-    worst = max(worst, e)
-    fail = {k: f"{v:.2e}" for k, v in errs.items() if v > TOL}
+    # (a NaN -- an output element nobody stored, or poisoned scratch that reached a result -- is a failure: `not v <= TOL`, never `v > TOL`)
+    e = float("nan") if any(v != v for v in errs.values()) else max(errs.values())
+    worst = worst if worst != worst else (e if e != e else max(worst, e))  # (a NaN stays)
+    fail = {k: f"{v:.2e}" for k, v in errs.items() if not v <= TOL}
     bad += bool(fail)
     print(f"{tag:46s} {e:.2e}  {names}{'   <-- FAIL ' + str(fail) if fail else ''}")
 
@@ -97,6 +101,8 @@ def conv_cases():
         gw_ref, gb_ref, dxp = O.conv2d_backward(xp, dy, w, s)
         dx_ref = dxp[:, :, pad:pad + H, pad:pad + W] if pad else dxp
         conv = capi.Conv2d(*case)
+        conv.ws = guarded_ws(conv.ws_bytes, "ws")
+        conv._bwd_ws = guarded_ws(int(conv.lib.cnn_conv2d_backward_workspace_bytes(conv.desc)), "backward ws")
         xd, wd, bd, dyd = dev(x), dev(w), dev(b), dev(dy)
         capi.kernel_timing(1)
         y = conv.forward(xd, wd, bd)
@@ -106,9 +112,11 @@ def conv_cases():
         torch.cuda.synchronize()
         names = " ".join(sorted({k_.split("|")[0] for k_ in capi.kernel_timing_report() if not any(t in k_ for t in ("prep", "reduce", "pack"))}))
         capi.kernel_timing(0)
-        report(str(case), {"y": rel(y.cpu().numpy(), y_ref), "dx": rel(dx.cpu().numpy(), dx_ref), "gw": rel(gw.cpu().numpy(), gw_ref),
-                           "gb": rel(gb.cpu().numpy(), gb_ref), "dx(both)": rel(dx2.cpu().numpy(), dx_ref), "gw(both)": rel(gw2.cpu().numpy(), gw_ref),
-                           "gb(both)": rel(gb2.cpu().numpy(), gb_ref)}, names)
+        errs = {"y": rel(y.cpu().numpy(), y_ref), "dx": rel(dx.cpu().numpy(), dx_ref), "gw": rel(gw.cpu().numpy(), gw_ref),
+                "gb": rel(gb.cpu().numpy(), gb_ref), "dx(both)": rel(dx2.cpu().numpy(), dx_ref), "gw(both)": rel(gw2.cpu().numpy(), gw_ref),
+                "gb(both)": rel(gb2.cpu().numpy(), gb_ref)}
+        errs.update(overruns())
+        report(str(case), errs, names)
 
 
 def pool_cases():
@@ -157,6 +165,7 @@ def bn_cases():
         y_o, _, sm_o, sv_o, mm_o, mv_o = O.batchnorm_forward(x, gamma, beta, mm0, mv0)
         dx_o, gg_o, gb_o = O.batchnorm_backward(x, dy, gamma, sm_o, sv_o)
         bn = capi.BatchNorm2d(B, C, H, W)
+        bn.ws = guarded_ws(bn.ws_bytes, "bn ws")
         xd, gd, bd, mmd, mvd = dev(x), dev(gamma), dev(beta), dev(mm0), dev(mv0)
         yd, rd = guarded(shape), guarded(shape)
         bn.forward(xd, gd, bd, mmd, mvd, yd, training=True, y_relu=rd)
@@ -174,6 +183,7 @@ def bn_cases():
             # fused forward: bit-identical to the separate calls
             p1, m1 = capi.maxpool_forward(rd, 2, 2)
             bn2 = capi.BatchNorm2d(B, C, H, W)
+            bn2.ws = guarded_ws(bn2.ws_bytes, "bn ws (pool forms)")
             p2, m2 = torch.full_like(p1, 7.0), torch.full_like(m1, -3)
             bn2.forward_relu_pool(xd, gd, bd, dev(mm0), dev(mv0), p2, m2, training=True)
             errs["fused fwd"] = 0.0 if (torch.equal(p1, p2) and torch.equal(m1, m2)) else 1.0
@@ -275,7 +285,8 @@ def misc_cases():
         dq = capi.dropout_backward(dev(xq).clone(), pq)
         # (the oracle's engine state: one training forward above, so its backward sees the same dropped channels -- the reference drops the
         #  FIRST int(p * C) channels of a shuffled sequence seeded 1314: identical on every first call)
-        errs = {"dropout train": bits(yq.cpu().numpy(), yq_ref), "dropout eval": bits(ye.cpu().numpy(), O.dropout_forward(xq, pq, training=False))}
+        errs = {"dropout train": bits(yq.cpu().numpy(), yq_ref), "dropout eval": bits(ye.cpu().numpy(), O.dropout_forward(xq, pq, training=False)),
+                "dropout backward": bits(dq.cpu().numpy(), O.dropout_backward(xq, pq))}
         cam, img = capi.grad_cam(dev(np.abs(xq)))
         cam_ref, img_ref = O.grad_cam(np.abs(xq))
         errs["grad-cam map"] = bits(cam.cpu().numpy(), cam_ref)
