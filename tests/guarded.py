@@ -14,6 +14,8 @@ allocation: the mistake shows as a changed canary, never as a fault.
 
 Two poisons, because each hides from one kind of reader: NAN (32-bit words 0x7FC00000) spreads through every sum but vanishes in a masked
 select (`x > 0 ? x : 0`), BYTES (0x5A everywhere: 1.5e16 as a float, a huge index as an int) survives any select but could cancel.
+operand() places an INPUT the same way (tests/test_gpu_operand_contract.py): its neighbours in memory are the poison, not whatever the
+caching allocator last held there.
 A plain module: the tests and the sweep scripts import it (`from tests import guarded`)."""
 import numpy as np
 
@@ -105,6 +107,20 @@ def output(shape, poison=NAN, keep=None, name="output", dtype=None, shift_bytes=
     t.guard = g
     if keep is not None:
         keep.append(g)
+    return t
+
+
+def operand(array, poison=NAN, keep=None, name="operand", shift_bytes=0, device="cuda"):
+    """a read-only (or in-out) operand between poison: output(...) plus a copy-in -> a tensor of the array's shape and dtype (fp32, int32
+    or uint8) whose every neighbour in memory is the poison; `.guard` is its Scratch, also appended to `keep`.  A kernel that lets a value
+    from beyond the tensor into a result carries the poison there; a store through the input pointer changes a canary (check(keep))."""
+    import torch
+
+    a = np.ascontiguousarray(array)
+    assert a.dtype in (np.float32, np.int32, np.uint8), a.dtype
+    src = torch.from_numpy(a)
+    t = output(a.shape, poison, keep, name, src.dtype, shift_bytes, device)
+    t.copy_(src)
     return t
 
 

@@ -91,10 +91,14 @@ class Refused(Exception):
 class Run:
     """one desc under one poison: the Conv2d object with every buffer replaced by a guarded one of the exact size"""
 
-    def __init__(self, T, case, poison, data, problems):
+    def __init__(self, T, case, poison, data, problems, place=None):
+        """place: how the operands reach the device -- None: plain uploads (dev); tests/test_gpu_operand_contract.py passes an object with
+        .label, .guards and place(name, array) -> tensor that puts every operand between poison, and its canaries are asked with the rest"""
         from cnn_amd import capi
 
         self.T, self.case, self.poison, self.problems = T, case, poison, problems
+        self.place, self.where = place, poison if place is None else place.label
+        self.operand_guards = [] if place is None else place.guards
         B, Ci, H, W, Co, k, s, pad = case[:8]
         self.conv = conv = capi.Conv2d(B, Ci, H, W, Co, k, s, pad)
         conv.desc.flags = case[8] if len(case) > 8 else 0
@@ -112,9 +116,12 @@ class Run:
         conv._bwd_ws, conv._im2col_ws = self.bwd.view, self.im2col.view
         self.scratch = [self.ws, self.bwd, self.im2col, self.pf, self.pd]
         self.repoison = [self.ws, self.bwd, self.im2col]  # (the prepared images: before prepare_filters only)
-        self.x, self.w, self.b, self.dy, self.relu_below = (dev(T, a) for a in data)
+        self.x, self.w, self.b, self.dy, self.relu_below = (self.operand(n, a) for n, a in zip(("x", "w", "b", "dy", "relu_below"), data))
         self.out_shape, self.x_shape, self.w_shape = conv.out_shape(), (B, Ci, H, W), (Co, Ci, k, k)
         self.results, self.logs = {}, {}
+
+    def operand(self, name, array):
+        return dev(self.T, array) if self.place is None else self.place(name, array)
 
     def out(self, shape, keep, dtype=None):
         return guarded.output(shape, self.poison, keep, dtype=dtype)
@@ -136,8 +143,8 @@ class Run:
             self.T.cuda.synchronize()
         except RuntimeError as e:
             pytest.exit(f"device error behind {name} of desc {self.case}: {e}", returncode=3)
-        for msg in guarded.check(self.scratch + keep + list(extra)):
-            self.problems.append(f"{name} [{self.poison}]: {msg}")
+        for msg in guarded.check(self.scratch + self.operand_guards + keep + list(extra)):
+            self.problems.append(f"{name} [{self.where}]: {msg}")
         self.logs[name] = {key.split("|")[0] for key in capi.kernel_timing_report()}  # (the launch log is on for the whole case)
         if outs is not None:
             self.results[name] = {k: host(v) for k, v in outs.items()}
@@ -260,12 +267,12 @@ def _check_conv_results(r, ref, may_refuse):
     """every result of one Run against the oracle and the compositions"""
     y_ref, gw_ref, gb_ref, dx_ref, dxm_ref = ref
     res, pr = r.results, r.problems
-    tag = lambda call, what: f"{call} [{r.poison}] {what}"
+    tag = lambda call, what: f"{call} [{r.where}] {what}"
     expect = {"y": y_ref, "y_relu": np.maximum(y_ref, np.float32(0)), "gw": gw_ref, "gb": gb_ref}
     for call, outs in res.items():
         if isinstance(outs, Refused):
             if not may_refuse(call):
-                pr.append(f"{call} [{r.poison}]: refused with a full-size buffer: {outs}")
+                pr.append(f"{call} [{r.where}]: refused with a full-size buffer: {outs}")
             continue
         if call.startswith("pool/"):
             continue
@@ -309,14 +316,14 @@ def _pool_family(r, packed):
     own = [mask_g, ws, pf_g, pd_g]
     if r.call(pre + "prepare_filters", lambda keep: capi.prepare_filters([conv], [r.w], [r.b], [pf_g.view], [pd_g.view]) or {}, extra=own) is None:
         return
-    tag = lambda call, what: f"{pre}{call} [{r.poison}] {what}"
+    tag = lambda call, what: f"{pre}{call} [{r.where}] {what}"
     # the composition the fused calls are held to (tests/test_gpu_parity.py): forward_relu + maxpool_forward, maxpool_backward_relu + the
     # plain gradient calls -- on plain buffers: they are the reference here, their own scratch is checked in _plain_calls
     plain = capi.Conv2d(B, Ci, H, W, Co, k, s, pad)
     y, yr = T.empty(r.out_shape, device="cuda"), T.empty(r.out_shape, device="cuda")
     plain.forward_relu(r.x, r.w, r.b, y, yr)
     pooled_ref, mask_ref = capi.maxpool_forward(yr, 2, 2)
-    dpool = dev(T, uniform_pm1(77, pshape))
+    dpool = r.operand("dpool", uniform_pm1(77, pshape))
     marked = (mask_ref | T.where(pooled_ref <= 0, T.full_like(mask_ref, -2 ** 31), T.zeros_like(mask_ref))).to(T.int32)
     dy = capi.maxpool_backward_relu(dpool, mask_ref, pooled_ref, r.out_shape, 2, 2)
     gw_ref, gb_ref = plain.backward_weight(r.x, dy, float(B))
@@ -350,6 +357,9 @@ def _pool_family(r, packed):
     if isinstance(r.results.get(pre + "relu_maxpool2_forward_prepared"), Refused):  # (the mask was poisoned in front of that call: nothing may read it)
         return
     pooled_arg = None if packed else pooled_ref
+    if r.place is not None:  # the backward calls' mask and pooled operands between poison of their own (the mask: the bytes the fused forward wrote)
+        mask = r.operand("packed pool mask (operand)" if packed else "pool mask (operand)", host(mask))
+        pooled_arg = None if packed else r.operand("pooled", host(pooled_ref))
 
     def wgrad(keep):
         gw, gb = r.out(r.w_shape, keep), r.out(r.w_shape[:1], keep)
@@ -458,7 +468,7 @@ def _short_buffers(r, ref):
                     outs["dx"] = r.out(r.x_shape, keep)
                     want["dx"] = dx_ref
                     rc = lib.cnn_conv2d_backward(d, P(r.x), P(r.dy), P(r.w), P(outs["gw"]), P(outs["gb"]), P(outs["dx"]), div, wsp, told, S(), 0)
-            where = f"{call} with {told} of {full} bytes [{r.poison}]"
+            where = f"{call} with {told} of {full} bytes [{r.where}]"
             if rc >= 1000:  # (CNN_AMD_E_HIP: a launch error is no refusal, and nothing more is started on the device)
                 pytest.exit(f"HIP error {rc} from {where} of desc {r.case}: {lib.cnn_amd_last_error().decode()}", returncode=3)
             try:
@@ -529,7 +539,7 @@ def test_conv_calls_live_within_their_scratch(T, param, golden, lib_option):
     for r in runs:  # the added descs: the stage-1 rows / the split-K partial tensors were really used, by the workspace and by the prepared path
         for call, kernel in MUST_LAUNCH.get(param, {}).items():
             if kernel not in r.logs.get(call, ()):
-                problems.append(f"{call} [{r.poison}]: no {kernel} launch, the log holds {sorted(r.logs.get(call, ()))}")
+                problems.append(f"{call} [{r.where}]: no {kernel} launch, the log holds {sorted(r.logs.get(call, ()))}")
     # the same bits under both poisons wherever the route golden pins a digest for that call of that desc (those calls repeat)
     a, b2 = runs[0].results, runs[1].results
     for call, rec in pinned.items():
@@ -545,6 +555,12 @@ BN_CASES = [BN_SHAPES[0], BN_SHAPES[2], BN_SHAPES[7], POOLED_SHAPES[4]]  # gener
 
 @pytest.mark.parametrize("shape", BN_CASES, ids=lambda s: "x".join(map(str, s)))
 def test_batchnorm_calls_live_within_their_workspace(T, shape):
+    _batchnorm_calls(T, shape)
+
+
+def _batchnorm_calls(T, shape, guard_operands=False):
+    """guard_operands (tests/test_gpu_operand_contract.py): x, gamma, beta, the moving and the saved statistics, dpool, mask and pooled lie
+    between the poison of the run too (guarded.operand), and their canaries are asked with the workspace's after every call"""
     from cnn_amd import capi
 
     L = capi.load()
@@ -560,10 +576,14 @@ def test_batchnorm_calls_live_within_their_workspace(T, shape):
     if shape in POOLED_SHAPES:  # (the shape that is here for the two pooled forms: they must really run)
         assert pool_ok and bool(L.cnn_batchnorm2d_backward_pooled_supported(B, Cc, H, W)), shape
     problems = []
-    xd, gd, bd = dev(T, x), dev(T, gamma), dev(T, beta)
     n_ws = int(L.cnn_batchnorm2d_workspace_bytes(B, Cc, H, W))
     for poison in guarded.POISONS:
+        operands = []  # (the guards of the placed operands)
+        up = (lambda name, a, poison=poison, operands=operands: guarded.operand(a, poison, operands, name)) if guard_operands else (lambda name, a: dev(T, a))
+        xd, gd, bd = up("x", x), up("gamma", gamma), up("beta", beta)
         bn = capi.BatchNorm2d(B, Cc, H, W)
+        if guard_operands:
+            bn.saved_mean, bn.saved_var = up("saved_mean", np.zeros(Cc, np.float32)), up("saved_var", np.zeros(Cc, np.float32))
         ws = guarded.scratch(n_ws, poison=poison, name="bn ws")
         bn.ws, bn.ws_bytes = ws.view, n_ws
         P = capi._ptr
@@ -574,7 +594,7 @@ def test_batchnorm_calls_live_within_their_workspace(T, shape):
             keep = []
             outs = fn(keep)
             T.cuda.synchronize()
-            problems.extend(f"{name} [{poison}]: {m}" for m in guarded.check([ws] + keep))
+            problems.extend(f"{name} [{poison}]: {m}" for m in guarded.check([ws] + operands + keep))
             return {k_: host(v) for k_, v in outs.items()}
 
         out = lambda keep, shp=shape, dtype=None: guarded.output(shp, poison, keep, dtype=dtype)
@@ -582,7 +602,7 @@ def test_batchnorm_calls_live_within_their_workspace(T, shape):
 
         def forward(training, relu):
             def fn(keep):
-                y, mm, mv = out(keep), dev(T, mm0), dev(T, mv0)
+                y, mm, mv = out(keep), up("moving_mean", mm0), up("moving_var", mv0)
                 yr = out(keep) if relu else None
                 bn.forward(xd, gd, bd, mm, mv, y, training=training, y_relu=yr)
                 res = {"y": y, "mm": mm, "mv": mv, "mean": bn.saved_mean.clone(), "var": bn.saved_var.clone()}
@@ -618,10 +638,12 @@ def test_batchnorm_calls_live_within_their_workspace(T, shape):
             pshape = (B, Cc, H // 2, W // 2)
             rd = dev(T, trr["y_relu"])
             p1, m1 = capi.maxpool_forward(rd, 2, 2)
+            if guard_operands:
+                p1, m1 = up("pooled", host(p1)), up("mask", host(m1))
 
             def relu_pool(keep):
                 pooled, mask = out(keep, pshape), out(keep, pshape, T.int32)
-                y, yr, mm, mv = out(keep), out(keep), dev(T, mm0), dev(T, mv0)
+                y, yr, mm, mv = out(keep), out(keep), up("moving_mean", mm0), up("moving_var", mv0)
                 bn.forward_relu_pool(xd, gd, bd, mm, mv, pooled, mask, y=y, y_relu=yr, training=True)
                 return {"pooled": pooled, "mask": mask, "y": y, "y_relu": yr, "mm": mm, "mv": mv}
 
@@ -630,7 +652,7 @@ def test_batchnorm_calls_live_within_their_workspace(T, shape):
                 _same(problems, f"forward_relu_pool [{poison}] {what} == forward_relu + maxpool", fp[what], want)
             _close(problems, f"forward_relu_pool [{poison}] pooled", fp["pooled"], O.maxpool_forward(O.relu_forward(y_o), 2, 2)[0])
             if bn.backward_pooled_supported():
-                dpool = dev(T, uniform_pm1(83, pshape))
+                dpool = up("dpool", uniform_pm1(83, pshape))
                 d_relu = capi.maxpool_backward_relu(dpool, m1, p1, shape, 2, 2)
                 dx3_o, gg3_o, gb3_o = O.batchnorm_backward(x, host(d_relu), gamma, sm_o, sv_o)
 
@@ -653,14 +675,14 @@ def test_batchnorm_calls_live_within_their_workspace(T, shape):
         count, dims = float(B * H * W), (B, Cc, H, W)
 
         def sync_forward(keep):
-            s1, s2, y, mm, mv = vec(keep), vec(keep), out(keep), dev(T, mm0), dev(T, mv0)
+            s1, s2, y, mm, mv = vec(keep), vec(keep), out(keep), up("moving_mean", mm0), up("moving_var", mv0)
             capi.check(L.cnn_batchnorm2d_partial_sums(P(xd), None, 0.0, P(s1), *dims, wsp, n_ws, capi._stream()), "partial_sums 1")
             T.cuda.synchronize()
-            problems.extend(f"partial_sums(1) [{poison}]: {m}" for m in guarded.check([ws]))
+            problems.extend(f"partial_sums(1) [{poison}]: {m}" for m in guarded.check([ws] + operands))
             ws.refill()
             capi.check(L.cnn_batchnorm2d_partial_sums(P(xd), P(s1), count, P(s2), *dims, wsp, n_ws, capi._stream()), "partial_sums 2")
             T.cuda.synchronize()
-            problems.extend(f"partial_sums(2) [{poison}]: {m}" for m in guarded.check([ws]))
+            problems.extend(f"partial_sums(2) [{poison}]: {m}" for m in guarded.check([ws] + operands))
             ws.refill()
             capi.check(L.cnn_batchnorm2d_forward_from_sums(P(xd), P(y), P(gd), P(bd), P(mm), P(mv), P(bn.saved_mean), P(bn.saved_var), P(s1), P(s2), count,
                                                            *dims, bn.eps, bn.momentum, capi._stream()), "forward_from_sums")
@@ -672,7 +694,7 @@ def test_batchnorm_calls_live_within_their_workspace(T, shape):
             capi.check(L.cnn_batchnorm2d_backward_sums(P(xd), P(dyd), P(gd), P(bn.saved_mean), P(bn.saved_var), P(s4), *dims, bn.eps, wsp, n_ws,
                                                        capi._stream()), "backward_sums")
             T.cuda.synchronize()
-            problems.extend(f"backward_sums [{poison}]: {m}" for m in guarded.check([ws]))
+            problems.extend(f"backward_sums [{poison}]: {m}" for m in guarded.check([ws] + operands))
             ws.refill()
             capi.check(L.cnn_batchnorm2d_backward_from_sums(P(xd), P(dyd), P(gd), P(bn.saved_mean), P(bn.saved_var), P(s4), count, P(gg), P(gb), *dims,
                                                             bn.eps, capi._stream()), "backward_from_sums")
