@@ -707,14 +707,9 @@ static int bn_forward_impl(const float* x, float* y, float* y_relu, const float*
         if (channel_path(B, C, H, W) && pooled == nullptr) {
             const size_t lds = (size_t)B * H * W * sizeof(float);
             static DeviceOnce attr_once;
-            if (attr_once.needed()) {
-                const int lim = (int)(kChanMaxElems * sizeof(float));
-                CNN_HIP_CHECK(hipFuncSetAttribute((const void*)bn_fwd_channel<false, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-                CNN_HIP_CHECK(hipFuncSetAttribute((const void*)bn_fwd_channel<true, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-                CNN_HIP_CHECK(hipFuncSetAttribute((const void*)bn_fwd_channel<false, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-                CNN_HIP_CHECK(hipFuncSetAttribute((const void*)bn_fwd_channel<true, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-                attr_once.mark();
-            }
+            if (int rc = allow_dynamic_lds(attr_once, (int)(kChanMaxElems * sizeof(float)), bn_fwd_channel<false, 1024>, bn_fwd_channel<true, 1024>,
+                                           bn_fwd_channel<false, 256>, bn_fwd_channel<true, 256>))
+                return rc;
             const bool wide = chan_threads() == 1024;
             if (y_relu) {
                 if (wide) CNN_KLAUNCH(s, "bn_fwd_channel+relu", (bn_fwd_channel<true, 1024><<<C, 1024, lds, s>>>(a, q)), BN_TAG);
@@ -797,12 +792,7 @@ int cnn_batchnorm2d_backward(const float* x, float* dy, const float* gamma, cons
     if (channel_path(B, C, H, W)) {
         const size_t lds = (size_t)B * H * W * sizeof(float) * 2;
         static DeviceOnce attr_once;
-        if (attr_once.needed()) {
-            const int lim = (int)(kChanMaxElems * sizeof(float) * 2);
-            CNN_HIP_CHECK(hipFuncSetAttribute((const void*)bn_bwd_channel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            CNN_HIP_CHECK(hipFuncSetAttribute((const void*)bn_bwd_channel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            attr_once.mark();
-        }
+        if (int rc = allow_dynamic_lds(attr_once, (int)(kChanMaxElems * sizeof(float) * 2), bn_bwd_channel<1024>, bn_bwd_channel<256>)) return rc;
         // (round 6) register-resident channels: same results bit for bit, no LDS to wait for beside the weight gradients
         if (chan_threads() == 1024 && CNN_OPT_INT("BN_BWD_LDS", 0) == 0) {
             const long long nel = (long long)B * H * W;

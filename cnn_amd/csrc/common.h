@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <initializer_list>
 
 #include "cnn_amd.h"
 
@@ -204,6 +205,23 @@ struct DeviceOnce {
         if (dev >= 0) done[dev].store(1, std::memory_order_release);
     }
 };
+// let `kernels` request up to `bytes` of dynamic LDS on the current device, once per device and `once` flag (one flag per call site
+// and template instance).  A failed call leaves the flag unmarked: `if (int rc = allow_dynamic_lds(...)) return rc;`
+template <class... K>
+inline int allow_dynamic_lds(DeviceOnce& once, int bytes, K... kernels) {
+    if (!once.needed()) return CNN_AMD_OK;
+    for (const void* kern : {(const void*)kernels...}) CNN_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    once.mark();
+    return CNN_AMD_OK;
+}
+
+// `total` work units over `want` workgroups (clamped to 1 .. total): units per workgroup, rounded up, and the workgroups that leaves
+inline void split_units(long long total, long long want, int* per_block, int* blocks) {
+    if (want < 1) want = 1;
+    if (want > total) want = total;
+    *per_block = (int)((total + want - 1) / want);
+    *blocks = (int)((total + *per_block - 1) / *per_block);
+}
 
 // SGD on one element (alexnet.cpp:62-65, conv2d.cpp / linear.cpp update_gradients):
 // p - lr*(g*scale) with every product/sum rounded separately: the reference is built without FMA

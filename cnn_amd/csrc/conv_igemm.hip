@@ -27,6 +27,7 @@
 #include <mutex>
 
 #include "conv_families.h"
+#include "lds_dma.h"
 
 using namespace cnn_amd;
 
@@ -542,7 +543,6 @@ void igemm_kernel(const IgemmParams p) {  // (round 4: the fused-ReLU epilogue o
 //   * the filter slab is stored [tap][k-half][m][4 k-steps] ("A4"), so a lane fetches its A operands for a whole tap
 //     (4 MFMA k-steps) with one conflict-free ds_read_b128; operands of tap t+1 are read before the 4*MA*NB MFMAs of
 //     tap t are issued.
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
 typedef const __attribute__((address_space(1))) void* gbl_void_ptr;
 
 //   * XM > 0 ("whole-image" staging, small images): instead of the rows a tile needs, the COMPLETE CK-channel block of
@@ -1498,11 +1498,9 @@ int make_plan(const char* who, const cnn_conv2d_desc* d, int mode, Plan* pl, boo
 template <int MF, int MA, int NB, int WM, int WN, int CK, bool NARROW, bool R2>
 int launch_cfg3(const Plan& pl, hipStream_t s, const cnn_conv2d_desc* d) {
     auto kern = igemm_kernel<MF, MA, NB, WM, WN, CK, NARROW, R2>;
-    static thread_local size_t max_set = 0;
-    if (pl.lds_bytes > 48 * 1024 && pl.lds_bytes > max_set) {
-        CNN_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        max_set = 160 * 1024;
-    }
+    static DeviceOnce attr_once;
+    if (pl.lds_bytes > 48 * 1024)
+        if (int rc = allow_dynamic_lds(attr_once, 160 * 1024, kern)) return rc;
     char name[96];
     snprintf(name, sizeof(name), "igemm_kernel<%d,%d,%d,%d,%d,%d>%s", MF, MA, NB, WM, WN, CK,
              pl.p.mode == MODE_FWD ? (R2 ? "/fwd+relu" : "/fwd") : (R2 ? "/dgrad+relu" : "/dgrad"));
@@ -1520,10 +1518,7 @@ template <int MF, int MA, int NB, int WM, int WN, int S, int XM, bool R2>
 int launch_dma_xm2(const Plan& pl, hipStream_t s, const cnn_conv2d_desc* d) {
     auto kern = igemm_dma_kernel<MF, MA, NB, WM, WN, S, XM, R2>;
     static DeviceOnce attr_once;
-    if (attr_once.needed()) {
-        CNN_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_once.mark();
-    }
+    if (int rc = allow_dynamic_lds(attr_once, 160 * 1024, kern)) return rc;
     char name[96];
     char ks[16] = "";
     if (pl.ksplit > 1) snprintf(ks, sizeof(ks), ",k/%d", pl.ksplit);

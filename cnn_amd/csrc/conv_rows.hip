@@ -623,12 +623,11 @@ bool make_rows_plan(const cnn_conv2d_desc* d, int mode, RowsPlan* pl) {
     pl->tall = 0;
     if (const int tr = (wi == 56 && pl->mt == 64) ? 14 : ((wi == 28 && pl->mt == 128) ? 7 : 0); tr && ho % tr == 0 && CNN_OPT_INT("ROWS_TALL", 1) != 0) {
         const int envb = CNN_OPT_INT("ROWS_BLOCKS", 0);
-        long long wantb = (envb > 0 ? envb : num_cus()) / pl->ntiles;
-        if (wantb < 1) wantb = 1;
+        const long long wantb = (envb > 0 ? envb : num_cus()) / pl->ntiles;
         auto cost = [&](int rows, double lane) {
-            const long long units = (long long)d->B * ((ho + rows - 1) / rows);
-            const long long w = wantb < units ? wantb : units;
-            return (double)((units + w - 1) / w) * rows * lane;
+            int per_block, blocks;
+            split_units((long long)d->B * ((ho + rows - 1) / rows), wantb, &per_block, &blocks);
+            return (double)per_block * rows * lane;
         };
         const double lane_tall = wi == 28 ? 208.0 / 196.0 : 1.0;
         if (cost(tr, lane_tall) < cost(rg, 1.0) || CNN_OPT_INT("ROWS_TALL", 1) == 2) {
@@ -653,11 +652,7 @@ bool make_rows_plan(const cnn_conv2d_desc* d, int mode, RowsPlan* pl) {
     // 64 x 128 -> 128 @ 28x28 95 / 96 against 80 / 72, 64 x 256 -> 256 @ 14x14 94 / 94 against 73 / 67, 128 x 512 -> 512 @ 14x14 101 / 107
     // against 97 / 101)
     const int env = CNN_OPT_INT("ROWS_BLOCKS", 0);
-    long long want = (env > 0 ? env : num_cus()) / pl->ntiles;
-    if (want < 1) want = 1;
-    if (want > p.units_total) want = p.units_total;
-    p.units_per_block = (int)((p.units_total + want - 1) / want);
-    pl->blocks = (p.units_total + p.units_per_block - 1) / p.units_per_block;
+    split_units(p.units_total, (env > 0 ? env : num_cus()) / pl->ntiles, &p.units_per_block, &pl->blocks);
     pl->wt_floats = (size_t)pl->ntiles * p.nchunk * ck * 9 * pl->qw;
     p.dbg = CNN_MEASURE_INT("ROWS_DBG", 0);
     return true;
@@ -669,10 +664,7 @@ int launch_rows2(const RowsPlan& pl, const char* tag, const cnn_conv2d_desc* d, 
     auto kern = conv_rows_kernel<WI, PAD, MT, RSEL, SR, RW, WP, MA, PK, CK, PROD>;
     if (G::ROWS != pl.rows || CK != pl.ck) return fail(CNN_AMD_E_BADARG, "conv_rows: plan / instance mismatch");
     static DeviceOnce attr_once;
-    if (attr_once.needed()) {
-        CNN_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_once.mark();
-    }
+    if (int rc = allow_dynamic_lds(attr_once, 160 * 1024, kern)) return rc;
     // (measurement switch ROWS_LDS=<bytes>: a larger LDS request, e.g. 90000 = never two workgroups on one CU)
     size_t lds = G::lds_bytes;
     if (const int want = CNN_MEASURE_INT("ROWS_LDS", 0); want > (int)lds && want <= 160 * 1024) lds = (size_t)want;

@@ -358,11 +358,7 @@ bool make_any_plan(const cnn_conv2d_desc* d, int mode, AnyPlan* pl) {
     pl->cls = cls; pl->pad = pad;
     pl->ntiles = (M + kMT - 1) / kMT;
     const int env = CNN_OPT_INT("ROWS_BLOCKS", 0);
-    long long want = (env > 0 ? env : num_cus()) / pl->ntiles;
-    if (want < 1) want = 1;
-    if (want > p.units_total) want = p.units_total;
-    p.units_per_block = (int)((p.units_total + want - 1) / want);
-    pl->blocks = (p.units_total + p.units_per_block - 1) / p.units_per_block;
+    split_units(p.units_total, (env > 0 ? env : num_cus()) / pl->ntiles, &p.units_per_block, &pl->blocks);
     pl->wt_floats = (size_t)pl->ntiles * p.nchunk * kCK * 9 * (kMT + 16);
     return true;
 }
@@ -373,10 +369,7 @@ int launch_any2(const AnyPlan& pl, const char* tag, const cnn_conv2d_desc* d, hi
     using G = AnyGeom<c.rp, c.xrmax>;
     auto kern = conv_any_kernel<c.rp, c.xrmax, NBW>;
     static DeviceOnce attr_once;
-    if (attr_once.needed()) {
-        CNN_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_once.mark();
-    }
+    if (int rc = allow_dynamic_lds(attr_once, 160 * 1024, kern)) return rc;
     char name[48];
     snprintf(name, sizeof(name), "conv_rows_any<%d,%dx%d>/%s", c.rp - kLeft - 2, pl.p.rpu, 16 * kWP * NBW, tag);
     CNN_KLAUNCH(s, name, (kern<<<dim3(pl.blocks, pl.ntiles), 256, G::lds_bytes, s>>>(pl.p)), "B%d Ci%d %dx%d Co%d k%d s%d p%d", d->B, d->Ci, d->H, d->W, d->Co,

@@ -516,10 +516,7 @@ int launch_inst(const S2Plan& pl, const char* tag, const cnn_conv2d_desc* d, hip
     constexpr S2Inst c = kInst[I];
     auto kern = conv_s2_kernel<c.mode, c.hi, c.wi, c.pad, c.wm, c.rpu, c.pk, c.ck>;
     static DeviceOnce attr_once;
-    if (attr_once.needed()) {
-        CNN_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_once.mark();
-    }
+    if (int rc = allow_dynamic_lds(attr_once, 160 * 1024, kern)) return rc;
     char name[48];
     snprintf(name, sizeof(name), "conv_s2<%d,%d,%d>/%s", c.wi, c.pad, G::MT, tag);
     CNN_KLAUNCH(s, name, (kern<<<dim3(pl.blocks, pl.ntiles), 256, G::lds_bytes, s>>>(pl.p)), "B%d Ci%d %dx%d Co%d k%d s%d p%d", d->B, d->Ci, d->H, d->W, d->Co,
@@ -563,11 +560,7 @@ bool make_s2_plan(const cnn_conv2d_desc* d, int mode, S2Plan* pl) {
     int per_cu = (int)((160 * 1024) / pl->lds);
     if (per_cu < 1) per_cu = 1;
     if (per_cu > 2) per_cu = 2;
-    long long want = (env > 0 ? env : num_cus() * per_cu) / pl->ntiles;
-    if (want < 1) want = 1;
-    if (want > p.units_total) want = p.units_total;
-    p.units_per_block = (int)((p.units_total + want - 1) / want);
-    pl->blocks = (p.units_total + p.units_per_block - 1) / p.units_per_block;
+    split_units(p.units_total, (env > 0 ? env : num_cus() * per_cu) / pl->ntiles, &p.units_per_block, &pl->blocks);
     pl->wt_floats = (size_t)pl->ntiles * p.nchunk * pl->ck * 9 * pl->qw;
     p.dbg = CNN_MEASURE_INT("S2_DBG", 0);
     return true;

@@ -305,14 +305,9 @@ int stem_forward(const cnn_conv2d_desc* d, const float* x, const float* w, const
     p.dbg = CNN_MEASURE_INT("STEM_DBG", 0);
     const size_t lds_bytes = ((size_t)(SKK + 1) * SAP + (size_t)SCI * SRIN * SLW + 64) * sizeof(float);
     static DeviceOnce attr_once[2];
-    const int which = y_relu ? 1 : 0;
-    if (attr_once[which].needed()) {
-        if (y_relu)
-            CNN_HIP_CHECK(hipFuncSetAttribute((const void*)conv_stem_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        else
-            CNN_HIP_CHECK(hipFuncSetAttribute((const void*)conv_stem_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        attr_once[which].mark();
-    }
+    if (int rc = y_relu ? allow_dynamic_lds(attr_once[1], (int)lds_bytes, conv_stem_fwd_kernel<true>)
+                        : allow_dynamic_lds(attr_once[0], (int)lds_bytes, conv_stem_fwd_kernel<false>))
+        return rc;
     const int co_blocks = (d->Co + 63) / 64;
     // two workgroups per CU; every workgroup gets the same number of items where that is possible
     long long gx = 2ll * num_cus() / co_blocks;
@@ -354,10 +349,7 @@ int stem_wgrad_launch(const cnn_conv2d_desc* d, const float* x, const float* dy,
     p.items = d->B * p.Ho * p.col_blocks;
     const size_t lds_bytes = ((size_t)(GXROWS + 1) * SLW + (size_t)64 * GDP) * sizeof(float);
     static DeviceOnce attr_once;
-    if (attr_once.needed()) {
-        CNN_HIP_CHECK(hipFuncSetAttribute((const void*)conv_stem_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        attr_once.mark();
-    }
+    if (int rc = allow_dynamic_lds(attr_once, (int)lds_bytes, conv_stem_wgrad_kernel)) return rc;
     const dim3 grid((unsigned)slots, (unsigned)((d->Co + 63) / 64));
     CNN_KLAUNCH(s, "conv_stem_wgrad<3,7,2,3>", (conv_stem_wgrad_kernel<<<grid, GWAVES * 64, lds_bytes, s>>>(p)), CONV_TAG(d));
     return CNN_AMD_OK;

@@ -725,10 +725,8 @@ int launch_w2(const WPlan& pl, hipStream_t s, const cnn_conv2d_desc* d, int* nsp
     auto kern = wgrad_kernel<MF, MA, NB, WM, WN, WK, NARROW, PC>;
     constexpr int kThreads = 64 * WM * WN * WK * (PC ? 2 : 1);
     static DeviceOnce attr_once;
-    if (pl.lds_bytes > 48 * 1024 && attr_once.needed()) {
-        CNN_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_once.mark();
-    }
+    if (pl.lds_bytes > 48 * 1024)
+        if (int rc = allow_dynamic_lds(attr_once, 160 * 1024, kern)) return rc;
     // split count = exactly the number of workgroups the chip holds at once (registers + LDS): a larger grid would run a
     // second, partly empty round.  The plan's nsplit is the upper bound the workspace was sized for.
     static thread_local size_t occ_lds = (size_t)-1;

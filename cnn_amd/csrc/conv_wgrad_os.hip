@@ -197,11 +197,7 @@ int launch_os(const cnn_conv2d_desc* d, const float* x, const float* dy, float* 
     p.units = d->B * G::UPI;
     p.dbg = CNN_MEASURE_INT("OS_DBG", 0);
     static DeviceOnce attr_once;
-    if (attr_once.needed()) {
-        CNN_HIP_CHECK(hipFuncSetAttribute((const void*)conv_wgrad_os_kernel<CI, CO, H, W, R>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)G::lds_bytes));
-        attr_once.mark();
-    }
+    if (int rc = allow_dynamic_lds(attr_once, (int)G::lds_bytes, conv_wgrad_os_kernel<CI, CO, H, W, R>)) return rc;
     const dim3 grid((unsigned)slots, CI / kCib, CO / kCob);
     char name[48];
     snprintf(name, sizeof(name), "conv_wgrad_os<%d,%d>", CI, CO);

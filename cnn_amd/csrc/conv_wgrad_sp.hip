@@ -26,18 +26,14 @@
 // one barrier per stage.
 // Output: slabs[blockIdx.x][Co][Ci*9 + 1] like the register-direct kernel (reduce_slabs adds the pixel ranges in a fixed order);
 // the bias gradient is accumulated on the VALU from the A registers.
-#include <cstdlib>
+// Shared with the siblings conv_wgrad_sp2.hip / conv_wgrad_sp_any.hip (wgrad_sp_common.h, lds_dma.h): the DMA primitive and its zero fill
+// of out-of-range lanes, the tile size, the plane stride of 16-byte units, a workgroup's stage range, the stage partition, the launcher.
+// Owned here: SpParams, SpGeom, the planner and the kernel body (LDS zero fill, stage loop, slab epilogue).
 #include <type_traits>
 
-#include "conv_families.h"
-
-using namespace cnn_amd;
+#include "wgrad_sp_common.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
-typedef const __attribute__((address_space(1))) void* gbl_void_ptr;
 
 struct SpParams {
     const float* x;
@@ -50,18 +46,12 @@ struct SpParams {
     int dbg;  // CNN_AMD_SP_DBG=9: workgroup 0 prints its shader-cycle count and the clock it ran at
 };
 
-// one LDS-DMA instruction through a buffer descriptor: lane l moves U floats from base + voff(l) + soff to lds + l*U.  A lane whose
-// voff lies outside the buffer moves ZEROS (probed on MI355X: tools/probes/buflds_probe.cpp) -- that is how pad floats, channels
-// behind the tensor, halo rows outside the image and the missing second sample of an odd batch are staged: every instruction runs
-// with all 64 lanes and no branch around it.
-constexpr unsigned kOob = 0x80000000u;
+// blds16 (lds_dma.h) for a DMA unit of U floats: lane l moves U floats from base + voff(l) + soff to lds + l*U
 template <int U>
 __device__ __forceinline__ void blds(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, float* lds) {
-    if constexpr (U == 4) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_ptr)lds, 16, (int)voff, (int)soff, 0, 0);
+    if constexpr (U == 4) blds16(r, voff, soff, lds);
     else __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_ptr)lds, 4, (int)voff, (int)soff, 0, 0);
 }
-
-constexpr int kTile = 64;  // output channels per workgroup tile
 
 // CT = input channels per workgroup tile: 64 (waves 2 x 2 over co x ci), or 32 for planes too wide for two LDS buffers of 64 + 64 channel
 //      rows (112-wide: waves 2 x 1 x 2 -- the two waves of a (co, ci) tile split the SEGMENTS of a stage and are added at the end).
@@ -81,16 +71,14 @@ struct SpGeom {
     static constexpr int XROWS = PAIR ? RU : RU + 2;   // staged input rows per plane (HALF: with the halo rows)
     static constexpr int XLEN = XROWS * W, DLEN = RU * WO;
     // plane strides: odd for 4-byte units (32 lanes = 32 banks); a multiple of 4 with an odd piece count for 16-byte units (4-way)
-    static constexpr int stride_for(int len) {
-        return U == 1 ? (len | 1) : ((((len + 3) / 4) & 1) ? (len + 3) / 4 * 4 : (len + 3) / 4 * 4 + 4);
-    }
+    static constexpr int plane_stride(int len) { return U == 1 ? (len | 1) : stride_for(len); }
     // HALF, 16-byte units: LEAD pad floats in front of every x plane put the first row of the image (staged row 1) on a unit boundary, so
     // that the units of the top halo row hold nothing else and can be staged as zeros for the first row block of a sample (the SOURCE
     // of a 16-byte unit needs no alignment: probed, tools/probes/buflds16_probe.cpp -- rows of 14 floats are as good as rows of 28)
     static constexpr int LEAD = (!PAIR && U == 4 && PAD == 1) ? (4 - W % 4) % 4 : 0;
     static constexpr int XSPAN = LEAD + XLEN;
-    static constexpr int QX = PAIR ? XLEN : stride_for(XSPAN);
-    static constexpr int QD = PAIR ? DLEN : stride_for(DLEN);
+    static constexpr int QX = PAIR ? XLEN : plane_stride(XSPAN);
+    static constexpr int QD = PAIR ? DLEN : plane_stride(DLEN);
     static_assert(!PAIR || (XLEN & 1), "PAIR: odd plane stride (32 lanes = 32 banks)");
     static constexpr int NU = PAIR ? 2 : 1;            // samples per stage
     // DMA instructions (64 lanes x U floats) per stage
@@ -132,8 +120,8 @@ __global__ __launch_bounds__(256) void wgrad_sp_kernel(const SpParams p) {
     // everything the DMA never writes (pad floats, planes of channels behind Ci / Co) reads as zero
     for (int i = tid * 4; i < 2 * G::BUF + 4 * 64 * U; i += 1024) *(float4*)(smem + i) = make_float4(0.f, 0.f, 0.f, 0.f);
 
-    const int s_lo = blockIdx.x * p.stages_per_block;
-    const int s_hi = s_lo + p.stages_per_block < p.stages_total ? s_lo + p.stages_per_block : p.stages_total;
+    int s_lo, s_hi;
+    sp_stage_range(p, &s_lo, &s_hi);
 
     // ---- HALF: this wave's share of a stage's DMA, decoded once: the lane's byte offset from (channel ci0 / co0, first staged row) of
     //      the sample -- for x counted from W + 4 floats in front of it, see xrs --, bit 0 set: the unit holds nothing but the top halo
@@ -384,8 +372,7 @@ bool make_sp_plan(const cnn_conv2d_desc* d, SpPlan* pl) {
     else ru = kRu112;
     const int Ho = d->H - 2 * (1 - d->pad);
     if (Ho < 1 || (ru && Ho % ru != 0)) return false;
-    // (buffer descriptors: byte sizes below 2^31)
-    if ((long long)d->B * d->Ci * d->H * d->W >= (1ll << 29) || (long long)d->B * d->Co * d->H * d->W >= (1ll << 29)) return false;
+    if (!sp_descriptors_fit(d, d->H, d->W)) return false;
     if ((long long)kTile * d->H * d->W >= (1 << 27)) return false;
     SpParams& p = pl->p;
     p.B = d->B; p.Ci = d->Ci; p.Co = d->Co; p.H = d->H;
@@ -401,31 +388,16 @@ bool make_sp_plan(const cnn_conv2d_desc* d, SpPlan* pl) {
     pl->ct = d->W == 112 ? 32 : 64;
     pl->gy = (d->Ci + pl->ct - 1) / pl->ct;
     pl->gz = (d->Co + kTile - 1) / kTile;
-    const int env = CNN_OPT_INT("SP_BLOCKS", 0);
-    long long want = (env > 0 ? env : num_cus()) / ((long long)pl->gy * pl->gz);  // one workgroup per CU (LDS)
-    if (want < 1) want = 1;
-    if (want > p.stages_total) want = p.stages_total;
-    p.stages_per_block = (int)((p.stages_total + want - 1) / want);
-    pl->kblocks = (p.stages_total + p.stages_per_block - 1) / p.stages_per_block;
+    sp_partition(p.stages_total, pl->gy, pl->gz, &p.stages_per_block, &pl->kblocks);
     p.dbg = CNN_MEASURE_INT("SP_DBG", 0);
     return true;
 }
 
 template <int W, int RU, bool PAIR, int U, int CT = 64, int PAD = 1>
 int launch_sp(const SpPlan& pl, const cnn_conv2d_desc* d, hipStream_t s) {
-    using G = SpGeom<W, RU, PAIR, U, CT, PAD>;
-    auto kern = wgrad_sp_kernel<W, RU, PAIR, U, CT, PAD>;
-    static DeviceOnce attr_once;
-    if (attr_once.needed()) {
-        CNN_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::lds_bytes));
-        attr_once.mark();
-    }
-    const dim3 grid(pl.kblocks, pl.gy, pl.gz);
     char name[48];
     snprintf(name, sizeof(name), CT == 64 ? "wgrad_sp<%d,%d,%d>" : "wgrad_sp<%d,%d,%d,ct32>", W, RU, U);
-    CNN_KLAUNCH(s, name, (kern<<<grid, 256, G::lds_bytes, s>>>(pl.p)), "B%d Ci%d %dx%d Co%d k3 s1 p%d slabs%d", d->B, d->Ci, d->H, d->W, d->Co, PAD,
-                pl.kblocks);
-    return CNN_AMD_OK;
+    return sp_launch<SpGeom<W, RU, PAIR, U, CT, PAD>>(wgrad_sp_kernel<W, RU, PAIR, U, CT, PAD>, name, pl, d, PAD, s);
 }
 
 }  // namespace

@@ -1,7 +1,8 @@
 // conv_wgrad_sp2.hip -- Conv2D weight / bias gradient (cpu/src/conv2d.cpp:117-159) of 3x3 / STRIDE-2 layers -- the reference's default
 // stride (architectures.h:69; the window walk x += stride at conv2d.cpp:76-77) -- as the stride-2 sibling of conv_wgrad_sp.hip (round 6):
 //     gw[co][ci][kx][ky] = sum_{b,r,c} dy[b][co][r][c] * x[b][ci][2r + kx - p][2c + ky - p]        (bias gradient: sum of dy)
-// Same machine as the stride-1 kernel: an output-stationary 64 (co) x CT (ci) x 9 (taps) tile per workgroup, nine 32x32 accumulators of
+// Same machine as the stride-1 kernel (the shared pieces: wgrad_sp_common.h, lds_dma.h; owned here: Sp2Params, Sp2Geom, the instance table,
+// the planner and the kernel body): an output-stationary 64 (co) x CT (ci) x 9 (taps) tile per workgroup, nine 32x32 accumulators of
 // v_mfma_f32_32x32x2_f32 per wave, both operands staged through LDS by buffer-addressed DMA with out-of-range zero fill, every LDS address
 // one per-lane base + a compile-time immediate, two buffers, one barrier per stage, the DMA of stage s + 1 issued in slices between the
 // MFMAs of stage s, slabs[workgroup][Co][Ci*9 + 1] out (reduce_slabs adds them in a fixed order).
@@ -18,17 +19,11 @@
 //     floats in front of every plane put image row 0 on a unit boundary); the tap column left of the image is the same column for all 64
 //     lanes -- those MFMAs are not issued (CT = 64) or their B value is selected away on the wave that owns the row's first segment
 //     (CT = 32).  Nothing is staged below or right of the image: with an even width 2 (WO - 1) + 1 = W - 1.  Pad 0: no halo at all.
-#include <cstdlib>
 #include <type_traits>
 
-#include "conv_families.h"
-
-using namespace cnn_amd;
+#include "wgrad_sp_common.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
 
 struct Sp2Params {
     const float* x;
@@ -39,13 +34,6 @@ struct Sp2Params {
     int nrb;          // row blocks per sample
     int stages_total, stages_per_block;
 };
-
-constexpr unsigned kOob = 0x80000000u;
-__device__ __forceinline__ void blds16(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, float* lds) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_ptr)lds, 16, (int)voff, (int)soff, 0, 0);
-}
-
-constexpr int kTile = 64;  // output channels per workgroup tile
 
 // W x W planes, padding PAD, RP row pairs per stage, CT input channels per workgroup tile (64: waves 2 (co) x 2 (ci); 32: waves 2 (co) x 2
 // (the two waves of a tile split the segments of a row and are added in the epilogue))
@@ -65,8 +53,6 @@ struct Sp2Geom {
     static constexpr bool RAGGED = HO % ROWS != 0;     // the last stage of a sample has empty row slots
     static constexpr int XROWS = 2 * ROWS + 1;         // staged input rows: 2 r0 - PAD ... 2 r0 - PAD + 2 ROWS
     static constexpr int XLEN = XROWS * W, DLEN = ROWS * WO;
-    // plane strides: a multiple of 4 floats with an odd number of 16-byte pieces
-    static constexpr int stride_for(int len) { return (((len + 3) / 4) & 1) ? (len + 3) / 4 * 4 : (len + 3) / 4 * 4 + 4; }
     static constexpr int LEAD = PAD == 1 ? (4 - W % 4) % 4 : 0;  // image row 0 of the first row block on a 16-byte unit
     static constexpr int XSPAN = LEAD + XLEN;
     static constexpr int QX = stride_for(XSPAN), QD = stride_for(DLEN);
@@ -103,8 +89,8 @@ __global__ __launch_bounds__(256) void wgrad_sp2_kernel(const Sp2Params p) {
     // everything the DMA never writes reads as zero
     for (int i = tid * 4; i < 2 * G::BUF + 4 * 256; i += 1024) *(float4*)(smem + i) = make_float4(0.f, 0.f, 0.f, 0.f);
 
-    const int s_lo = blockIdx.x * p.stages_per_block;
-    const int s_hi = s_lo + p.stages_per_block < p.stages_total ? s_lo + p.stages_per_block : p.stages_total;
+    int s_lo, s_hi;
+    sp_stage_range(p, &s_lo, &s_hi);
 
     // ---- this wave's share of a stage's DMA, decoded once: the lane's byte offset from (channel ci0 / co0, first staged row) of the sample
     //      -- for x counted from PAD*W + 4 floats in front of it, see xrs --, bit 0 set: the unit holds nothing but the halo row above the
@@ -238,7 +224,8 @@ __global__ __launch_bounds__(256) void wgrad_sp2_kernel(const Sp2Params p) {
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the reload behind the last stage)
 
-    // ---- epilogue: the tile goes through LDS in two halves of 32 output channels, then to the slab in whole rows
+    // ---- epilogue: the tile goes through LDS in two halves of 32 output channels, then to the slab in whole rows (the same text in all three
+    //      siblings: wgrad_sp_common.h)
     float* slab = p.slabs + (size_t)blockIdx.x * p.Co * p.pitch;
     float* outs = smem;                 // [32][OP]
     float* bias_s = smem + 32 * G::OP;  // [64]
@@ -317,7 +304,7 @@ bool make_sp2_plan(const cnn_conv2d_desc* d, Sp2Plan* pl) {
     const int min_ch = all ? 1 : 32;  // (small channel counts: the 64 x 64 tile would be mostly padding)
     if (d->Ci < min_ch || d->Co < min_ch) return false;
     const int Ho = (d->H + 2 * d->pad - 3) / 2 + 1;
-    if ((long long)d->B * d->Ci * d->H * d->W >= (1ll << 29) || (long long)d->B * d->Co * Ho * Ho >= (1ll << 29)) return false;
+    if (!sp_descriptors_fit(d, Ho, Ho)) return false;
     Sp2Params& p = pl->p;
     p.B = d->B; p.Ci = d->Ci; p.Co = d->Co;
     p.Ntot = d->Ci * 9; p.pitch = p.Ntot + 1;
@@ -327,31 +314,16 @@ bool make_sp2_plan(const cnn_conv2d_desc* d, Sp2Plan* pl) {
     pl->inst = inst;
     pl->gy = (d->Ci + kInst[inst].ct - 1) / kInst[inst].ct;
     pl->gz = (d->Co + kTile - 1) / kTile;
-    const int env = CNN_OPT_INT("SP_BLOCKS", 0);
-    long long want = (env > 0 ? env : num_cus()) / ((long long)pl->gy * pl->gz);  // one workgroup per CU (LDS)
-    if (want < 1) want = 1;
-    if (want > p.stages_total) want = p.stages_total;
-    p.stages_per_block = (int)((p.stages_total + want - 1) / want);
-    pl->kblocks = (p.stages_total + p.stages_per_block - 1) / p.stages_per_block;
+    sp_partition(p.stages_total, pl->gy, pl->gz, &p.stages_per_block, &pl->kblocks);
     return true;
 }
 
 template <int I>
 int launch_inst(const Sp2Plan& pl, const cnn_conv2d_desc* d, hipStream_t s) {
     constexpr Sp2Inst c = kInst[I];
-    using G = Sp2Geom<c.w, c.pad, c.rp, c.ct>;
-    auto kern = wgrad_sp2_kernel<c.w, c.pad, c.rp, c.ct>;
-    static DeviceOnce attr_once;
-    if (attr_once.needed()) {
-        CNN_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::lds_bytes));
-        attr_once.mark();
-    }
-    const dim3 grid(pl.kblocks, pl.gy, pl.gz);
     char name[48];
     snprintf(name, sizeof(name), "wgrad_sp2<%d,%d,%d,ct%d>", c.w, c.pad, c.rp, c.ct);
-    CNN_KLAUNCH(s, name, (kern<<<grid, 256, G::lds_bytes, s>>>(pl.p)), "B%d Ci%d %dx%d Co%d k3 s2 p%d slabs%d", d->B, d->Ci, d->H, d->W, d->Co, c.pad,
-                pl.kblocks);
-    return CNN_AMD_OK;
+    return sp_launch<Sp2Geom<c.w, c.pad, c.rp, c.ct>>(wgrad_sp2_kernel<c.w, c.pad, c.rp, c.ct>, name, pl, d, c.pad, s);
 }
 
 template <int... I>

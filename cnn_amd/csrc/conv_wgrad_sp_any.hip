@@ -3,7 +3,8 @@
 //     gw[co][ci][kx][ky] = sum_{b,r,c} dy[b][co][r][c] * x[b][ci][r + kx - p][c + ky - p]        (bias gradient: sum of dy)
 // conv_wgrad_sp.hip is instantiated for the plane widths of the BASELINE workloads (7 / 14 / 28 / 56 / 112: left / right halves of a row or
 // sample pairs on the two k-slots, rows of whole 7-pixel segments); every other 3x3 / stride-1 geometry ran on the register-direct kernel
-// (67 - 108 TFLOP/s on the reference's own pad-0 VGG shapes at batch 128).  Same machine here -- a 64 (co) x 64 (ci) x 9 (taps) tile per
+// (67 - 108 TFLOP/s on the reference's own pad-0 VGG shapes at batch 128).  Same machine here (the shared pieces: wgrad_sp_common.h,
+// lds_dma.h; owned here: SpaParams, SpaGeom, the planner and the kernel body) -- a 64 (co) x 64 (ci) x 9 (taps) tile per
 // workgroup, nine 32x32 accumulators of v_mfma_f32_32x32x2_f32 per wave, both operands staged through LDS by buffer-addressed DMA, two
 // buffers, one barrier per stage, the DMA of stage s + 1 issued between the MFMAs of stage s, slabs out -- with NO plane size in any address
 // computation of the loop:
@@ -15,17 +16,11 @@
 //     the tail of the unit that straddles the end, which the lane that issued it overwrites once its DMA has landed (conv_rows_any.hip).
 //     A delta of zero contributes nothing: no lane masks, no selects, no padding- or size-dependent code between the MFMAs.
 // The planner picks CW by the fewest staged pixels per live pixel (21-wide outputs: one block of 21; 220-wide: eight of 28).
-#include <cstdlib>
 #include <type_traits>
 
-#include "conv_families.h"
-
-using namespace cnn_amd;
+#include "wgrad_sp_common.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
 
 struct SpaParams {
     const float* x;
@@ -37,13 +32,7 @@ struct SpaParams {
     int stages_total, stages_per_block;
 };
 
-constexpr unsigned kOob = 0x80000000u;
-__device__ __forceinline__ void blds16(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, float* lds) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_ptr)lds, 16, (int)voff, (int)soff, 0, 0);
-}
-
-constexpr int kTile = 64;  // channels per workgroup tile, both ways (waves 2 x 2)
-constexpr int kLeft = 4;   // floats the staged x window starts left of its column block (one DMA unit)
+constexpr int kLeft = 4;  // floats the staged x window starts left of its column block (one DMA unit)
 
 template <int CW>
 struct SpaGeom {
@@ -53,8 +42,6 @@ struct SpaGeom {
     static constexpr int XW = (kLeft + CW + 2 + 3) / 4 * 4;     // staged x row: columns c0 - 4 ... c0 + CW + 1 (+ slack)
     static constexpr int DROWS = 2, XROWS = 4;
     static constexpr int DLEN = DROWS * DP, XLEN = XROWS * XW;
-    // plane strides: a multiple of 4 floats with an odd number of 16-byte pieces
-    static constexpr int stride_for(int len) { return (((len + 3) / 4) & 1) ? (len + 3) / 4 * 4 : (len + 3) / 4 * 4 + 4; }
     static constexpr int QD = stride_for(DLEN), QX = stride_for(XLEN);
     static constexpr int PPD = QD / 4, PPX = QX / 4;            // 16-byte pieces per plane
     static constexpr int UPD = DP / 4, UPX = XW / 4;            // ... per staged row
@@ -86,8 +73,8 @@ __global__ __launch_bounds__(256) void wgrad_spa_kernel(const SpaParams p) {
 
     for (int i = tid * 4; i < 2 * G::BUF + 4 * 256; i += 1024) *(float4*)(smem + i) = make_float4(0.f, 0.f, 0.f, 0.f);
 
-    const int s_lo = blockIdx.x * p.stages_per_block;
-    const int s_hi = s_lo + p.stages_per_block < p.stages_total ? s_lo + p.stages_per_block : p.stages_total;
+    int s_lo, s_hi;
+    sp_stage_range(p, &s_lo, &s_hi);
 
     // ---- this wave's share of a stage's DMA, decoded once: 16-byte unit q of an image = (plane, staged row, unit of the row); the lane's
     //      byte offset from the stage's first element, its row and its first column inside the window (-1: nothing to move)
@@ -267,7 +254,7 @@ __global__ __launch_bounds__(256) void wgrad_spa_kernel(const SpaParams p) {
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the reload behind the last stage)
 
-    // ---- epilogue: the tile goes through LDS in two halves of 32 output channels, then to the slab in whole rows (conv_wgrad_sp.hip)
+    // ---- epilogue: the tile goes through LDS in two halves of 32 output channels, then to the slab in whole rows (the same text in all three siblings: wgrad_sp_common.h)
     float* slab = p.slabs + (size_t)blockIdx.x * p.Co * p.pitch;
     float* outs = smem;                 // [32][OP]
     float* bias_s = smem + 32 * G::OP;  // [64]
@@ -314,7 +301,7 @@ bool make_spa_plan(const cnn_conv2d_desc* d, SpaPlan* pl) {
     // (output rows of whole 16-pixel runs are the register-direct kernel's best case: measured at batch 128 / 64, 48-wide outputs: 107 / 87
     //  TFLOP/s there against 96 / 87 here -- everywhere else this kernel wins by 9 - 33 %)
     if (!forced && Wo % 16 == 0) return false;
-    if ((long long)d->B * d->Ci * d->H * d->W >= (1ll << 29) || (long long)d->B * d->Co * Ho * Wo >= (1ll << 29)) return false;
+    if (!sp_descriptors_fit(d, Ho, Wo)) return false;
     if ((long long)kTile * d->H * d->W >= (1 << 27)) return false;
     SpaParams& p = pl->p;
     p.B = d->B; p.Ci = d->Ci; p.Co = d->Co; p.H = d->H; p.W = d->W; p.HO = Ho; p.WO = Wo; p.pad = d->pad;
@@ -329,30 +316,15 @@ bool make_spa_plan(const cnn_conv2d_desc* d, SpaPlan* pl) {
     p.stages_total = (int)stages;
     pl->gy = (d->Ci + kTile - 1) / kTile;
     pl->gz = (d->Co + kTile - 1) / kTile;
-    const int env = CNN_OPT_INT("SP_BLOCKS", 0);
-    long long want = (env > 0 ? env : num_cus()) / ((long long)pl->gy * pl->gz);  // one workgroup per CU (LDS)
-    if (want < 1) want = 1;
-    if (want > p.stages_total) want = p.stages_total;
-    p.stages_per_block = (int)((p.stages_total + want - 1) / want);
-    pl->kblocks = (p.stages_total + p.stages_per_block - 1) / p.stages_per_block;
+    sp_partition(p.stages_total, pl->gy, pl->gz, &p.stages_per_block, &pl->kblocks);
     return true;
 }
 
 template <int CW>
 int launch_spa(const SpaPlan& pl, const cnn_conv2d_desc* d, hipStream_t s) {
-    using G = SpaGeom<CW>;
-    auto kern = wgrad_spa_kernel<CW>;
-    static DeviceOnce attr_once;
-    if (attr_once.needed()) {
-        CNN_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::lds_bytes));
-        attr_once.mark();
-    }
-    const dim3 grid(pl.kblocks, pl.gy, pl.gz);
     char name[48];
     snprintf(name, sizeof(name), "wgrad_sp_any<2x%d>", CW);
-    CNN_KLAUNCH(s, name, (kern<<<grid, 256, G::lds_bytes, s>>>(pl.p)), "B%d Ci%d %dx%d Co%d k3 s1 p%d slabs%d", d->B, d->Ci, d->H, d->W, d->Co, d->pad,
-                pl.kblocks);
-    return CNN_AMD_OK;
+    return sp_launch<SpaGeom<CW>>(wgrad_spa_kernel<CW>, name, pl, d, d->pad, s);
 }
 
 }  // namespace

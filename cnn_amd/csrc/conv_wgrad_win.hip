@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "conv_families.h"
+#include "lds_dma.h"
 
 using namespace cnn_amd;
 
@@ -38,7 +39,6 @@ __device__ unsigned long long g_prof[256 * 8][8];
 #endif
 constexpr int kExp = CNN_WIN_EXPERIMENT;  // timing experiments only (3: no LDS operand reads, 4: no MFMAs); 0 in the product
 
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
 typedef const __attribute__((address_space(1))) void* gbl_void_ptr;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -659,11 +659,7 @@ template <int POOLED, bool DMA16, bool SPEC>
 int launch_win3(const cnn_conv2d_desc* d, WinParams& p, int grid, hipStream_t s, const char* name) {
     const size_t lds_bytes = (size_t)kWaves * num_bufs(POOLED) * buf_floats(POOLED) * sizeof(float) + (SPEC ? 256 : 0);
     static DeviceOnce attr_once;  // (per template instance)
-    if (attr_once.needed()) {
-        CNN_HIP_CHECK(hipFuncSetAttribute((const void*)conv_wgrad_win_kernel<POOLED, DMA16, SPEC>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)lds_bytes));
-        attr_once.mark();
-    }
+    if (int rc = allow_dynamic_lds(attr_once, (int)lds_bytes, conv_wgrad_win_kernel<POOLED, DMA16, SPEC>)) return rc;
     constexpr int threads = (kWaves + (SPEC ? kProd : 0)) * 64;
     CNN_KLAUNCH(s, name, (conv_wgrad_win_kernel<POOLED, DMA16, SPEC><<<grid, threads, lds_bytes, s>>>(p)), CONV_TAG(d));
 #if CNN_WIN_EXPERIMENT == 6

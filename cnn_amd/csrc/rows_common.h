@@ -1,22 +1,15 @@
 // rows_common.h -- device helpers shared by the LDS-staged row kernels (conv_rows.hip: stride 1; conv_rows_s2.hip: stride 2): 16-byte
-// buffer-addressed LDS DMA, the in-place accumulating 16x16x4 fp32 MFMA as inline assembly, and the filter-image job both prepare with.
+// buffer-addressed LDS DMA (lds_dma.h), the in-place accumulating 16x16x4 fp32 MFMA as inline assembly, and the filter-image job both prepare with.
 #pragma once
 #include <type_traits>
 #include <utility>
 
-#include "common.h"
+#include "lds_dma.h"
 
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));  // a 16-byte access at any float address
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
-
-constexpr unsigned kOob = 0x80000000u;
-__device__ __forceinline__ void blds16(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, float* lds) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_ptr)lds, 16, (int)voff, (int)soff, 0, 0);
-}
-
 // The accumulating MFMA as inline assembly, destination = addend, both in AGPRs.  Through the builtin the register allocator is free to
 // give the result another register than the addend; across the unrolled stage loop that ended in a rotation of the whole accumulator file
 // at every back edge (~100 v_accvgpr_mov / read / write per stage in the round-5 ISA, 10 - 15 % of a stage).  What the compiler's hazard
