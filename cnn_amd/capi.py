@@ -161,6 +161,7 @@ SIGNATURES = {
     "cnn_adam_update": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.POINTER(AdamOptions), C.c_float, _P, _P, C.c_size_t, _P, _P]),
     "cnn_clip_grad_norm_workspace_bytes": (C.c_size_t, [C.c_size_t]),
     "cnn_clip_grad_norm": (C.c_int, [_P, C.c_size_t, C.c_float, C.c_float, _P, C.c_size_t, _P, _P]),
+    "cnn_grad_accumulate": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P]),
     "cnn_layerwise_create": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_void_p)]),
     "cnn_layerwise_destroy": (C.c_int, [_P]),
     "cnn_layerwise_stats": (C.c_int, [_P, C.POINTER(C.c_void_p)]),
@@ -762,6 +763,14 @@ def clip_grad_norm(grads, max_norm, grad_scale=1.0, n=None):
           "cnn_clip_grad_norm")
     torch.cuda.current_stream().synchronize()  # (the workspace must outlive the kernels that use it)
     return stats
+
+
+def grad_accumulate(acc, grads, first, n=None):
+    """cnn_grad_accumulate on device tensors (or views of them): acc = grads (first: a copy of the bits) or acc += grads"""
+    _need_gpu(acc, grads)
+    n = acc.numel() if n is None else int(n)
+    check(load().cnn_grad_accumulate(_ptr(acc), _ptr(grads), n, 1 if first else 0, _stream()), "cnn_grad_accumulate")
+    return acc
 
 
 class Layerwise:

@@ -1,5 +1,6 @@
 // elementwise.hip -- HBM-bound streaming kernels: ReLU fwd/bwd (relu.cpp:21-26,35-40), the SGD step
-// (conv2d.cpp:205-217, linear.cpp:95-102) and the softmax / cross-entropy glue (func.cpp:16-73).
+// (conv2d.cpp:205-217, linear.cpp:95-102), the optimizer steps, the clip and the gradient accumulation on the flat arena (additions), and
+// the softmax / cross-entropy glue (func.cpp:16-73).
 // All are 16 B/lane vectorised grid-stride loops; roofline = HBM (8 / 12 / 12 B per element).
 #include <cfloat>
 #include <cstdint>
@@ -90,6 +91,35 @@ __global__ __launch_bounds__(kBlock) void sgd_scalar(float* __restrict__ p, cons
         if (keep) keep[i] = p[i];
         p[i] = sgd_one(p[i], g[i], lr, scale, scaled);
     }
+}
+
+// ---- gradient accumulation over micro-batches (cnn_grad_accumulate) ----------------------------------------------------------------
+// sgd_vec's shape: float4 body, the <= 3 trailing elements in workgroup 0, a scalar kernel for unaligned pointers.  kFirst opens a
+// window: acc = g, loads and stores only (every bit pattern survives, acc is not read: 8 B per element); otherwise acc = acc + g,
+// one fp32 add per element (12 B per element).
+template <bool kFirst>
+__global__ __launch_bounds__(kBlock) void gacc_vec(float4* __restrict__ acc, const float4* __restrict__ g, size_t n4, size_t n) {
+    if (blockIdx.x == 0 && n4 * 4 + threadIdx.x < n) {
+        float* as = (float*)acc;
+        const float* gs = (const float*)g;
+        const size_t i = n4 * 4 + threadIdx.x;
+        as[i] = kFirst ? gs[i] : as[i] + gs[i];
+    }
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (size_t)gridDim.x * kBlock) {
+        const float4 gv = g[i];
+        if (kFirst) {
+            acc[i] = gv;
+        } else {
+            float4 av = acc[i];
+            av.x = av.x + gv.x; av.y = av.y + gv.y; av.z = av.z + gv.z; av.w = av.w + gv.w;
+            acc[i] = av;
+        }
+    }
+}
+template <bool kFirst>
+__global__ __launch_bounds__(kBlock) void gacc_scalar(float* __restrict__ acc, const float* __restrict__ g, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock)
+        acc[i] = kFirst ? g[i] : acc[i] + g[i];
 }
 
 // ---- SGD with momentum / weight decay / Nesterov (cnn_sgd_momentum_update; sgdm_one(): common.h) -----------------------------
@@ -615,6 +645,30 @@ int cnn_sgd_update_keep(float* params, const float* grads, size_t n, float lr, f
         CNN_KLAUNCH(s, "sgd_scalar",
                     (sgd_scalar<<<stream_grid(n - done, kBlock), kBlock, 0, s>>>(params, grads, done, n, lr, grad_scale, scaled, previous)),
                     "tail n=%zu", n - done);
+    }
+    return CNN_AMD_OK;
+}
+
+int cnn_grad_accumulate(float* acc, const float* grads, size_t n, int first, void* stream) {
+    CNN_REQUIRE(acc && grads, "cnn_grad_accumulate: null pointer");
+    CNN_REQUIRE(n != 0, "cnn_grad_accumulate: n=0");
+    CNN_REQUIRE(acc != grads, "cnn_grad_accumulate: acc and grads are the same buffer");
+    hipStream_t s = as_stream(stream);
+    if (aligned16(acc) && aligned16(grads) && n >= 4) {
+        const size_t n4 = n / 4;
+        const unsigned grid = stream_grid(n4, kBlock);
+        if (first) {
+            CNN_KLAUNCH(s, "gacc_vec_first", (gacc_vec<true><<<grid, kBlock, 0, s>>>((float4*)acc, (const float4*)grads, n4, n)), "n=%zu", n);
+        } else {
+            CNN_KLAUNCH(s, "gacc_vec_add", (gacc_vec<false><<<grid, kBlock, 0, s>>>((float4*)acc, (const float4*)grads, n4, n)), "n=%zu", n);
+        }
+    } else {
+        const unsigned grid = stream_grid(n, kBlock);
+        if (first) {
+            CNN_KLAUNCH(s, "gacc_scalar_first", (gacc_scalar<true><<<grid, kBlock, 0, s>>>(acc, grads, n)), "tail n=%zu", n);
+        } else {
+            CNN_KLAUNCH(s, "gacc_scalar_add", (gacc_scalar<false><<<grid, kBlock, 0, s>>>(acc, grads, n)), "tail n=%zu", n);
+        }
     }
     return CNN_AMD_OK;
 }

@@ -453,7 +453,8 @@ public:
 //     normalise over the GLOBAL batch (sync-BN) and update_gradients() sums the gradient arena over the replicas first;
 //   * an optional optimizer on the arena instead of the reference's w -= lr * g -- one of momentum SGD (set_optimizer), Adam / AdamW
 //     (set_adam), LAMB (set_lamb), LARS (set_lars); the setter called last is the active kind (OptKind, optimizer.cpp);
-//   * clipping by the global gradient norm (set_grad_clip) in front of whichever step is active.
+//   * clipping by the global gradient norm (set_grad_clip) in front of whichever step is active;
+//   * gradient accumulation over micro-batches (set_grad_accumulation): k container steps, one optimizer step on their summed gradients.
 class Sequential {
 public:
     bool print_info = false;
@@ -553,8 +554,8 @@ protected:
         std::vector<uint32_t> seg_bounds, seg_flags;   // ... and the segment table it was created from (host copy)
     } opt;
     // what every setter starts with: finalized and the 32-bit table limit (deliberately checked in every build, not asserts: they abort
-    // with the setter's name), flush_deferred, synchronize
-    void begin_optimizer_switch(const char* setter);
+    // with the setter's name), flush_deferred, synchronize.  (set_grad_accumulation builds no table: its kernel's indices are 64-bit)
+    void begin_optimizer_switch(const char* setter, bool builds_32bit_table = true);
     const DecayTable& decay_table_of(size_t lo, size_t hi) const;  // the table built for exactly this range; aborts when there is none
     void ensure_state_arena(data_type*& arena);
     void build_decay_table(DecayTable& t, size_t lo, size_t hi, bool bias_and_norm);
@@ -567,6 +568,18 @@ protected:
     size_t clip_workspace_bytes = 0;
     data_type* clip_stats = nullptr;   // [2] on the device: total norm, coefficient of the latest clipped step
     size_t front_block_params() const;
+    // ---- gradient accumulation over micro-batches (set_grad_accumulation): orthogonal to the kind and to clipping ----
+    int accum_k = 1;                   // micro-batches per window; 1: off
+    int accum_phase = 0;               // micro-batches in the open window, 0 .. accum_k - 1
+    data_type* accum_grads = nullptr;  // n_params floats, owned by the container whoever owns the arenas
+    // the gradients the exchange, the clip and the step read: the ONE place that decides between the arena and the accumulator
+    data_type* step_grads() const { return accum_k > 1 ? accum_grads : grad_arena; }
+    // accum_k > 1: counts this container step as one micro-batch -- flush_deferred, ONE cnn_grad_accumulate on the compute stream.
+    // true: the call closes the window (the exchange over the accumulator has run, the caller clips and steps); false: it returns
+    bool count_micro_batch();
+    void exchange_grads(data_type* grads);  // the event-fenced all-reduce of n_params gradients on the communication stream
+    // the tail of every container step: [the clip,] the active kind's step over the whole arena reading step_grads(), the snapshot
+    void clip_and_step(data_type learning_rate, data_type grad_scale);
     // the step of the active kind on arena[lo, hi) (parameters, gradients, state, snapshot) on `on_stream`: the ONE dispatch on opt_kind.
     // kSgdm / kAdam step the three ranges decay tables exist for; kLamb / kLars the whole arena only.
     void step_arena(size_t lo, size_t hi, data_type learning_rate, data_type grad_scale, void* on_stream);
@@ -622,6 +635,8 @@ public:
     // of them and activates the optimizer the file was written for.  Both return 0 on success.  save: 1 = cannot write, 4 = no
     // optimizer was ever set.  load: 1 = cannot open, 2 = not such a file / truncated / options out of range, 3 = written for another
     // n_params; nothing is changed on failure, on success the file's options are set as by the setter, then its arenas and step counter.
+    // An open accumulation window (set_grad_accumulation) is NOT part of the file -- neither the accumulator nor the phase nor k:
+    // save at a window boundary (accumulation_phase() == 0), or the micro-batches of the open window are to be run again after a load.
     int save_optimizer_state(const std::filesystem::path& path);
     int load_optimizer_state(const std::filesystem::path& path);
 
@@ -676,6 +691,27 @@ public:
     // w_norm, u_norm, ratio of the latest layer-wise step (segment_count() values each); like last_grad_norm() it synchronises.
     // false: no layer-wise optimizer was ever set.
     bool trust_stats(std::vector<data_type>& w_norm, std::vector<data_type>& u_norm, std::vector<data_type>& ratio);
+
+    // Gradient accumulation: a window of micro_steps micro-batches counts as ONE optimizer step on their summed gradients -- the large
+    // batch activation memory does not allow.  micro_steps >= 1; 1 (the default) switches it off.  Call it after finalize(), any number
+    // of times: the first micro_steps > 1 allocates the accumulator (num_params() floats, owned by the container also where the caller
+    // provided the arenas, kept until the container goes).  Calling it with a window open discards that window.
+    // With micro_steps = k > 1 every container step -- update_gradients(lr), update_gradients(lr, grad_scale), train_step -- counts one
+    // micro-batch: flush_deferred(), then one cnn_grad_accumulate of the gradient arena into the accumulator (a copy of the bits when
+    // it opens the window, one fp32 add per element afterwards).  Calls 1 .. k-1 return there: no parameter, optimizer state or step
+    // counter moves, lr is ignored, get_output() stays valid; only BatchNorm2D's moving statistics move, with every forward pass as
+    // always.  Call k closes the window: the exchange when a communicator is set (ONE all-reduce over the accumulator; the bucketed
+    // exchange inside backward() is off and allreduce_gradients() a no-op while k > 1), the clip when it is on, then the active
+    // kind's step -- all three read the accumulator.  Its gradient scale is 1 / (k * world) in the one-argument form and
+    // grad_scale / k in the two-argument form; the Adam / LAMB step counter advances once per window and last_grad_norm() reports the
+    // accumulated gradient's norm.  THE PRICE: the front block's in-kernel SGD step would move parameters in the middle of a window,
+    // so the fused step tail (fused_tail) declines while k > 1, as under clipping, and every micro-batch adds one streaming pass over
+    // the arena.  With k = 1 nothing changes, not one launch.  The state files do not carry an open window (see below).  Stand-alone
+    // Layer::update_gradients and a non-finalized list never accumulate.
+    void set_grad_accumulation(int micro_steps);
+    int grad_accumulation() const { return accum_k; }
+    int accumulation_phase() const { return accum_phase; }                 // micro-batches in the open window, 0 .. k-1
+    data_type* accumulated_grads_device() const { return accum_grads; }    // null before the first micro_steps > 1
 
 protected:
     void invalidate_filter_images();  // (the part of parameters_changed() the container's own SGD step needs too)

@@ -176,6 +176,17 @@ int cnnh_net_last_grad_norm(void* hv, float* norm_out, float* coef_out) {  // 1:
     if (coef_out) *coef_out = coef;
     return 0;
 }
+// Sequential::set_grad_accumulation: k micro-batches per optimizer step (1: off), the open window's length, the accumulator
+void cnnh_net_set_grad_accumulation(void* hv, int micro_steps) { ((Handle*)hv)->net->set_grad_accumulation(micro_steps); }
+int cnnh_net_accumulation_phase(void* hv) { return ((Handle*)hv)->net->accumulation_phase(); }
+int cnnh_net_get_accumulated_grads(void* hv, float* host) {  // 1: accumulation was never on
+    Handle* h = (Handle*)hv;
+    if (h->net->accumulated_grads_device() == nullptr) return 1;
+    h->net->flush_deferred();
+    must(cnn_memcpy_d2h(host, h->net->accumulated_grads_device(), sizeof(float) * h->net->num_params(), stream), "cnn_memcpy_d2h");
+    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
+    return 0;
+}
 int cnnh_net_save_optimizer_state(void* hv, const char* path) { return ((Handle*)hv)->net->save_optimizer_state(path); }
 int cnnh_net_load_optimizer_state(void* hv, const char* path) { return ((Handle*)hv)->net->load_optimizer_state(path); }
 void cnnh_set_stream(void* hip_stream) { architectures::stream = hip_stream; }

@@ -1,7 +1,7 @@
 // optimizer.cpp -- the optimizer of architectures::Sequential (member functions; the class is in architectures.h): ONE kind
 // (OptKind) says which step the container takes on its flat arena, every kind has its options struct, all kinds share one block of
 // state (OptState), and the state files are one writer and one reader over a table of formats.  Clipping by the global gradient norm
-// is orthogonal to the kind and sits at the end.
+// is orthogonal to the kind and sits at the end, with the setter of gradient accumulation over micro-batches.
 #include <algorithm>
 #include <cassert>
 #include <cstddef>
@@ -136,12 +136,12 @@ bool moment_options_ok(data_type beta1, data_type beta2, data_type eps, data_typ
 }
 }  // namespace
 
-void Sequential::begin_optimizer_switch(const char* setter) {
+void Sequential::begin_optimizer_switch(const char* setter, const bool builds_32bit_table) {
     if (!finalized) {
         std::fprintf(stderr, "cnn_amd host: %s works on the flat arena: call finalize() first\n", setter);
         std::abort();
     }
-    if (n_params >= ((size_t)1 << 32) - 1024) {
+    if (builds_32bit_table && n_params >= ((size_t)1 << 32) - 1024) {
         std::fprintf(stderr, "cnn_amd host: %s: the decay-range / segment tables are 32-bit, the arena has %zu parameters\n", setter, n_params);
         std::abort();
     }
@@ -211,7 +211,7 @@ const Sequential::DecayTable& Sequential::decay_table_of(const size_t lo, const 
 void Sequential::step_arena(const size_t lo, const size_t hi, const data_type learning_rate, const data_type grad_scale, void* on_stream) {
     if (hi <= lo) return;
     const size_t n = hi - lo;
-    data_type *p = param_arena + lo, *g = grad_arena + lo, *prev = param_prev + lo;
+    data_type *p = param_arena + lo, *g = step_grads() + lo, *prev = param_prev + lo;
     switch (opt_kind) {
         case OptKind::kPlain:  // the reference's w -= lr * g
             must(cnn_sgd_update_keep(p, g, n, learning_rate, grad_scale, prev, on_stream), "cnn_sgd_update_keep");
@@ -427,6 +427,20 @@ void Sequential::set_grad_clip(const data_type max_norm) {
         must(cnn_memset_zero(clip_stats, sizeof(data_type) * 2, stream), "cnn_memset_zero");
     }
     clip_max_norm = max_norm;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// gradient accumulation over micro-batches: which gradients the exchange, the clip and the step read (step_grads()), and how many
+// container steps make one of them (count_micro_batch(), sequential.cpp)
+void Sequential::set_grad_accumulation(const int micro_steps) {
+    if (micro_steps < 1) {
+        std::fprintf(stderr, "cnn_amd host: set_grad_accumulation: micro_steps=%d, at least 1 (1 = off)\n", micro_steps);
+        std::abort();
+    }
+    begin_optimizer_switch("set_grad_accumulation", /*builds_32bit_table=*/false);
+    if (micro_steps > 1) ensure_state_arena(accum_grads);  // (zeroed once; a window's first micro-batch overwrites it)
+    accum_k = micro_steps;
+    accum_phase = 0;  // (an open window is discarded)
 }
 
 data_type Sequential::last_grad_norm(data_type* coef_out) {

@@ -182,6 +182,7 @@ Sequential::~Sequential() {
     if (opt.exp_avg_sq) cnn_device_free(opt.exp_avg_sq);
     if (clip_workspace) cnn_device_free(clip_workspace);
     if (clip_stats) cnn_device_free(clip_stats);
+    if (accum_grads) cnn_device_free(accum_grads);
     if (opt.layerwise) cnn_layerwise_destroy(opt.layerwise);
     if (opt.lamb_update) cnn_device_free(opt.lamb_update);
     for (auto& t : opt.decay_tables)
@@ -299,7 +300,8 @@ void Sequential::backward(std::vector<tensor>& delta_start) {
     if (print_info) delta_start[0]->print_shape();
     flush_deferred();
     const bool force_buckets = cnn_amd_get_option("DP_FORCE_BUCKETS", nullptr, 0) == 0;  // (tests: exercise the path with one rank)
-    const bool bucketed = finalized && comm != nullptr && (comm_world > 1 || force_buckets) && n_params >= 2 * bucket_floats;
+    // (not inside an accumulation window: its closing call exchanges the accumulator once)
+    const bool bucketed = finalized && comm != nullptr && (comm_world > 1 || force_buckets) && n_params >= 2 * bucket_floats && accum_k == 1;
     size_t pending_hi = n_params, idx = layers_sequence.size();
     for (auto layer = layers_sequence.rbegin(); layer != layers_sequence.rend(); ++layer) {
         delta_start = (*layer)->backward(delta_start);
@@ -413,23 +415,42 @@ bool Sequential::exchange_active() const {
     return comm_world > 1 || cnn_amd_get_option("DP_FORCE_EXCHANGE", nullptr, 0) == 0;
 }
 
-void Sequential::allreduce_gradients() {
-    if (!exchange_active() || grads_reduced) return;
-    assert(finalized && "data parallelism needs the flat gradient arena: call finalize()");
+void Sequential::exchange_grads(data_type* grads) {
     must(cnn_event_record(ev_grads, stream), "cnn_event_record");
     must(cnn_stream_wait_event(comm_stream, ev_grads), "cnn_stream_wait_event");
-    must(cnn_allreduce_grads(comm, grad_arena, n_params, comm_stream), "cnn_allreduce_grads");
+    must(cnn_allreduce_grads(comm, grads, n_params, comm_stream), "cnn_allreduce_grads");
     must(cnn_event_record(ev_comm, comm_stream), "cnn_event_record");
     cnn_amd_timing_span_begin(stream, "span:exchange_wait");
     must(cnn_stream_wait_event(stream, ev_comm), "cnn_stream_wait_event");
     cnn_amd_timing_span_end(stream);
+}
+
+void Sequential::allreduce_gradients() {
+    if (accum_k > 1) return;  // (a micro-batch's gradients are not exchanged: the closing call of the window exchanges the accumulator)
+    if (!exchange_active() || grads_reduced) return;
+    assert(finalized && "data parallelism needs the flat gradient arena: call finalize()");
+    exchange_grads(grad_arena);
     grads_reduced = true;
+}
+
+// gradient accumulation: this container step is one micro-batch of the window
+bool Sequential::count_micro_batch() {
+    flush_deferred();
+    if (n_params > 0) must(cnn_grad_accumulate(accum_grads, grad_arena, n_params, accum_phase == 0 ? 1 : 0, stream), "cnn_grad_accumulate");
+    if (++accum_phase < accum_k) return false;
+    accum_phase = 0;
+    if (exchange_active()) exchange_grads(accum_grads);  // ONE exchange per window, behind its last accumulate
+    return true;
 }
 
 void Sequential::update_gradients(const data_type learning_rate) {
     flush_deferred();
     if (!finalized) {  // plain list of stand-alone layers: the reference's loop (alexnet.cpp:62-65)
         for (auto& layer : layers_sequence) layer->update_gradients(learning_rate);
+        return;
+    }
+    if (accum_k > 1) {  // the sum of k micro-batches over `world` replicas -> their mean
+        if (count_micro_batch()) clip_and_step(learning_rate, 1.f / (data_type)(accum_k * comm_world));
         return;
     }
     if (exchange_active()) {
@@ -442,11 +463,19 @@ void Sequential::update_gradients(const data_type learning_rate) {
 
 void Sequential::update_gradients(const data_type learning_rate, const data_type grad_scale) {
     assert(finalized && "the grad_scale form works on the flat arena: call finalize()");
+    if (accum_k > 1) {  // (grad_scale is the caller's 1/G for ONE pass; the window summed k of them)
+        if (count_micro_batch()) clip_and_step(learning_rate, grad_scale / (data_type)accum_k);
+        return;
+    }
+    clip_and_step(learning_rate, grad_scale);
+}
+
+void Sequential::clip_and_step(const data_type learning_rate, const data_type grad_scale) {
     // (the old values go to the snapshot: Conv2D::get_output() of a fused-away tensor re-computes it with them)
     if (params_stepped)  // a second step without a forward pass in between: the snapshot would now receive already-stepped values
         for (auto& layer : layers_sequence) layer->params_of_last_forward_lost();
     if (clip_max_norm > 0 && n_params > 0)  // (behind the all-reduce, in front of the step; the step applies grad_scale to the clipped values)
-        must(cnn_clip_grad_norm(grad_arena, n_params, clip_max_norm, grad_scale, clip_workspace, clip_workspace_bytes, clip_stats, stream),
+        must(cnn_clip_grad_norm(step_grads(), n_params, clip_max_norm, grad_scale, clip_workspace, clip_workspace_bytes, clip_stats, stream),
              "cnn_clip_grad_norm");
     if (step_uses_adam_moments()) ++opt.step;
     step_arena(0, n_params, learning_rate, grad_scale, stream);  // (optimizer.cpp: the dispatch on the active kind)
@@ -484,6 +513,7 @@ bool Sequential::fused_tail(std::vector<tensor>& delta, const data_type learning
     if (cnn_amd_get_option("NO_FUSED_TAIL", nullptr, 0) == 0) return false;  // (A/B switch)
     if (clip_max_norm > 0) return false;  // (the norm needs every gradient of the step before any parameter moves: the plain sequence)
     if (step_needs_whole_tensors()) return false;  // (so does a trust ratio: every gradient of a tensor before that tensor moves)
+    if (accum_k > 1) return false;  // (the block's in-kernel step would move parameters in the middle of a window: the plain sequence)
     const size_t lo = front_block_params();  // the block's convolution owns arena[0, lo)
     const bool dp = exchange_active();
     const data_type scale = dp ? 1.f / (data_type)comm_world : 1.f;

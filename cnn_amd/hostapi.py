@@ -48,6 +48,9 @@ SIGNATURES = {
     "cnnh_net_get_segments": (None, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cnnh_net_get_trust_stats": (C.c_int, [C.c_void_p, _F, _F, _F]),
     "cnnh_net_last_grad_norm": (C.c_int, [C.c_void_p, _F, _F]),
+    "cnnh_net_set_grad_accumulation": (None, [C.c_void_p, C.c_int]),
+    "cnnh_net_accumulation_phase": (C.c_int, [C.c_void_p]),
+    "cnnh_net_get_accumulated_grads": (C.c_int, [C.c_void_p, _F]),
     "cnnh_net_save_optimizer_state": (C.c_int, [C.c_void_p, C.c_char_p]),
     "cnnh_net_load_optimizer_state": (C.c_int, [C.c_void_p, C.c_char_p]),
     "cnnh_set_stream": (None, [C.c_void_p]),
@@ -237,6 +240,25 @@ class HostNet:
         if self.lib.cnnh_net_get_trust_stats(self.h, _fp(w), _fp(u), _fp(r)) != 0:
             raise capi.CnnAmdError("trust_stats before set_lamb / set_lars")
         return w[:ns], u[:ns], r[:ns]
+
+    def set_grad_accumulation(self, micro_steps):
+        """Sequential::set_grad_accumulation: every later container step counts one micro-batch, the optimizer steps once per
+        micro_steps of them on their summed gradients (1: off); an open window is discarded.  No fused step tail while it is on."""
+        if int(micro_steps) < 1:
+            raise capi.CnnAmdError(f"set_grad_accumulation({micro_steps}): at least 1")
+        self.lib.cnnh_net_set_grad_accumulation(self.h, int(micro_steps))
+
+    def accumulation_phase(self):
+        """micro-batches in the open window, 0 .. micro_steps - 1"""
+        return int(self.lib.cnnh_net_accumulation_phase(self.h))
+
+    def get_accumulated_grads(self):
+        """the accumulator on the host: the sum over the open window's micro-batches -- after a closing call the closed window's sum,
+        clipped when clipping is on"""
+        out = np.empty(self.n_params, np.float32)
+        if self.lib.cnnh_net_get_accumulated_grads(self.h, _fp(out)) != 0:
+            raise capi.CnnAmdError("get_accumulated_grads before set_grad_accumulation(k > 1)")
+        return out
 
     def save_optimizer_state(self, path):
         rc = self.lib.cnnh_net_save_optimizer_state(self.h, str(path).encode())

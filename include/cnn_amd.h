@@ -484,6 +484,15 @@ size_t cnn_clip_grad_norm_workspace_bytes(size_t n);
 int cnn_clip_grad_norm(float* grads, size_t n, float max_norm, float grad_scale, void* workspace, size_t workspace_bytes,
                        float* stats_dev /* [2]: total norm, coefficient */, void* stream);
 
+/* Gradient accumulation over micro-batches: one streaming pass that folds the gradients of one backward pass into an accumulator.
+ *     first != 0 :  acc[i] = grads[i]             a copy of the bits -- -0.0, infinities, NaN payloads and denormals come out as they
+ *                                                 went in; acc is not read (it may hold anything), 8 bytes per element
+ *     first == 0 :  acc[i] = acc[i] + grads[i]    one fp32 add, denormals kept, 12 bytes per element
+ * A window of k passes is one call with first = 1 and k - 1 with first = 0: acc = ((g1 + g2) + g3) + ..., the order a host loop
+ * would use.  acc and grads may be misaligned independently (a pointer that is not 16-byte aligned takes the scalar kernel).  Checked
+ * before any launch: no null pointer, n > 0, acc != grads.  One kernel launch per call (its name begins with gacc_). */
+int cnn_grad_accumulate(float* acc, const float* grads, size_t n, int first, void* stream);
+
 /* ---- layer-wise optimizers: LAMB and LARS over one flat arena cut into tensors ("segments") --------------------------------------
  * A handle describes how the flat range [0, n) is cut into n_segments tensors and owns the device copy of that table, the workspace
  * of the segmented norm and a device statistics array; it is created once and reused every step (no per-step host-to-device copy).
