@@ -162,6 +162,9 @@ SIGNATURES = {
     "cnn_clip_grad_norm_workspace_bytes": (C.c_size_t, [C.c_size_t]),
     "cnn_clip_grad_norm": (C.c_int, [_P, C.c_size_t, C.c_float, C.c_float, _P, C.c_size_t, _P, _P]),
     "cnn_grad_accumulate": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P]),
+    "cnn_ema_decay_at": (C.c_float, [C.c_float, C.c_int, C.c_uint64]),
+    "cnn_ema_update": (C.c_int, [_P, _P, C.c_size_t, C.c_float, _P, _P, C.c_size_t, _P]),
+    "cnn_arena_swap": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "cnn_layerwise_create": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_void_p)]),
     "cnn_layerwise_destroy": (C.c_int, [_P]),
     "cnn_layerwise_stats": (C.c_int, [_P, C.POINTER(C.c_void_p)]),
@@ -771,6 +774,37 @@ def grad_accumulate(acc, grads, first, n=None):
     n = acc.numel() if n is None else int(n)
     check(load().cnn_grad_accumulate(_ptr(acc), _ptr(grads), n, 1 if first else 0, _stream()), "cnn_grad_accumulate")
     return acc
+
+
+def ema_decay_at(decay, warmup, updates_done):
+    """cnn_ema_decay_at: the decay of the update that follows updates_done earlier ones (host only)"""
+    return float(load().cnn_ema_decay_at(float(decay), 1 if warmup else 0, int(updates_done)))
+
+
+def ema_update(ema, params, decay, avg_ranges=(), n=None):
+    """cnn_ema_update on device tensors (or views of them): ema = decay * ema + (1 - decay) * params inside avg_ranges ([(begin, end)]
+    relative to params, ascending), a copy of the bits elsewhere and everywhere with decay 0.  Tables longer than SGD_INLINE_RANGES
+    are uploaded here (a caller that updates repeatedly would keep the device copy)."""
+    import numpy as np
+    import torch
+
+    _need_gpu(ema, params)
+    n = ema.numel() if n is None else int(n)
+    table = np.ascontiguousarray(np.asarray(list(avg_ranges), dtype=np.uint32).reshape(-1, 2))
+    n_ranges = table.shape[0]
+    dev = torch.from_numpy(table.view(np.int32).reshape(-1)).to(ema.device) if n_ranges > SGD_INLINE_RANGES else None
+    check(load().cnn_ema_update(_ptr(ema), _ptr(params), n, float(decay), table.ctypes.data_as(C.c_void_p) if n_ranges else None, _ptr(dev),
+                                n_ranges, _stream()), "cnn_ema_update")
+    if dev is not None:
+        torch.cuda.current_stream().synchronize()  # (the table must outlive the kernel that reads it)
+    return ema
+
+
+def arena_swap(a, b, n=None):
+    """cnn_arena_swap on device tensors (or views of them): the bits of two disjoint buffers change places"""
+    _need_gpu(a, b)
+    n = a.numel() if n is None else int(n)
+    check(load().cnn_arena_swap(_ptr(a), _ptr(b), n, _stream()), "cnn_arena_swap")
 
 
 class Layerwise:

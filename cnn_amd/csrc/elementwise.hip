@@ -1,9 +1,10 @@
 // elementwise.hip -- HBM-bound streaming kernels: ReLU fwd/bwd (relu.cpp:21-26,35-40), the SGD step
-// (conv2d.cpp:205-217, linear.cpp:95-102), the optimizer steps, the clip and the gradient accumulation on the flat arena (additions), and
-// the softmax / cross-entropy glue (func.cpp:16-73).
+// (conv2d.cpp:205-217, linear.cpp:95-102), the optimizer steps, the clip, the gradient accumulation, the parameter average and the
+// buffer exchange on the flat arena (additions), and the softmax / cross-entropy glue (func.cpp:16-73).
 // All are 16 B/lane vectorised grid-stride loops; roofline = HBM (8 / 12 / 12 B per element).
 #include <cfloat>
 #include <cstdint>
+#include <type_traits>
 
 #include "common.h"
 
@@ -284,6 +285,79 @@ __global__ __launch_bounds__(kBlock) void adam_scalar(float* __restrict__ p, con
         p[i] = adam_one(p[i], g[i], mi, vi, a.s, decay);
         m[i] = mi;
         v[i] = vi;
+    }
+}
+
+// ---- exponential moving average of the parameters (cnn_ema_update) ----------------------------------------------------------------
+// gacc_vec's shape with sgdm_vec's range table: reads ema, p and writes ema (12 B per element).  The same range structs and
+// wave-uniform search decide which elements are AVERAGED (ema = decay * ema + omd * p, two products and one sum, each rounded); the
+// others -- BatchNorm2D's moving statistics -- take p's bits.  decay == 0 or an empty table averages nothing: that call is
+// gacc_vec<true> / gacc_scalar<true> (acc = g: loads and stores only, ema is not read, 8 B per element) under the names
+// ema_vec_copy / ema_scalar_copy.
+struct EmaArgs {
+    float decay, omd;
+    int nr;  // number of ranges, >= 1
+};
+__device__ __forceinline__ float ema_one(float e, float p, float decay, float omd, bool averaged) {
+#pragma clang fp contract(off)
+    const float de = decay * e;
+    const float op = omd * p;
+    const float sum = de + op;
+    return averaged ? sum : p;  // (a select: p's bits as they are)
+}
+
+template <class Ranges>
+__global__ __launch_bounds__(kBlock) void ema_vec(float4* __restrict__ ema, const float4* __restrict__ p, size_t n4, size_t n, const EmaArgs a,
+                                                  const Ranges r) {
+    if (blockIdx.x == 0 && n4 * 4 + threadIdx.x < n) {
+        float* es = (float*)ema;
+        const float* ps = (const float*)p;
+        const size_t i = n4 * 4 + threadIdx.x;
+        es[i] = ema_one(es[i], ps[i], a.decay, a.omd, decays_at(r, a.nr, i));
+    }
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (size_t)gridDim.x * kBlock) {
+        // (the streams' loads are issued first: the table search below runs while they are in flight)
+        float4 ev = ema[i];
+        const float4 pv = p[i];
+        const unsigned bits = decay_bits4(r, a.nr, i);  // bit j: element 4*i + j is averaged
+        ev.x = ema_one(ev.x, pv.x, a.decay, a.omd, bits & 1u);
+        ev.y = ema_one(ev.y, pv.y, a.decay, a.omd, bits & 2u);
+        ev.z = ema_one(ev.z, pv.z, a.decay, a.omd, bits & 4u);
+        ev.w = ema_one(ev.w, pv.w, a.decay, a.omd, bits & 8u);
+        ema[i] = ev;
+    }
+}
+template <class Ranges>
+__global__ __launch_bounds__(kBlock) void ema_scalar(float* __restrict__ ema, const float* __restrict__ p, size_t n, const EmaArgs a,
+                                                     const Ranges r) {
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock)
+        ema[i] = ema_one(ema[i], p[i], a.decay, a.omd, decays_at(r, a.nr, i));
+}
+
+// ---- exchange of two disjoint buffers (cnn_arena_swap) -------------------------------------------------------------------------------
+// gacc_vec's shape: loads and stores only, every bit pattern survives; reads and writes both (16 B per element).  The buffers do
+// not overlap (checked by the entry), so every element is read before either copy of it is written.
+__global__ __launch_bounds__(kBlock) void aswap_vec(float4* __restrict__ a, float4* __restrict__ b, size_t n4, size_t n) {
+    if (blockIdx.x == 0 && n4 * 4 + threadIdx.x < n) {
+        float* as = (float*)a;
+        float* bs = (float*)b;
+        const size_t i = n4 * 4 + threadIdx.x;
+        const float av = as[i], bv = bs[i];
+        as[i] = bv;
+        bs[i] = av;
+    }
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (size_t)gridDim.x * kBlock) {
+        const float4 av = a[i];
+        const float4 bv = b[i];
+        a[i] = bv;
+        b[i] = av;
+    }
+}
+__global__ __launch_bounds__(kBlock) void aswap_scalar(float* __restrict__ a, float* __restrict__ b, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
+        const float av = a[i], bv = b[i];
+        a[i] = bv;
+        b[i] = av;
     }
 }
 
@@ -671,6 +745,58 @@ int cnn_grad_accumulate(float* acc, const float* grads, size_t n, int first, voi
         }
     }
     return CNN_AMD_OK;
+}
+
+float cnn_ema_decay_at(float decay, int warmup, uint64_t updates_done) {
+    if (warmup == 0) return decay;
+    const double t = (double)updates_done;
+    const float ramp = (float)((1.0 + t) / (10.0 + t));
+    return ramp < decay ? ramp : decay;
+}
+
+// two runs of n floats share an element
+static bool floats_overlap(const float* a, const float* b, size_t n) {
+    const uintptr_t ua = reinterpret_cast<uintptr_t>(a), ub = reinterpret_cast<uintptr_t>(b);
+    return (ua > ub ? ua - ub : ub - ua) < (uintptr_t)n * sizeof(float);
+}
+
+int cnn_ema_update(float* ema, const float* params, size_t n, float decay, const uint32_t* avg_ranges, const uint32_t* avg_ranges_dev,
+                   size_t n_ranges, void* stream) {
+    CNN_REQUIRE(ema && params, "cnn_ema_update: null pointer");
+    CNN_REQUIRE(n != 0, "cnn_ema_update: n=0");
+    CNN_REQUIRE(!floats_overlap(ema, params, n), "cnn_ema_update: ema and params are the same buffer or overlap");
+    CNN_REQUIRE(decay >= 0.f && decay < 1.f, "cnn_ema_update: decay=%g outside [0, 1)", (double)decay);
+    if (int rc = check_decay_ranges("cnn_ema_update", n, avg_ranges, avg_ranges_dev, n_ranges)) return rc;
+    hipStream_t s = as_stream(stream);
+    const bool aligned = aligned16(ema) && aligned16(params);
+    if (decay == 0.f || n_ranges == 0) {  // nothing is averaged: the copy of the bits
+        return launch_update(
+            s, "ema_vec_copy", "ema_scalar_copy", aligned, n, 0,
+            [&](unsigned grid, size_t n4) { gacc_vec<true><<<grid, kBlock, 0, s>>>((float4*)ema, (const float4*)params, n4, n); },
+            [&](unsigned grid) { gacc_scalar<true><<<grid, kBlock, 0, s>>>(ema, params, n); });
+    }
+    EmaArgs a;
+    a.decay = decay;
+    a.omd = 1.f - decay;
+    a.nr = (int)n_ranges;
+    return with_ranges(a.nr, avg_ranges, avg_ranges_dev, [&](const auto& r) {
+        using Ranges = std::decay_t<decltype(r)>;
+        return launch_update(
+            s, "ema_vec", "ema_scalar", aligned, n, a.nr,
+            [&](unsigned grid, size_t n4) { ema_vec<Ranges><<<grid, kBlock, 0, s>>>((float4*)ema, (const float4*)params, n4, n, a, r); },
+            [&](unsigned grid) { ema_scalar<Ranges><<<grid, kBlock, 0, s>>>(ema, params, n, a, r); });
+    });
+}
+
+int cnn_arena_swap(float* a, float* b, size_t n, void* stream) {
+    CNN_REQUIRE(a && b, "cnn_arena_swap: null pointer");
+    CNN_REQUIRE(n != 0, "cnn_arena_swap: n=0");
+    CNN_REQUIRE(!floats_overlap(a, b, n), "cnn_arena_swap: a and b are the same buffer or overlap");
+    hipStream_t s = as_stream(stream);
+    return launch_update(
+        s, "aswap_vec", "aswap_scalar", aligned16(a) && aligned16(b), n, 0,
+        [&](unsigned grid, size_t n4) { aswap_vec<<<grid, kBlock, 0, s>>>((float4*)a, (float4*)b, n4, n); },
+        [&](unsigned grid) { aswap_scalar<<<grid, kBlock, 0, s>>>(a, b, n); });
 }
 
 // (the two update entries differ in when n == 0 returns: this one returns OK before it looks at any argument, cnn_adam_update validates

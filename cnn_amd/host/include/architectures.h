@@ -454,7 +454,9 @@ public:
 //   * an optional optimizer on the arena instead of the reference's w -= lr * g -- one of momentum SGD (set_optimizer), Adam / AdamW
 //     (set_adam), LAMB (set_lamb), LARS (set_lars); the setter called last is the active kind (OptKind, optimizer.cpp);
 //   * clipping by the global gradient norm (set_grad_clip) in front of whichever step is active;
-//   * gradient accumulation over micro-batches (set_grad_accumulation): k container steps, one optimizer step on their summed gradients.
+//   * gradient accumulation over micro-batches (set_grad_accumulation): k container steps, one optimizer step on their summed gradients;
+//   * an exponential moving average of the parameters (set_ema) behind every optimizer step, swapped into the arena for evaluation
+//     and export (swap_ema), with a state file of its own (save_ema_state / load_ema_state).
 class Sequential {
 public:
     bool print_info = false;
@@ -578,8 +580,21 @@ protected:
     // true: the call closes the window (the exchange over the accumulator has run, the caller clips and steps); false: it returns
     bool count_micro_batch();
     void exchange_grads(data_type* grads);  // the event-fenced all-reduce of n_params gradients on the communication stream
-    // the tail of every container step: [the clip,] the active kind's step over the whole arena reading step_grads(), the snapshot
+    // the tail of every container step: [the clip,] the active kind's step over the whole arena reading step_grads(), the snapshot,
+    // [the average]
     void clip_and_step(data_type learning_rate, data_type grad_scale);
+    // ---- exponential moving average of the parameters (set_ema): orthogonal to the kind, to clipping and to accumulation ----
+    struct EmaState {
+        data_type decay = 0;               // 0: off (the shadow and the counter are kept)
+        bool warmup = false, average_stats = false;
+        data_type* shadow = nullptr;       // n_params floats, owned by the container whoever owns the arenas
+        uint64_t updates = 0;              // updates taken since the shadow was last (re)filled
+        bool swapped = false;              // the arena holds the average, the shadow the training weights (swap_ema)
+        DecayTable table;                  // the averaged index ranges of the arena (lo = 0, hi = n_params)
+    } ema;
+    void build_ema_table(bool average_stats);
+    void fill_ema_shadow();                // shadow = parameters (one cnn_ema_update with decay 0), counter = 0
+    void unswap_ema() { if (ema.swapped) swap_ema(); }  // what every entry that steps, or touches the average, starts with
     // the step of the active kind on arena[lo, hi) (parameters, gradients, state, snapshot) on `on_stream`: the ONE dispatch on opt_kind.
     // kSgdm / kAdam step the three ranges decay tables exist for; kLamb / kLars the whole arena only.
     void step_arena(size_t lo, size_t hi, data_type learning_rate, data_type grad_scale, void* on_stream);
@@ -712,6 +727,44 @@ public:
     int grad_accumulation() const { return accum_k; }
     int accumulation_phase() const { return accum_phase; }                 // micro-batches in the open window, 0 .. k-1
     data_type* accumulated_grads_device() const { return accum_grads; }    // null before the first micro_steps > 1
+
+    // Exponential moving average of the parameters: a shadow copy of the arena that follows every optimizer step,
+    //     shadow = d * shadow + (1 - d) * parameters,   d = cnn_ema_decay_at(decay, warmup, updates taken so far)
+    // (formula and rounding in include/cnn_amd.h, cnn_ema_update; warmup: d = min(decay, (1 + t) / (10 + t)), 0.1 at first).
+    // Call it after finalize(), any number of times.  decay in (0, 1) switches it on, decay == 0 off: the shadow and the counter are
+    // kept and nothing more is launched.  The first call with decay > 0 allocates the shadow (num_params() floats, owned by the
+    // container also where the caller provided the arenas, kept until the container goes), fills it with a copy of the bits of the
+    // current parameters and sets the update counter to 0; later calls change the options only.  Averaged are the layers'
+    // decay_ranges(true, ...): weights, biases, BatchNorm2D's gamma / beta.  BatchNorm2D's moving statistics are averages already:
+    // the shadow takes their bits as they are, unless average_stats asks for the whole arena.
+    // The update is the last launch of every optimizer step (update_gradients(lr), update_gradients(lr, grad_scale), train_step), on
+    // the same stream behind the step: ONE cnn_ema_update, 12 bytes per parameter -- once per window under
+    // set_grad_accumulation(k > 1).  Under set_comm nothing is exchanged: every replica averages the same parameters.  THE PRICE:
+    // the average must follow the WHOLE step, and the fused step tail (fused_tail) finishes the arena on two streams, so it declines
+    // while the average is on, as under clipping, trust ratios and accumulation.  With set_ema never called, or off again, nothing
+    // changes, not one launch.  Stand-alone Layer::update_gradients and a non-finalized list never average.
+    void set_ema(data_type decay, bool warmup = false, bool average_stats = false);
+    // shadow = the current parameters (a copy of the bits), counter = 0 -- e.g. after load_weights.  Nothing before the first set_ema.
+    void reset_ema();
+    // Evaluation and export with the averaged weights, without a second network: flush_deferred(), ONE cnn_arena_swap of the arena
+    // and the shadow, parameters_changed().  While swapped forward() (also under WithoutGrad), save_weights() -- the reference's
+    // .model format, unchanged --, grad_cam() and params_device() see the average; a second call restores the training weights bit
+    // for bit.  No misuse to guard against: every entry that steps or counts a micro-batch (both update_gradients forms,
+    // train_step), set_ema, reset_ema, save_ema_state and load_ema_state swap back first.  A write to the arena from outside while
+    // swapped lands in the AVERAGED copy.  Before the first set_ema(decay > 0) it does nothing.
+    void swap_ema();
+    bool ema_swapped() const { return ema.swapped; }
+    data_type* ema_device() const { return ema.shadow; }  // null before the first set_ema(decay > 0)
+    data_type ema_decay() const { return ema.decay; }
+    uint64_t ema_updates() const { return ema.updates; }
+    bool ema_active() const { return ema.decay > 0; }
+    // The average beside a .model checkpoint and an optimizer state file (whose formats do not change): a header of magic "CNNAEMA1",
+    // n_params, updates, decay, warmup, average_stats, then the shadow.  Status codes as save_ / load_optimizer_state: save 0 = ok,
+    // 1 = cannot write, 4 = the average was never switched on (no shadow); load 0 = ok, 1 = cannot open, 2 = not such a file / truncated / options out of
+    // range, 3 = written for another n_params; nothing is changed on failure, on success the file's options are set as by set_ema,
+    // then its shadow and counter.  (A file may carry decay 0: an average that was switched off.)
+    int save_ema_state(const std::filesystem::path& path);
+    int load_ema_state(const std::filesystem::path& path);
 
 protected:
     void invalidate_filter_images();  // (the part of parameters_changed() the container's own SGD step needs too)

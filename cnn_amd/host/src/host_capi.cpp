@@ -187,6 +187,23 @@ int cnnh_net_get_accumulated_grads(void* hv, float* host) {  // 1: accumulation 
     must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
     return 0;
 }
+// Sequential::set_ema and its shadow arena (cnnh_net_get_ema: 1 before the first cnnh_net_set_ema with decay > 0), the swap for
+// evaluation / export, the state file (status codes: architectures.h)
+void cnnh_net_set_ema(void* hv, float decay, int warmup, int average_stats) { ((Handle*)hv)->net->set_ema(decay, warmup != 0, average_stats != 0); }
+void cnnh_net_reset_ema(void* hv) { ((Handle*)hv)->net->reset_ema(); }
+int cnnh_net_get_ema(void* hv, float* host) {
+    Handle* h = (Handle*)hv;
+    if (h->net->ema_device() == nullptr) return 1;
+    h->net->flush_deferred();
+    must(cnn_memcpy_d2h(host, h->net->ema_device(), sizeof(float) * h->net->num_params(), stream), "cnn_memcpy_d2h");
+    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
+    return 0;
+}
+uint64_t cnnh_net_ema_updates(void* hv) { return ((Handle*)hv)->net->ema_updates(); }
+void cnnh_net_swap_ema(void* hv) { ((Handle*)hv)->net->swap_ema(); }
+int cnnh_net_ema_swapped(void* hv) { return ((Handle*)hv)->net->ema_swapped() ? 1 : 0; }
+int cnnh_net_save_ema_state(void* hv, const char* path) { return ((Handle*)hv)->net->save_ema_state(path); }
+int cnnh_net_load_ema_state(void* hv, const char* path) { return ((Handle*)hv)->net->load_ema_state(path); }
 int cnnh_net_save_optimizer_state(void* hv, const char* path) { return ((Handle*)hv)->net->save_optimizer_state(path); }
 int cnnh_net_load_optimizer_state(void* hv, const char* path) { return ((Handle*)hv)->net->load_optimizer_state(path); }
 void cnnh_set_stream(void* hip_stream) { architectures::stream = hip_stream; }

@@ -1,7 +1,8 @@
 // optimizer.cpp -- the optimizer of architectures::Sequential (member functions; the class is in architectures.h): ONE kind
 // (OptKind) says which step the container takes on its flat arena, every kind has its options struct, all kinds share one block of
 // state (OptState), and the state files are one writer and one reader over a table of formats.  Clipping by the global gradient norm
-// is orthogonal to the kind and sits at the end, with the setter of gradient accumulation over micro-batches.
+// is orthogonal to the kind and sits at the end, with the setter of gradient accumulation over micro-batches and the exponential
+// moving average of the parameters (its setters, the swap, its state file).
 #include <algorithm>
 #include <cassert>
 #include <cstddef>
@@ -450,4 +451,112 @@ data_type Sequential::last_grad_norm(data_type* coef_out) {
     must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
     if (coef_out) *coef_out = host[1];
     return host[0];
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// exponential moving average of the parameters: a shadow arena behind every optimizer step (clip_and_step(), sequential.cpp), swapped
+// into the parameter arena for evaluation and export
+void Sequential::build_ema_table(const bool average_stats) {
+    if (!average_stats) {  // weights, biases, gamma / beta -- everything but BatchNorm2D's moving statistics
+        build_decay_table(ema.table, 0, n_params, /*bias_and_norm=*/true);
+        return;
+    }
+    build_decay_table(ema.table, 0, 0, true);  // (empties the table and frees a device copy)
+    ema.table.hi = n_params;
+    if (n_params > 0) ema.table.host = {0u, (uint32_t)n_params};
+}
+
+void Sequential::fill_ema_shadow() {
+    if (n_params > 0) must(cnn_ema_update(ema.shadow, param_arena, n_params, 0.f, nullptr, nullptr, 0, stream), "cnn_ema_update");
+    ema.updates = 0;
+}
+
+void Sequential::set_ema(const data_type decay, const bool warmup, const bool average_stats) {
+    if (!(decay >= 0 && decay < 1)) {
+        std::fprintf(stderr, "cnn_amd host: set_ema: decay=%g outside [0, 1) (0 = off)\n", (double)decay);
+        std::abort();
+    }
+    begin_optimizer_switch("set_ema");
+    unswap_ema();
+    build_ema_table(average_stats);
+    ema.warmup = warmup;
+    ema.average_stats = average_stats;
+    if (decay > 0 && ema.shadow == nullptr) {
+        ema.shadow = (data_type*)dev_alloc(sizeof(data_type) * (n_params ? n_params : 1));
+        fill_ema_shadow();
+    }
+    ema.decay = decay;
+}
+
+void Sequential::reset_ema() {
+    if (ema.shadow == nullptr) return;
+    flush_deferred();
+    unswap_ema();
+    fill_ema_shadow();
+}
+
+void Sequential::swap_ema() {
+    if (ema.shadow == nullptr) return;
+    flush_deferred();
+    if (n_params > 0) must(cnn_arena_swap(param_arena, ema.shadow, n_params, stream), "cnn_arena_swap");
+    ema.swapped = !ema.swapped;
+    parameters_changed();
+}
+
+namespace {
+struct EmaStateHeader {  // then the shadow, n_params floats
+    char magic[8];
+    uint64_t n_params, updates;
+    float decay;
+    uint32_t warmup, average_stats, pad;  // (pad: written as 0)
+};
+static_assert(sizeof(EmaStateHeader) == 40 && offsetof(EmaStateHeader, updates) == 16 && offsetof(EmaStateHeader, decay) == 24 &&
+                  offsetof(EmaStateHeader, warmup) == 28 && offsetof(EmaStateHeader, average_stats) == 32 && offsetof(EmaStateHeader, pad) == 36,
+              "the EMA state file's header is 40 bytes, its layout is fixed");
+const char kEmaMagic[9] = "CNNAEMA1";
+}  // namespace
+
+int Sequential::save_ema_state(const std::filesystem::path& path) {
+    assert(finalized);
+    if (ema.shadow == nullptr) return 4;
+    flush_deferred();
+    unswap_ema();
+    std::vector<data_type> host(n_params);
+    must(cnn_memcpy_d2h(host.data(), ema.shadow, sizeof(data_type) * n_params, stream), "cnn_memcpy_d2h");
+    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
+    EmaStateHeader h;
+    std::memset(&h, 0, sizeof(h));
+    std::memcpy(h.magic, kEmaMagic, 8);
+    h.n_params = n_params;
+    h.updates = ema.updates;
+    h.decay = ema.decay;
+    h.warmup = ema.warmup;
+    h.average_stats = ema.average_stats;
+    std::ofstream writer(path.c_str(), std::ios::binary);
+    writer.write((const char*)&h, sizeof(h));
+    writer.write((const char*)host.data(), sizeof(data_type) * host.size());
+    writer.close();
+    return writer.good() ? 0 : 1;
+}
+
+// Nothing is changed on any failure: the header is checked and the whole payload read before the setter runs.
+int Sequential::load_ema_state(const std::filesystem::path& path) {
+    assert(finalized);
+    std::ifstream reader(path.c_str(), std::ios::binary);
+    if (!reader.good()) return 1;
+    EmaStateHeader h;
+    std::memset(&h, 0, sizeof(h));
+    reader.read((char*)&h, sizeof(h));
+    if (!reader.good() || std::memcmp(h.magic, kEmaMagic, 8) != 0) return 2;
+    if (h.n_params != (uint64_t)n_params) return 3;
+    if (!(h.decay >= 0 && h.decay < 1) || h.warmup > 1 || h.average_stats > 1 || h.pad != 0) return 2;
+    std::vector<data_type> host(n_params);
+    reader.read((char*)host.data(), sizeof(data_type) * host.size());
+    if ((size_t)reader.gcount() != sizeof(data_type) * host.size()) return 2;
+    set_ema(h.decay, h.warmup != 0, h.average_stats != 0);  // (swaps back first)
+    if (ema.shadow == nullptr) ema.shadow = (data_type*)dev_alloc(sizeof(data_type) * (n_params ? n_params : 1));  // (a file with decay 0)
+    must(cnn_memcpy_h2d(ema.shadow, host.data(), sizeof(data_type) * n_params, stream), "cnn_memcpy_h2d");
+    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
+    ema.updates = h.updates;
+    return 0;
 }

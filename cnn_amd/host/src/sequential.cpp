@@ -183,6 +183,8 @@ Sequential::~Sequential() {
     if (clip_workspace) cnn_device_free(clip_workspace);
     if (clip_stats) cnn_device_free(clip_stats);
     if (accum_grads) cnn_device_free(accum_grads);
+    if (ema.shadow) cnn_device_free(ema.shadow);
+    if (ema.table.dev) cnn_device_free(ema.table.dev);
     if (opt.layerwise) cnn_layerwise_destroy(opt.layerwise);
     if (opt.lamb_update) cnn_device_free(opt.lamb_update);
     for (auto& t : opt.decay_tables)
@@ -445,6 +447,7 @@ bool Sequential::count_micro_batch() {
 
 void Sequential::update_gradients(const data_type learning_rate) {
     flush_deferred();
+    unswap_ema();  // (the step moves the training weights, never the average)
     if (!finalized) {  // plain list of stand-alone layers: the reference's loop (alexnet.cpp:62-65)
         for (auto& layer : layers_sequence) layer->update_gradients(learning_rate);
         return;
@@ -463,6 +466,7 @@ void Sequential::update_gradients(const data_type learning_rate) {
 
 void Sequential::update_gradients(const data_type learning_rate, const data_type grad_scale) {
     assert(finalized && "the grad_scale form works on the flat arena: call finalize()");
+    unswap_ema();
     if (accum_k > 1) {  // (grad_scale is the caller's 1/G for ONE pass; the window summed k of them)
         if (count_micro_batch()) clip_and_step(learning_rate, grad_scale / (data_type)accum_k);
         return;
@@ -481,6 +485,12 @@ void Sequential::clip_and_step(const data_type learning_rate, const data_type gr
     step_arena(0, n_params, learning_rate, grad_scale, stream);  // (optimizer.cpp: the dispatch on the active kind)
     invalidate_filter_images();
     params_stepped = true;
+    if (ema.decay > 0 && n_params > 0) {  // the average follows the whole step: one launch on the same stream behind it
+        const data_type decay = cnn_ema_decay_at(ema.decay, ema.warmup ? 1 : 0, ema.updates);
+        must(cnn_ema_update(ema.shadow, param_arena, n_params, decay, ema.table.host.data(), ema.table.dev, ema.table.host.size() / 2, stream),
+             "cnn_ema_update");
+        ++ema.updates;
+    }
 }
 
 // the pool-fused front block's convolution owns arena[0, front_block_params()) (wire(): block_conv is the first layer); 0 without one
@@ -514,6 +524,8 @@ bool Sequential::fused_tail(std::vector<tensor>& delta, const data_type learning
     if (clip_max_norm > 0) return false;  // (the norm needs every gradient of the step before any parameter moves: the plain sequence)
     if (step_needs_whole_tensors()) return false;  // (so does a trust ratio: every gradient of a tensor before that tensor moves)
     if (accum_k > 1) return false;  // (the block's in-kernel step would move parameters in the middle of a window: the plain sequence)
+    // (the average reads the whole arena behind the step, and this tail finishes the arena on two streams: the plain sequence)
+    if (ema.decay > 0) return false;
     const size_t lo = front_block_params();  // the block's convolution owns arena[0, lo)
     const bool dp = exchange_active();
     const data_type scale = dp ? 1.f / (data_type)comm_world : 1.f;
@@ -630,6 +642,7 @@ void Sequential::train_step(const std::vector<tensor>& input, const int* labels_
     const int classes = head->out_features();
     ensure_loss_buffers(B, classes);
     if (print_info) input[0]->print_shape();
+    unswap_ema();  // (a step trains the training weights: an average swapped in for evaluation goes back first)
     if (finalized && fuse_layers && !filters_prepared) {
         flush_deferred();  // (a full re-preparation rewrites filter images a pending data gradient may read)
         prepare_filters();

@@ -1,5 +1,6 @@
 """ctypes front end of libcnn_amd_host.so -- the C++17 mirror of the reference's Layer/AlexNet API
 (cnn_amd/host).  Used by tests/ and bench.py to drive exactly the code path a reference user links against."""
+import contextlib
 import ctypes as C
 import os
 
@@ -51,6 +52,14 @@ SIGNATURES = {
     "cnnh_net_set_grad_accumulation": (None, [C.c_void_p, C.c_int]),
     "cnnh_net_accumulation_phase": (C.c_int, [C.c_void_p]),
     "cnnh_net_get_accumulated_grads": (C.c_int, [C.c_void_p, _F]),
+    "cnnh_net_set_ema": (None, [C.c_void_p, C.c_float, C.c_int, C.c_int]),
+    "cnnh_net_reset_ema": (None, [C.c_void_p]),
+    "cnnh_net_get_ema": (C.c_int, [C.c_void_p, _F]),
+    "cnnh_net_ema_updates": (C.c_uint64, [C.c_void_p]),
+    "cnnh_net_swap_ema": (None, [C.c_void_p]),
+    "cnnh_net_ema_swapped": (C.c_int, [C.c_void_p]),
+    "cnnh_net_save_ema_state": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "cnnh_net_load_ema_state": (C.c_int, [C.c_void_p, C.c_char_p]),
     "cnnh_net_save_optimizer_state": (C.c_int, [C.c_void_p, C.c_char_p]),
     "cnnh_net_load_optimizer_state": (C.c_int, [C.c_void_p, C.c_char_p]),
     "cnnh_set_stream": (None, [C.c_void_p]),
@@ -259,6 +268,60 @@ class HostNet:
         if self.lib.cnnh_net_get_accumulated_grads(self.h, _fp(out)) != 0:
             raise capi.CnnAmdError("get_accumulated_grads before set_grad_accumulation(k > 1)")
         return out
+
+    def set_ema(self, decay, warmup=False, average_stats=False):
+        """Sequential::set_ema: a shadow copy of the arena follows every later optimizer step, shadow = d * shadow + (1 - d) * params
+        (0: off, the shadow stays); warmup: d = min(decay, (1 + t) / (10 + t)); BatchNorm2D's moving statistics are copied, not
+        averaged, unless average_stats.  No fused step tail while it is on."""
+        if not 0.0 <= float(decay) < 1.0:
+            raise capi.CnnAmdError(f"set_ema({decay}): decay in [0, 1)")
+        self.lib.cnnh_net_set_ema(self.h, float(decay), 1 if warmup else 0, 1 if average_stats else 0)
+
+    def reset_ema(self):
+        """the shadow becomes a copy of the current parameters, the update counter 0 (e.g. after load_checkpoint)"""
+        self.lib.cnnh_net_reset_ema(self.h)
+
+    def get_ema(self):
+        """the shadow arena on the host -- while swapped (swap_ema) it holds the training weights"""
+        out = np.empty(self.n_params, np.float32)
+        if self.lib.cnnh_net_get_ema(self.h, _fp(out)) != 0:
+            raise capi.CnnAmdError("get_ema before set_ema(decay > 0)")
+        return out
+
+    def ema_updates(self):
+        """updates of the average since the shadow was last (re)filled"""
+        return int(self.lib.cnnh_net_ema_updates(self.h))
+
+    def swap_ema(self):
+        """Sequential::swap_ema: the arena and the shadow change places (forward, save_checkpoint, grad_cam then see the averaged
+        weights); a second call, or any step, swaps back"""
+        self.lib.cnnh_net_swap_ema(self.h)
+
+    def ema_swapped(self):
+        return self.lib.cnnh_net_ema_swapped(self.h) != 0
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """with net.averaged(): ... -- the averaged weights are swapped in for the body and swapped back on exit, also when it raises"""
+        if not self.ema_swapped():
+            self.swap_ema()
+        try:
+            yield self
+        finally:
+            if self.ema_swapped():
+                self.swap_ema()
+
+    def save_ema_state(self, path):
+        rc = self.lib.cnnh_net_save_ema_state(self.h, str(path).encode())
+        if rc != 0:
+            raise capi.CnnAmdError(f"save_ema_state({path}): rc={rc}" + (" (the average was never switched on)" if rc == 4 else ""))
+
+    def load_ema_state(self, path):
+        rc = self.lib.cnnh_net_load_ema_state(self.h, str(path).encode())
+        if rc == 1:
+            raise FileNotFoundError(path)
+        if rc != 0:
+            raise capi.CnnAmdError(f"load_ema_state({path}): rc={rc}" + (" (written for another n_params)" if rc == 3 else ""))
 
     def save_optimizer_state(self, path):
         rc = self.lib.cnnh_net_save_optimizer_state(self.h, str(path).encode())

@@ -493,6 +493,35 @@ int cnn_clip_grad_norm(float* grads, size_t n, float max_norm, float grad_scale,
  * before any launch: no null pointer, n > 0, acc != grads.  One kernel launch per call (its name begins with gacc_). */
 int cnn_grad_accumulate(float* acc, const float* grads, size_t n, int first, void* stream);
 
+/* Exponential moving average of the parameters (torch.optim.swa_utils.AveragedModel, timm's ModelEmaV2, TF's
+ * ExponentialMovingAverage): one streaming pass that folds the current parameters into a shadow copy of the arena, in
+ * cnn_sgd_momentum_update's arithmetic (fp32, every product and sum rounded separately, no FMA, denormals kept).  Host scalar of the
+ * call: omd = 1.f - decay.  Per element i:
+ *     decay == 0    :  ema[i] = params[i]                          a copy of the bits -- -0.0, infinities, NaN payloads and denormals come
+ *                                                                  out as they went in; ema is not read (it may hold anything), 8 bytes
+ *                                                                  per element
+ *     averaged(i)   :  ema[i] = decay * ema[i] + omd * params[i]   two products and one sum, 12 bytes per element
+ *     otherwise     :  ema[i] = params[i]                          a copy of the bits: BatchNorm2D's moving statistics, which are
+ *                                                                  averages already and follow the model
+ * averaged(i): i lies inside one of n_ranges half-open index ranges; avg_ranges, avg_ranges_dev and n_ranges follow the conventions
+ * of cnn_sgd_momentum_update's decay_ranges / decay_ranges_dev -- a HOST array of begin, end pairs relative to `params`, ascending,
+ * non-empty and disjoint, end <= n; up to CNN_SGD_INLINE_RANGES ranges travel in the kernel arguments, beyond that the kernel reads
+ * the DEVICE copy; n <= 2^32 - 257.  With n_ranges == 0 no element is averaged and the call is the copy.  ema and params may be
+ * misaligned independently (a pointer that is not 16-byte aligned, or n < 4, takes the scalar kernel, same results).  Checked before
+ * any launch: no null pointer, n > 0, ema and params do not overlap, decay in [0, 1) (a NaN fails), the range table.  One kernel
+ * launch per call (its name begins with ema_).
+ * cnn_ema_decay_at: the decay of the update that follows updates_done earlier ones -- pure host code.  warmup == 0: decay.
+ * Otherwise min(decay, (float)((1.0 + t) / (10.0 + t))) with t = (double)updates_done: the warm-up of TF and timm, whose first
+ * update uses 0.1. */
+float cnn_ema_decay_at(float decay, int warmup, uint64_t updates_done);
+int cnn_ema_update(float* ema, const float* params, size_t n, float decay, const uint32_t* avg_ranges, const uint32_t* avg_ranges_dev,
+                   size_t n_ranges, void* stream);
+
+/* Exchanges the bits of two disjoint buffers of n floats in one launch (its name begins with aswap_): 16 bytes per element, any
+ * alignment, every bit pattern survives; two calls restore both buffers.  Checked before the launch: no null pointer, n > 0, a and b
+ * at least n floats apart. */
+int cnn_arena_swap(float* a, float* b, size_t n, void* stream);
+
 /* ---- layer-wise optimizers: LAMB and LARS over one flat arena cut into tensors ("segments") --------------------------------------
  * A handle describes how the flat range [0, n) is cut into n_segments tensors and owns the device copy of that table, the workspace
  * of the segmented norm and a device statistics array; it is created once and reused every step (no per-step host-to-device copy).
