@@ -1,7 +1,17 @@
-// elementwise.hip -- HBM-bound streaming kernels: ReLU fwd/bwd (relu.cpp:21-26,35-40), the SGD step
-// (conv2d.cpp:205-217, linear.cpp:95-102), the optimizer steps, the clip, the gradient accumulation, the parameter average and the
-// buffer exchange on the flat arena (additions), and the softmax / cross-entropy glue (func.cpp:16-73).
-// All are 16 B/lane vectorised grid-stride loops; roofline = HBM (8 / 12 / 12 B per element).
+// elementwise.hip -- HBM-bound streaming kernels: ReLU fwd/bwd (relu.cpp:21-26,35-40), dropout, the SGD step (conv2d.cpp:205-217,
+// linear.cpp:95-102), the optimizer steps, the clip, the gradient accumulation, the parameter average and the buffer exchange on the
+// flat arena (additions), and the softmax / cross-entropy and Grad-CAM glue (func.cpp:16-73, alexnet.cpp:107-140), which have shapes
+// of their own.
+//
+// Every streaming kernel here has ONE shape (stream_walk) over the flat range [0, n):
+//   * the float4 form (every pointer 16-byte aligned): workgroup 0 first takes the n % 4 trailing elements, one per lane, then every
+//     lane grid-strides over the n / 4 float4 -- 16 B per lane and stream, consecutive lanes on consecutive float4;
+//   * the scalar form (any alignment): a grid-stride loop over the elements from `begin`.
+// A rule is an Op: the streams' pointers, the rule's scalars, and ONE member run<V>(i) that says what happens at index i of the
+// streams taken as V = float (element i) or V = float4 (elements 4i .. 4i + 3): load the streams with at<V>, hand the values to the
+// one-element arithmetic with each<V> / each_bit<V> (once, or on x, y, z, w in that order), store.  A rule's kernels are two named
+// one-line wrappers around the walker (<rule>_vec, <rule>_scalar: the names profiles and tools know them by), and its entry point
+// launches them through launch_stream, the one place that chooses between them.  Roofline = HBM (8 .. 32 B per element).
 #include <cfloat>
 #include <cstdint>
 #include <type_traits>
@@ -14,134 +24,161 @@ namespace {
 
 constexpr int kBlock = 256;
 
+// ---- the shape ------------------------------------------------------------------------------------------------------------------------
+template <bool kVec, class Op>
+__device__ __forceinline__ void stream_walk(Op& op, size_t begin, size_t n) {
+    const size_t lane = (size_t)blockIdx.x * kBlock + threadIdx.x, stride = (size_t)gridDim.x * kBlock;
+    if constexpr (kVec) {
+        const size_t n4 = n / 4;
+        if (blockIdx.x == 0 && n4 * 4 + threadIdx.x < n) op.template run<float>(n4 * 4 + threadIdx.x);
+        for (size_t i = lane; i < n4; i += stride) op.template run<float4>(i);
+    } else {
+        for (size_t i = begin + lane; i < n; i += stride) op.template run<float>(i);
+    }
+}
+
+// index i of a stream taken as V
+template <class V>
+__device__ __forceinline__ V& at(float* p, size_t i) { return reinterpret_cast<V*>(p)[i]; }
+template <class V>
+__device__ __forceinline__ const V& at(const float* p, size_t i) { return reinterpret_cast<const V*>(p)[i]; }
+
+// f(values of one element ...) on the element (V = float) or on x, y, z, w in that order (V = float4); each_bit: with bit j of
+// `bits` behind the j-th element's values
+template <class V, class F, class... A>
+__device__ __forceinline__ void each(const F& f, A&... a) {
+    if constexpr (std::is_same<V, float>::value) {
+        f(a...);
+    } else {
+        f(a.x...); f(a.y...); f(a.z...); f(a.w...);
+    }
+}
+template <class V, class F, class... A>
+__device__ __forceinline__ void each_bit(unsigned bits, const F& f, A&... a) {
+    if constexpr (std::is_same<V, float>::value) {
+        f(a..., bits & 1u);
+    } else {
+        f(a.x..., bits & 1u); f(a.y..., bits & 2u); f(a.z..., bits & 4u); f(a.w..., bits & 8u);
+    }
+}
+
+// ---- ReLU -----------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float relu_f(float v) { return v >= 0.f ? v : 0.f; }        // relu.cpp:25
 __device__ __forceinline__ float relu_b(float y, float d) { return y <= 0.f ? 0.f : d; }  // relu.cpp:38
 
-__global__ __launch_bounds__(kBlock) void relu_fwd_vec(const float4* __restrict__ x, float4* __restrict__ y,
-                                                       size_t n4) {
-    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (size_t)gridDim.x * kBlock) {
-        float4 v = x[i];
-        v.x = relu_f(v.x); v.y = relu_f(v.y); v.z = relu_f(v.z); v.w = relu_f(v.w);
-        y[i] = v;
+struct ReluFwdOp {
+    const float* x;
+    float* y;
+    template <class V>
+    __device__ __forceinline__ void run(size_t i) const {
+        V v = at<V>(x, i);
+        each<V>([](float& ve) { ve = relu_f(ve); }, v);
+        at<V>(y, i) = v;
     }
-}
-__global__ __launch_bounds__(kBlock) void relu_fwd_scalar(const float* __restrict__ x, float* __restrict__ y,
-                                                          size_t begin, size_t n) {
-    for (size_t i = begin + (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock)
-        y[i] = relu_f(x[i]);
-}
-
-__global__ __launch_bounds__(kBlock) void relu_bwd_vec(const float4* __restrict__ y, float4* __restrict__ d,
-                                                       size_t n4) {
-    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (size_t)gridDim.x * kBlock) {
-        const float4 yv = y[i];
-        float4 dv = d[i];
-        dv.x = relu_b(yv.x, dv.x); dv.y = relu_b(yv.y, dv.y); dv.z = relu_b(yv.z, dv.z); dv.w = relu_b(yv.w, dv.w);
-        d[i] = dv;
+};
+struct ReluBwdOp {
+    const float* y;
+    float* d;
+    template <class V>
+    __device__ __forceinline__ void run(size_t i) const {
+        const V yv = at<V>(y, i);
+        V dv = at<V>(d, i);
+        each<V>([](float ye, float& de) { de = relu_b(ye, de); }, yv, dv);
+        at<V>(d, i) = dv;
     }
-}
-__global__ __launch_bounds__(kBlock) void relu_bwd_scalar(const float* __restrict__ y, float* __restrict__ d,
-                                                          size_t begin, size_t n) {
-    for (size_t i = begin + (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock)
-        d[i] = relu_b(y[i], d[i]);
-}
+};
+__global__ __launch_bounds__(kBlock) void relu_fwd_vec(const ReluFwdOp op, size_t n) { stream_walk<true>(op, 0, n); }
+__global__ __launch_bounds__(kBlock) void relu_fwd_scalar(const ReluFwdOp op, size_t begin, size_t n) { stream_walk<false>(op, begin, n); }
+__global__ __launch_bounds__(kBlock) void relu_bwd_vec(const ReluBwdOp op, size_t n) { stream_walk<true>(op, 0, n); }
+__global__ __launch_bounds__(kBlock) void relu_bwd_scalar(const ReluBwdOp op, size_t begin, size_t n) { stream_walk<false>(op, begin, n); }
 
 // Dropout (cpu/src/dropout.cpp): CHANNEL dropout -- the first `dropped` channels of every sample are zeroed in training
 // (:34-41: the loop tests the channel INDEX o against selected_num; the shuffled `sequence` only feeds the mask bookkeeping,
 // so the dropped set is always channels 0 .. selected_num-1), the whole tensor is scaled by 1 - p under no_grad (:44-53).
-// backward (:57-69) zeroes the same channels of the delta in place.  16 B/lane where the channel planes allow it.
-__global__ __launch_bounds__(kBlock) void dropout_fwd(const float* __restrict__ x, float* __restrict__ y, size_t n, int C, int area,
-                                                      int dropped, int training, float keep) {
-    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
+// backward (:57-69) zeroes the same channels of the delta in place.  The scalar form only: the channel comes from the element index.
+struct DropoutFwdOp {
+    const float* x;
+    float* y;
+    int C, area, dropped, training;
+    float keep;
+    template <class V>
+    __device__ __forceinline__ void run(size_t i) const {
         const int o = (int)((i / (size_t)area) % (size_t)C);
         const float v = x[i];
         y[i] = training ? (o >= dropped ? v : 0.f) : v * keep;
     }
-}
-__global__ __launch_bounds__(kBlock) void dropout_bwd(float* __restrict__ d, size_t n, int C, int area, int dropped) {
-    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
+};
+struct DropoutBwdOp {
+    float* d;
+    int C, area, dropped;
+    template <class V>
+    __device__ __forceinline__ void run(size_t i) const {
         const int o = (int)((i / (size_t)area) % (size_t)C);
         if (o < dropped) d[i] = 0.f;
     }
-}
+};
+__global__ __launch_bounds__(kBlock) void dropout_fwd(const DropoutFwdOp op, size_t n) { stream_walk<false>(op, 0, n); }
+__global__ __launch_bounds__(kBlock) void dropout_bwd(const DropoutBwdOp op, size_t n) { stream_walk<false>(op, 0, n); }
 
-// sgd_one(): common.h
-// (the <= 3 trailing elements of an arena whose length is not a multiple of 4 ride along in workgroup 0)
-// `keep` (nullable, wave-uniform): receives the value every parameter had BEFORE the step (cnn_sgd_update_keep)
-__global__ __launch_bounds__(kBlock) void sgd_vec(float4* __restrict__ p, const float4* __restrict__ g, size_t n4,
-                                                  size_t n, float lr, float scale, bool scaled, float4* __restrict__ keep) {
-    if (blockIdx.x == 0 && n4 * 4 + threadIdx.x < n) {
-        float* ps = (float*)p;
-        const float* gs = (const float*)g;
-        const size_t i = n4 * 4 + threadIdx.x;
-        if (keep) ((float*)keep)[i] = ps[i];
-        ps[i] = sgd_one(ps[i], gs[i], lr, scale, scaled);
+// ---- the SGD step (cnn_sgd_update_keep; sgd_one(): common.h) --------------------------------------------------------------------------
+// `keep` (nullable, wave-uniform): receives the value every parameter had BEFORE the step
+struct SgdOp {
+    float* p;
+    const float* g;
+    float* keep;
+    float lr, scale;
+    bool scaled;
+    template <class V>
+    __device__ __forceinline__ void run(size_t i) const {
+        V pv = at<V>(p, i);
+        const V gv = at<V>(g, i);
+        if (keep) at<V>(keep, i) = pv;
+        each<V>([&](float& pe, float ge) { pe = sgd_one(pe, ge, lr, scale, scaled); }, pv, gv);
+        at<V>(p, i) = pv;
     }
-    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (size_t)gridDim.x * kBlock) {
-        float4 pv = p[i];
-        const float4 gv = g[i];
-        if (keep) keep[i] = pv;
-        pv.x = sgd_one(pv.x, gv.x, lr, scale, scaled); pv.y = sgd_one(pv.y, gv.y, lr, scale, scaled);
-        pv.z = sgd_one(pv.z, gv.z, lr, scale, scaled); pv.w = sgd_one(pv.w, gv.w, lr, scale, scaled);
-        p[i] = pv;
-    }
-}
-__global__ __launch_bounds__(kBlock) void sgd_scalar(float* __restrict__ p, const float* __restrict__ g,
-                                                     size_t begin, size_t n, float lr, float scale, bool scaled, float* __restrict__ keep) {
-    for (size_t i = begin + (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
-        if (keep) keep[i] = p[i];
-        p[i] = sgd_one(p[i], g[i], lr, scale, scaled);
-    }
-}
+};
+__global__ __launch_bounds__(kBlock) void sgd_vec(const SgdOp op, size_t n) { stream_walk<true>(op, 0, n); }
+__global__ __launch_bounds__(kBlock) void sgd_scalar(const SgdOp op, size_t begin, size_t n) { stream_walk<false>(op, begin, n); }
 
 // ---- gradient accumulation over micro-batches (cnn_grad_accumulate) ----------------------------------------------------------------
-// sgd_vec's shape: float4 body, the <= 3 trailing elements in workgroup 0, a scalar kernel for unaligned pointers.  kFirst opens a
-// window: acc = g, loads and stores only (every bit pattern survives, acc is not read: 8 B per element); otherwise acc = acc + g,
-// one fp32 add per element (12 B per element).
+// kFirst opens a window: acc = g, loads and stores only (every bit pattern survives, acc is not read: 8 B per element); otherwise
+// acc = acc + g, one fp32 add per element (12 B per element).
 template <bool kFirst>
-__global__ __launch_bounds__(kBlock) void gacc_vec(float4* __restrict__ acc, const float4* __restrict__ g, size_t n4, size_t n) {
-    if (blockIdx.x == 0 && n4 * 4 + threadIdx.x < n) {
-        float* as = (float*)acc;
-        const float* gs = (const float*)g;
-        const size_t i = n4 * 4 + threadIdx.x;
-        as[i] = kFirst ? gs[i] : as[i] + gs[i];
-    }
-    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (size_t)gridDim.x * kBlock) {
-        const float4 gv = g[i];
+struct GaccOp {
+    float* acc;
+    const float* g;
+    template <class V>
+    __device__ __forceinline__ void run(size_t i) const {
+        const V gv = at<V>(g, i);
         if (kFirst) {
-            acc[i] = gv;
+            at<V>(acc, i) = gv;
         } else {
-            float4 av = acc[i];
-            av.x = av.x + gv.x; av.y = av.y + gv.y; av.z = av.z + gv.z; av.w = av.w + gv.w;
-            acc[i] = av;
+            V av = at<V>(acc, i);
+            each<V>([](float& ae, float ge) { ae = ae + ge; }, av, gv);
+            at<V>(acc, i) = av;
         }
     }
-}
-template <bool kFirst>
-__global__ __launch_bounds__(kBlock) void gacc_scalar(float* __restrict__ acc, const float* __restrict__ g, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock)
-        acc[i] = kFirst ? g[i] : acc[i] + g[i];
-}
-
-// ---- SGD with momentum / weight decay / Nesterov (cnn_sgd_momentum_update; sgdm_one(): common.h) -----------------------------
-// Same shape as sgd_vec: float4 body, the <= 3 trailing elements in workgroup 0, a scalar kernel for unaligned pointers, nullable
-// `keep`.  Reads p, g, v and writes p, v (20 B per element, 24 with keep).  Weight decay applies inside the sorted, disjoint index
-// ranges [begin(k), end(k)) of `r` only: by value in the kernel arguments up to CNN_SGD_INLINE_RANGES of them, a device table beyond.
-// A wave's 64 float4 are 256 consecutive elements: ONE wave-uniform binary search finds the first range that ends behind the wave's
-// first element; a wave that lies wholly inside or outside a range (nearly all of them: ranges are layers' weight blocks) is done
-// with that, the others walk on from there per lane.
-struct SgdmArgs {
-    float lr, momentum, wd, scale;
-    bool scaled, nesterov;
-    int nr;  // number of ranges; 0 when weight_decay == 0
 };
+template <bool kFirst>
+__global__ __launch_bounds__(kBlock) void gacc_vec(const GaccOp<kFirst> op, size_t n) { stream_walk<true>(op, 0, n); }
+template <bool kFirst>
+__global__ __launch_bounds__(kBlock) void gacc_scalar(const GaccOp<kFirst> op, size_t begin, size_t n) { stream_walk<false>(op, begin, n); }
+
+// ---- index ranges of the flat arena (weight decay of sgdm / adam, the averaged elements of ema) -------------------------------------
+// The sorted, disjoint index ranges [begin(k), end(k)) of `r`: by value in the kernel arguments up to CNN_SGD_INLINE_RANGES of them,
+// a device table beyond.  A wave's 64 float4 are 256 consecutive elements: ONE wave-uniform binary search finds the first range that
+// ends behind the wave's first element; a wave that lies wholly inside or outside a range (nearly all of them: ranges are layers'
+// weight blocks) is done with that, the others walk on from there per lane.
 struct InlineRanges {
     uint32_t be[2 * CNN_SGD_INLINE_RANGES];
     __device__ __forceinline__ uint32_t begin(int k) const { return be[2 * k]; }
     __device__ __forceinline__ uint32_t end(int k) const { return be[2 * k + 1]; }
 };
 struct DeviceRanges {
-    const uint32_t* be;
+    // (the constant address space: nothing writes the table while a kernel runs, so the wave-uniform search reads it with scalar loads
+    // whatever the streams' pointers may alias)
+    using Table = const __attribute__((address_space(4))) uint32_t*;
+    Table be;
     __device__ __forceinline__ uint32_t begin(int k) const { return be[2 * k]; }
     __device__ __forceinline__ uint32_t end(int k) const { return be[2 * k + 1]; }
 };
@@ -162,7 +199,7 @@ __device__ __forceinline__ bool in_range_from(const Ranges& r, int nr, int& k, u
     return k < nr && r.begin(k) <= idx;
 }
 
-// which of the four elements of float4 i decay (bit j: element 4*i + j); the search is wave-uniform, see above
+// which of the four elements of float4 i are inside a range (bit j: element 4*i + j); the search is wave-uniform, see above
 template <class Ranges>
 __device__ __forceinline__ unsigned decay_bits4(const Ranges& r, int nr, size_t i) {
     unsigned bits = 0;
@@ -190,110 +227,89 @@ __device__ __forceinline__ bool decays_at(const Ranges& r, int nr, size_t i) {
     int k = nr ? first_open_range(r, nr, (uint32_t)i) : 0;
     return nr && in_range_from(r, nr, k, (uint32_t)i);
 }
+// the bits of index i of a stream taken as V (each_bit's).  An Op asks AFTER it has issued its streams' loads: the table search runs
+// while they are in flight.
+template <class V, class Ranges>
+__device__ __forceinline__ unsigned range_bits(const Ranges& r, int nr, size_t i) {
+    if constexpr (std::is_same<V, float>::value) return decays_at(r, nr, i) ? 1u : 0u;
+    else return decay_bits4(r, nr, i);
+}
 
+// ---- SGD with momentum / weight decay / Nesterov (cnn_sgd_momentum_update; sgdm_one(): common.h) -----------------------------
+// Reads p, g, v and writes p, v (20 B per element, 24 with the nullable `keep`); kMomentum = false neither reads nor writes v.  Weight
+// decay applies inside the ranges of `r` only.
+struct SgdmArgs {
+    float lr, momentum, wd, scale;
+    bool scaled, nesterov;
+    int nr;  // number of ranges; 0 when weight_decay == 0
+};
 template <bool kMomentum, class Ranges>
-__global__ __launch_bounds__(kBlock) void sgdm_vec(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ v,
-                                                   size_t n4, size_t n, const SgdmArgs a, float4* __restrict__ keep, const Ranges r) {
-    if (blockIdx.x == 0 && n4 * 4 + threadIdx.x < n) {
-        float* ps = (float*)p;
-        const float* gs = (const float*)g;
-        float* vs = (float*)v;
-        const size_t i = n4 * 4 + threadIdx.x;
-        const bool decay = decays_at(r, a.nr, i);
-        float vel = kMomentum ? vs[i] : 0.f;
-        if (keep) ((float*)keep)[i] = ps[i];
-        ps[i] = sgdm_one<kMomentum>(ps[i], gs[i], vel, a.lr, a.momentum, a.wd, a.scale, a.scaled, decay, a.nesterov);
-        if (kMomentum) vs[i] = vel;
+struct SgdmOp {
+    float* p;
+    const float* g;
+    float* v;
+    float* keep;
+    SgdmArgs a;
+    Ranges r;
+    template <class V>
+    __device__ __forceinline__ void run(size_t i) const {
+        V pv = at<V>(p, i);
+        const V gv = at<V>(g, i);
+        V vv = kMomentum ? at<V>(v, i) : V{};
+        const unsigned bits = range_bits<V>(r, a.nr, i);  // bit j: the j-th element decays
+        if (keep) at<V>(keep, i) = pv;
+        each_bit<V>(bits, [&](float& pe, float ge, float& ve, bool decay) {
+            pe = sgdm_one<kMomentum>(pe, ge, ve, a.lr, a.momentum, a.wd, a.scale, a.scaled, decay, a.nesterov);
+        }, pv, gv, vv);
+        at<V>(p, i) = pv;
+        if (kMomentum) at<V>(v, i) = vv;
     }
-    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (size_t)gridDim.x * kBlock) {
-        // (the streams' loads are issued first: the table search below runs while they are in flight)
-        float4 pv = p[i];
-        const float4 gv = g[i];
-        float4 vv = kMomentum ? v[i] : float4{0.f, 0.f, 0.f, 0.f};
-        const unsigned bits = decay_bits4(r, a.nr, i);  // bit j: element 4*i + j decays
-        if (keep) keep[i] = pv;
-        pv.x = sgdm_one<kMomentum>(pv.x, gv.x, vv.x, a.lr, a.momentum, a.wd, a.scale, a.scaled, bits & 1u, a.nesterov);
-        pv.y = sgdm_one<kMomentum>(pv.y, gv.y, vv.y, a.lr, a.momentum, a.wd, a.scale, a.scaled, bits & 2u, a.nesterov);
-        pv.z = sgdm_one<kMomentum>(pv.z, gv.z, vv.z, a.lr, a.momentum, a.wd, a.scale, a.scaled, bits & 4u, a.nesterov);
-        pv.w = sgdm_one<kMomentum>(pv.w, gv.w, vv.w, a.lr, a.momentum, a.wd, a.scale, a.scaled, bits & 8u, a.nesterov);
-        p[i] = pv;
-        if (kMomentum) v[i] = vv;
-    }
-}
+};
 template <bool kMomentum, class Ranges>
-__global__ __launch_bounds__(kBlock) void sgdm_scalar(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ v,
-                                                      size_t begin, size_t n, const SgdmArgs a, float* __restrict__ keep, const Ranges r) {
-    for (size_t i = begin + (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
-        const bool decay = decays_at(r, a.nr, i);
-        float vel = kMomentum ? v[i] : 0.f;
-        if (keep) keep[i] = p[i];
-        p[i] = sgdm_one<kMomentum>(p[i], g[i], vel, a.lr, a.momentum, a.wd, a.scale, a.scaled, decay, a.nesterov);
-        if (kMomentum) v[i] = vel;
-    }
-}
+__global__ __launch_bounds__(kBlock) void sgdm_vec(const SgdmOp<kMomentum, Ranges> op, size_t n) { stream_walk<true>(op, 0, n); }
+template <bool kMomentum, class Ranges>
+__global__ __launch_bounds__(kBlock) void sgdm_scalar(const SgdmOp<kMomentum, Ranges> op, size_t begin, size_t n) { stream_walk<false>(op, begin, n); }
 
 // ---- Adam / AdamW (cnn_adam_update; adam_one(): common.h) -------------------------------------------------------------------------
-// sgdm_vec's shape with four streams: reads p, g, m, v and writes p, m, v (28 B per element, 32 with keep); the same range structs
-// and wave-uniform search decide where weight decay applies.  Three correctly rounded divide / root sequences per element.
+// Four streams: reads p, g, m, v and writes p, m, v (28 B per element, 32 with keep); weight decay inside the ranges of `r` only.
+// Three correctly rounded divide / root sequences per element.
 struct AdamArgs {
     AdamScalars s;
     int nr;  // number of ranges; 0 when weight_decay == 0
 };
-
 template <class Ranges>
-__global__ __launch_bounds__(kBlock) void adam_vec(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ m,
-                                                   float4* __restrict__ v, size_t n4, size_t n, const AdamArgs a, float4* __restrict__ keep,
-                                                   const Ranges r) {
-    if (blockIdx.x == 0 && n4 * 4 + threadIdx.x < n) {
-        float* ps = (float*)p;
-        const float* gs = (const float*)g;
-        float* ms = (float*)m;
-        float* vs = (float*)v;
-        const size_t i = n4 * 4 + threadIdx.x;
-        const bool decay = decays_at(r, a.nr, i);
-        float mi = ms[i], vi = vs[i];
-        if (keep) ((float*)keep)[i] = ps[i];
-        ps[i] = adam_one(ps[i], gs[i], mi, vi, a.s, decay);
-        ms[i] = mi;
-        vs[i] = vi;
+struct AdamOp {
+    float* p;
+    const float* g;
+    float* m;
+    float* v;
+    float* keep;
+    AdamArgs a;
+    Ranges r;
+    template <class V>
+    __device__ __forceinline__ void run(size_t i) const {
+        V pv = at<V>(p, i);
+        const V gv = at<V>(g, i);
+        V mv = at<V>(m, i);
+        V vv = at<V>(v, i);
+        const unsigned bits = range_bits<V>(r, a.nr, i);  // bit j: the j-th element decays
+        if (keep) at<V>(keep, i) = pv;
+        each_bit<V>(bits, [&](float& pe, float ge, float& me, float& ve, bool decay) { pe = adam_one(pe, ge, me, ve, a.s, decay); }, pv, gv, mv, vv);
+        at<V>(p, i) = pv;
+        at<V>(m, i) = mv;
+        at<V>(v, i) = vv;
     }
-    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (size_t)gridDim.x * kBlock) {
-        // (the streams' loads are issued first: the table search below runs while they are in flight)
-        float4 pv = p[i];
-        const float4 gv = g[i];
-        float4 mv = m[i];
-        float4 vv = v[i];
-        const unsigned bits = decay_bits4(r, a.nr, i);  // bit j: element 4*i + j decays
-        if (keep) keep[i] = pv;
-        pv.x = adam_one(pv.x, gv.x, mv.x, vv.x, a.s, bits & 1u);
-        pv.y = adam_one(pv.y, gv.y, mv.y, vv.y, a.s, bits & 2u);
-        pv.z = adam_one(pv.z, gv.z, mv.z, vv.z, a.s, bits & 4u);
-        pv.w = adam_one(pv.w, gv.w, mv.w, vv.w, a.s, bits & 8u);
-        p[i] = pv;
-        m[i] = mv;
-        v[i] = vv;
-    }
-}
+};
 template <class Ranges>
-__global__ __launch_bounds__(kBlock) void adam_scalar(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                      float* __restrict__ v, size_t begin, size_t n, const AdamArgs a, float* __restrict__ keep,
-                                                      const Ranges r) {
-    for (size_t i = begin + (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
-        const bool decay = decays_at(r, a.nr, i);
-        float mi = m[i], vi = v[i];
-        if (keep) keep[i] = p[i];
-        p[i] = adam_one(p[i], g[i], mi, vi, a.s, decay);
-        m[i] = mi;
-        v[i] = vi;
-    }
-}
+__global__ __launch_bounds__(kBlock) void adam_vec(const AdamOp<Ranges> op, size_t n) { stream_walk<true>(op, 0, n); }
+template <class Ranges>
+__global__ __launch_bounds__(kBlock) void adam_scalar(const AdamOp<Ranges> op, size_t begin, size_t n) { stream_walk<false>(op, begin, n); }
 
 // ---- exponential moving average of the parameters (cnn_ema_update) ----------------------------------------------------------------
-// gacc_vec's shape with sgdm_vec's range table: reads ema, p and writes ema (12 B per element).  The same range structs and
-// wave-uniform search decide which elements are AVERAGED (ema = decay * ema + omd * p, two products and one sum, each rounded); the
-// others -- BatchNorm2D's moving statistics -- take p's bits.  decay == 0 or an empty table averages nothing: that call is
-// gacc_vec<true> / gacc_scalar<true> (acc = g: loads and stores only, ema is not read, 8 B per element) under the names
-// ema_vec_copy / ema_scalar_copy.
+// Reads ema, p and writes ema (12 B per element).  The ranges of `r` are the elements that are AVERAGED (ema = decay * ema + omd * p,
+// two products and one sum, each rounded); the others -- BatchNorm2D's moving statistics -- take p's bits.  decay == 0 or an empty
+// table averages nothing: that call is GaccOp<true> (acc = g: loads and stores only, ema is not read, 8 B per element) under the
+// names ema_vec_copy / ema_scalar_copy.
 struct EmaArgs {
     float decay, omd;
     int nr;  // number of ranges, >= 1
@@ -305,66 +321,48 @@ __device__ __forceinline__ float ema_one(float e, float p, float decay, float om
     const float sum = de + op;
     return averaged ? sum : p;  // (a select: p's bits as they are)
 }
-
 template <class Ranges>
-__global__ __launch_bounds__(kBlock) void ema_vec(float4* __restrict__ ema, const float4* __restrict__ p, size_t n4, size_t n, const EmaArgs a,
-                                                  const Ranges r) {
-    if (blockIdx.x == 0 && n4 * 4 + threadIdx.x < n) {
-        float* es = (float*)ema;
-        const float* ps = (const float*)p;
-        const size_t i = n4 * 4 + threadIdx.x;
-        es[i] = ema_one(es[i], ps[i], a.decay, a.omd, decays_at(r, a.nr, i));
+struct EmaOp {
+    float* ema;
+    const float* p;
+    EmaArgs a;
+    Ranges r;
+    template <class V>
+    __device__ __forceinline__ void run(size_t i) const {
+        V ev = at<V>(ema, i);
+        const V pv = at<V>(p, i);
+        const unsigned bits = range_bits<V>(r, a.nr, i);  // bit j: the j-th element is averaged
+        each_bit<V>(bits, [&](float& ee, float pe, bool averaged) { ee = ema_one(ee, pe, a.decay, a.omd, averaged); }, ev, pv);
+        at<V>(ema, i) = ev;
     }
-    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (size_t)gridDim.x * kBlock) {
-        // (the streams' loads are issued first: the table search below runs while they are in flight)
-        float4 ev = ema[i];
-        const float4 pv = p[i];
-        const unsigned bits = decay_bits4(r, a.nr, i);  // bit j: element 4*i + j is averaged
-        ev.x = ema_one(ev.x, pv.x, a.decay, a.omd, bits & 1u);
-        ev.y = ema_one(ev.y, pv.y, a.decay, a.omd, bits & 2u);
-        ev.z = ema_one(ev.z, pv.z, a.decay, a.omd, bits & 4u);
-        ev.w = ema_one(ev.w, pv.w, a.decay, a.omd, bits & 8u);
-        ema[i] = ev;
-    }
-}
+};
 template <class Ranges>
-__global__ __launch_bounds__(kBlock) void ema_scalar(float* __restrict__ ema, const float* __restrict__ p, size_t n, const EmaArgs a,
-                                                     const Ranges r) {
-    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock)
-        ema[i] = ema_one(ema[i], p[i], a.decay, a.omd, decays_at(r, a.nr, i));
-}
+__global__ __launch_bounds__(kBlock) void ema_vec(const EmaOp<Ranges> op, size_t n) { stream_walk<true>(op, 0, n); }
+template <class Ranges>
+__global__ __launch_bounds__(kBlock) void ema_scalar(const EmaOp<Ranges> op, size_t begin, size_t n) { stream_walk<false>(op, begin, n); }
 
 // ---- exchange of two disjoint buffers (cnn_arena_swap) -------------------------------------------------------------------------------
-// gacc_vec's shape: loads and stores only, every bit pattern survives; reads and writes both (16 B per element).  The buffers do
-// not overlap (checked by the entry), so every element is read before either copy of it is written.
-__global__ __launch_bounds__(kBlock) void aswap_vec(float4* __restrict__ a, float4* __restrict__ b, size_t n4, size_t n) {
-    if (blockIdx.x == 0 && n4 * 4 + threadIdx.x < n) {
-        float* as = (float*)a;
-        float* bs = (float*)b;
-        const size_t i = n4 * 4 + threadIdx.x;
-        const float av = as[i], bv = bs[i];
-        as[i] = bv;
-        bs[i] = av;
+// Loads and stores only, every bit pattern survives; reads and writes both (16 B per element).  The buffers do not overlap (checked
+// by the entry), so every element is read before either copy of it is written.
+struct SwapOp {
+    float* a;
+    float* b;
+    template <class V>
+    __device__ __forceinline__ void run(size_t i) const {
+        const V av = at<V>(a, i);
+        const V bv = at<V>(b, i);
+        at<V>(a, i) = bv;
+        at<V>(b, i) = av;
     }
-    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (size_t)gridDim.x * kBlock) {
-        const float4 av = a[i];
-        const float4 bv = b[i];
-        a[i] = bv;
-        b[i] = av;
-    }
-}
-__global__ __launch_bounds__(kBlock) void aswap_scalar(float* __restrict__ a, float* __restrict__ b, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
-        const float av = a[i], bv = b[i];
-        a[i] = bv;
-        b[i] = av;
-    }
-}
+};
+__global__ __launch_bounds__(kBlock) void aswap_vec(const SwapOp op, size_t n) { stream_walk<true>(op, 0, n); }
+__global__ __launch_bounds__(kBlock) void aswap_scalar(const SwapOp op, size_t begin, size_t n) { stream_walk<false>(op, begin, n); }
 
 // ---- clipping by the global L2 norm (cnn_clip_grad_norm) ----------------------------------------------------------------------------
 // Three launches, no host round trip, no floating-point atomics:
-//   clip_partial : every workgroup sums (double)g * (double)g over its grid-stride share (per lane, then the wave's shuffle tree, then
-//                  the four waves in order) into partial[blockIdx.x] -- the products are exact in fp64;
+//   clip_partial : every workgroup sums (double)g * (double)g over its share of the walk (per lane in the walk's order -- the tail
+//                  element, then x, y, z, w of each float4 --, then the wave's shuffle tree, then the four waves in order) into
+//                  partial[blockIdx.x] -- the products are exact in fp64;
 //   clip_finish  : ONE workgroup adds the partials (each lane its strided share in ascending order, then the same tree), takes the
 //                  root, and writes stats = {total norm, coefficient};
 //   clip_scale   : g *= coefficient; every workgroup returns at once when the coefficient is 1 (the arena is not written).
@@ -386,32 +384,35 @@ __device__ __forceinline__ double block_sum(double x, double* lds) {
     return total;  // (valid in thread 0)
 }
 
+struct SumSqOp {
+    const float* g;
+    double acc;  // the lane's sum
+    template <class V>
+    __device__ __forceinline__ void run(size_t i) {
+        const V q = at<V>(g, i);
+        each<V>([&](float ge) {
+            const double x = (double)ge;
+            acc += x * x;
+        }, q);
+    }
+};
+struct ScaleOp {
+    float* g;
+    float coef;
+    template <class V>
+    __device__ __forceinline__ void run(size_t i) const {
+        V q = at<V>(g, i);
+        each<V>([&](float& ge) { ge *= coef; }, q);
+        at<V>(g, i) = q;
+    }
+};
+
 template <bool kVec>
 __global__ __launch_bounds__(kBlock) void clip_partial(const float* __restrict__ g, size_t n, double* __restrict__ partial) {
     __shared__ double lds[kBlock / kWave];
-    double acc = 0.0;
-    if (kVec) {
-        const size_t n4 = n / 4;
-        const float4* g4 = (const float4*)g;
-        if (blockIdx.x == 0 && n4 * 4 + threadIdx.x < n) {
-            const double x = (double)g[n4 * 4 + threadIdx.x];
-            acc += x * x;
-        }
-        for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (size_t)gridDim.x * kBlock) {
-            const float4 q = g4[i];
-            const double x = (double)q.x, y = (double)q.y, z = (double)q.z, w = (double)q.w;
-            acc += x * x;
-            acc += y * y;
-            acc += z * z;
-            acc += w * w;
-        }
-    } else {
-        for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
-            const double x = (double)g[i];
-            acc += x * x;
-        }
-    }
-    const double total = block_sum(acc, lds);
+    SumSqOp op{g, 0.0};
+    stream_walk<kVec>(op, 0, n);
+    const double total = block_sum(op.acc, lds);
     if (threadIdx.x == 0) partial[blockIdx.x] = total;
 }
 
@@ -436,18 +437,8 @@ template <bool kVec>
 __global__ __launch_bounds__(kBlock) void clip_scale(float* __restrict__ g, size_t n, const float* __restrict__ stats) {
     const float coef = stats[1];
     if (!(coef < 1.f)) return;
-    if (kVec) {
-        const size_t n4 = n / 4;
-        float4* g4 = (float4*)g;
-        if (blockIdx.x == 0 && n4 * 4 + threadIdx.x < n) g[n4 * 4 + threadIdx.x] *= coef;
-        for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (size_t)gridDim.x * kBlock) {
-            float4 q = g4[i];
-            q.x *= coef; q.y *= coef; q.z *= coef; q.w *= coef;
-            g4[i] = q;
-        }
-    } else {
-        for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) g[i] *= coef;
-    }
+    const ScaleOp op{g, coef};
+    stream_walk<kVec>(op, 0, n);
 }
 
 // func.cpp:6-12
@@ -497,8 +488,48 @@ __global__ __launch_bounds__(kBlock) void softmax_xent_kernel(const float* __res
     if (threadIdx.x == 0 && loss_sum) loss_sum[0] = -running;
 }
 
-// ---- host side shared by the two arena update rules (cnn_sgd_momentum_update, cnn_adam_update) ------------------------------------
-// the decay-range table of an update entry: n fits the 32-bit table, the ranges are there, sorted, disjoint, non-empty and inside [0, n)
+// ---- host side: the one launcher of the streaming shape -----------------------------------------------------------------------------
+// Which launches an entry makes over n elements, and how the launch log shows them:
+//   kTailRides : ONE launch -- the float4 kernel over all n (the n % 4 trailing elements ride in its workgroup 0) when every pointer
+//                is 16-byte aligned and n >= 4, the scalar kernel alone otherwise;
+//   kSplit     : the float4 kernel over n / 4 * 4 elements under the same condition, then the scalar kernel over the rest (ReLU);
+//   kClip      : kTailRides on clip_grid, the float4 kernel whatever n is, no "tail" in the scalar kernel's geometry (the clip passes).
+// vec(grid, n_vec) / scalar(grid, begin) launch and return nothing.  The geometry is "n=<n>" for the float4 kernel and "tail n=<what
+// the scalar kernel covers>" for the other, with " ranges=<nr>" behind it where nr >= 0.
+enum StreamForm { kTailRides, kSplit, kClip };
+
+// grid of the clip kernels: stream_grid, never more than the workspace holds
+inline unsigned clip_grid(size_t work_items) {
+    const unsigned g = stream_grid(work_items, kBlock);
+    return g > (unsigned)kClipMaxBlocks ? (unsigned)kClipMaxBlocks : g;
+}
+
+template <class Vec, class Scalar>
+int launch_stream(hipStream_t s, const char* vec_name, const char* scalar_name, StreamForm form, bool all_aligned, size_t n, int nr,
+                  const Vec& vec, const Scalar& scalar) {
+    const auto grid = [&](size_t work_items) { return form == kClip ? clip_grid(work_items) : stream_grid(work_items, kBlock); };
+    size_t begin = 0;
+    if (all_aligned && (n >= 4 || form == kClip)) {
+        begin = form == kSplit ? n / 4 * 4 : n;
+        CNN_KLAUNCH(s, vec_name, vec(grid(n / 4), begin), nr < 0 ? "n=%zu" : "n=%zu ranges=%d", n, nr);
+    }
+    if (begin < n) {
+        const char* tag = form == kClip ? "n=%zu" : nr < 0 ? "tail n=%zu" : "tail n=%zu ranges=%d";
+        CNN_KLAUNCH(s, scalar_name, scalar(grid(n - begin), begin), tag, n - begin, nr);
+    }
+    return CNN_AMD_OK;
+}
+// ... of an Op and its two wrappers
+template <class Op>
+int launch_stream(hipStream_t s, const char* vec_name, void (*vec)(Op, size_t), const char* scalar_name, void (*scalar)(Op, size_t, size_t),
+                  StreamForm form, bool all_aligned, size_t n, int nr, const Op& op) {
+    return launch_stream(
+        s, vec_name, scalar_name, form, all_aligned, n, nr, [&](unsigned grid, size_t n_vec) { vec<<<grid, kBlock, 0, s>>>(op, n_vec); },
+        [&](unsigned grid, size_t begin) { scalar<<<grid, kBlock, 0, s>>>(op, begin, n); });
+}
+
+// ---- host side shared by the arena entries with a range table (cnn_sgd_momentum_update, cnn_adam_update, cnn_ema_update) ---------------
+// the range table of an entry: n fits the 32-bit table, the ranges are there, sorted, disjoint, non-empty and inside [0, n)
 int check_decay_ranges(const char* entry, size_t n, const uint32_t* decay_ranges, const uint32_t* decay_ranges_dev, size_t n_ranges) {
     CNN_REQUIRE(n <= (size_t)0xFFFFFFFFu - 4 * kWave, "%s: n=%zu exceeds the 32-bit range table: step the arena in pieces", entry, n);
     CNN_REQUIRE(n_ranges <= n && (n_ranges == 0 || decay_ranges), "%s: null decay_ranges / n_ranges=%zu with n=%zu", entry, n_ranges, n);
@@ -516,48 +547,18 @@ int check_decay_ranges(const char* entry, size_t n, const uint32_t* decay_ranges
 // calls launch(ranges) with the first nr ranges by value in the kernel arguments, or with the device table beyond CNN_SGD_INLINE_RANGES
 template <class Launch>
 int with_ranges(int nr, const uint32_t* decay_ranges, const uint32_t* decay_ranges_dev, const Launch& launch) {
-    if (nr > CNN_SGD_INLINE_RANGES) return launch(DeviceRanges{decay_ranges_dev});
+    if (nr > CNN_SGD_INLINE_RANGES) return launch(DeviceRanges{(DeviceRanges::Table)decay_ranges_dev});
     InlineRanges r;
     for (int k = 0; k < 2 * CNN_SGD_INLINE_RANGES; ++k) r.be[k] = k < 2 * nr ? decay_ranges[k] : 0u;
     return launch(r);
-}
-
-// one launch of an update rule over n elements: the float4 kernel (its scalar tail rides in workgroup 0) when every pointer is 16-byte
-// aligned, the scalar kernel alone otherwise, like cnn_sgd_update_keep.  vec(grid, n4) / scalar(grid) launch and return nothing.
-template <class Vec, class Scalar>
-int launch_update(hipStream_t s, const char* vec_name, const char* scalar_name, bool all_aligned, size_t n, int nr, const Vec& vec,
-                  const Scalar& scalar) {
-    if (all_aligned && n >= 4) {
-        const size_t n4 = n / 4;
-        CNN_KLAUNCH(s, vec_name, vec(stream_grid(n4, kBlock), n4), "n=%zu ranges=%d", n, nr);
-    } else {
-        CNN_KLAUNCH(s, scalar_name, scalar(stream_grid(n, kBlock)), "tail n=%zu ranges=%d", n, nr);
-    }
-    return CNN_AMD_OK;
 }
 
 template <bool kMomentum, class Ranges>
 int launch_sgdm(float* params, const float* grads, float* velocity, size_t n, const SgdmArgs& a, float* previous, const Ranges& r,
                 hipStream_t s) {
     const bool aligned = aligned16(params) && aligned16(grads) && (!kMomentum || aligned16(velocity)) && (previous == nullptr || aligned16(previous));
-    return launch_update(
-        s, "sgdm_vec", "sgdm_scalar", aligned, n, a.nr,
-        [&](unsigned grid, size_t n4) {
-            sgdm_vec<kMomentum, Ranges><<<grid, kBlock, 0, s>>>((float4*)params, (const float4*)grads, (float4*)velocity, n4, n, a, (float4*)previous, r);
-        },
-        [&](unsigned grid) { sgdm_scalar<kMomentum, Ranges><<<grid, kBlock, 0, s>>>(params, grads, velocity, 0, n, a, previous, r); });
-}
-
-template <class Ranges>
-int launch_adam(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n, const AdamArgs& a, float* previous,
-                const Ranges& r, hipStream_t s) {
-    const bool aligned = aligned16(params) && aligned16(grads) && aligned16(exp_avg) && aligned16(exp_avg_sq) && (previous == nullptr || aligned16(previous));
-    return launch_update(
-        s, "adam_vec", "adam_scalar", aligned, n, a.nr,
-        [&](unsigned grid, size_t n4) {
-            adam_vec<Ranges><<<grid, kBlock, 0, s>>>((float4*)params, (const float4*)grads, (float4*)exp_avg, (float4*)exp_avg_sq, n4, n, a, (float4*)previous, r);
-        },
-        [&](unsigned grid) { adam_scalar<Ranges><<<grid, kBlock, 0, s>>>(params, grads, exp_avg, exp_avg_sq, 0, n, a, previous, r); });
+    return launch_stream(s, "sgdm_vec", sgdm_vec<kMomentum, Ranges>, "sgdm_scalar", sgdm_scalar<kMomentum, Ranges>, kTailRides, aligned, n, a.nr,
+                         SgdmOp<kMomentum, Ranges>{params, grads, velocity, previous, a, r});
 }
 
 // the scalars of one Adam step that do not depend on the element (common.h, adam_one): plain host arithmetic, every fp32 operation
@@ -581,13 +582,6 @@ AdamScalars adam_scalars(const cnn_adam_options& o, float grad_scale) {
     a.decoupled = o.decoupled != 0;
     return a;
 }
-
-// grid of the clip kernels: stream_grid, never more than the workspace holds
-inline unsigned clip_grid(size_t work_items) {
-    const unsigned g = stream_grid(work_items, kBlock);
-    return g > (unsigned)kClipMaxBlocks ? (unsigned)kClipMaxBlocks : g;
-}
-
 
 // ---- AlexNet::grad_cam (alexnet.cpp:107-140) on a [B][C][H][W] feature map -------------------------------------------------
 // weights[b][o] = (sum_i fea[b][o][i]) / area, sequential in i (:111-119; the reference takes the channel mean of the FEATURE MAP,
@@ -664,37 +658,15 @@ extern "C" {
 int cnn_relu_forward(const float* x, float* y, size_t n, void* stream) {
     if (n == 0) return CNN_AMD_OK;
     CNN_REQUIRE(x && y, "cnn_relu_forward: null pointer");
-    hipStream_t s = as_stream(stream);
-    size_t done = 0;
-    if (aligned16(x) && aligned16(y) && n >= 4) {
-        const size_t n4 = n / 4;
-        CNN_KLAUNCH(s, "relu_fwd_vec", (relu_fwd_vec<<<stream_grid(n4, kBlock), kBlock, 0, s>>>((const float4*)x, (float4*)y, n4)),
-                    "n=%zu", n);
-        done = n4 * 4;
-    }
-    if (done < n) {
-        CNN_KLAUNCH(s, "relu_fwd_scalar", (relu_fwd_scalar<<<stream_grid(n - done, kBlock), kBlock, 0, s>>>(x, y, done, n)),
-                    "tail n=%zu", n - done);
-    }
-    return CNN_AMD_OK;
+    return launch_stream(as_stream(stream), "relu_fwd_vec", relu_fwd_vec, "relu_fwd_scalar", relu_fwd_scalar, kSplit, aligned16(x) && aligned16(y), n, -1,
+                         ReluFwdOp{x, y});
 }
 
 int cnn_relu_backward(const float* y, float* dy, size_t n, void* stream) {
     if (n == 0) return CNN_AMD_OK;
     CNN_REQUIRE(y && dy, "cnn_relu_backward: null pointer");
-    hipStream_t s = as_stream(stream);
-    size_t done = 0;
-    if (aligned16(y) && aligned16(dy) && n >= 4) {
-        const size_t n4 = n / 4;
-        CNN_KLAUNCH(s, "relu_bwd_vec", (relu_bwd_vec<<<stream_grid(n4, kBlock), kBlock, 0, s>>>((const float4*)y, (float4*)dy, n4)),
-                    "n=%zu", n);
-        done = n4 * 4;
-    }
-    if (done < n) {
-        CNN_KLAUNCH(s, "relu_bwd_scalar", (relu_bwd_scalar<<<stream_grid(n - done, kBlock), kBlock, 0, s>>>(y, dy, done, n)),
-                    "tail n=%zu", n - done);
-    }
-    return CNN_AMD_OK;
+    return launch_stream(as_stream(stream), "relu_bwd_vec", relu_bwd_vec, "relu_bwd_scalar", relu_bwd_scalar, kSplit, aligned16(y) && aligned16(dy), n, -1,
+                         ReluBwdOp{y, dy});
 }
 
 int cnn_sgd_update(float* params, const float* grads, size_t n, float lr, float grad_scale, void* stream) {
@@ -704,23 +676,9 @@ int cnn_sgd_update(float* params, const float* grads, size_t n, float lr, float 
 int cnn_sgd_update_keep(float* params, const float* grads, size_t n, float lr, float grad_scale, float* previous, void* stream) {
     if (n == 0) return CNN_AMD_OK;
     CNN_REQUIRE(params && grads, "cnn_sgd_update: null pointer");
-    hipStream_t s = as_stream(stream);
-    const bool scaled = grad_scale != 1.0f;
-    size_t done = 0;
-    if (aligned16(params) && aligned16(grads) && (previous == nullptr || aligned16(previous)) && n >= 4) {
-        const size_t n4 = n / 4;
-        CNN_KLAUNCH(s, "sgd_vec",
-                    (sgd_vec<<<stream_grid(n4, kBlock), kBlock, 0, s>>>((float4*)params, (const float4*)grads, n4, n, lr,
-                                                                       grad_scale, scaled, (float4*)previous)),
-                    "n=%zu", n);
-        done = n;
-    }
-    if (done < n) {
-        CNN_KLAUNCH(s, "sgd_scalar",
-                    (sgd_scalar<<<stream_grid(n - done, kBlock), kBlock, 0, s>>>(params, grads, done, n, lr, grad_scale, scaled, previous)),
-                    "tail n=%zu", n - done);
-    }
-    return CNN_AMD_OK;
+    const bool aligned = aligned16(params) && aligned16(grads) && (previous == nullptr || aligned16(previous));
+    return launch_stream(as_stream(stream), "sgd_vec", sgd_vec, "sgd_scalar", sgd_scalar, kTailRides, aligned, n, -1,
+                         SgdOp{params, grads, previous, lr, grad_scale, grad_scale != 1.0f});
 }
 
 int cnn_grad_accumulate(float* acc, const float* grads, size_t n, int first, void* stream) {
@@ -728,23 +686,9 @@ int cnn_grad_accumulate(float* acc, const float* grads, size_t n, int first, voi
     CNN_REQUIRE(n != 0, "cnn_grad_accumulate: n=0");
     CNN_REQUIRE(acc != grads, "cnn_grad_accumulate: acc and grads are the same buffer");
     hipStream_t s = as_stream(stream);
-    if (aligned16(acc) && aligned16(grads) && n >= 4) {
-        const size_t n4 = n / 4;
-        const unsigned grid = stream_grid(n4, kBlock);
-        if (first) {
-            CNN_KLAUNCH(s, "gacc_vec_first", (gacc_vec<true><<<grid, kBlock, 0, s>>>((float4*)acc, (const float4*)grads, n4, n)), "n=%zu", n);
-        } else {
-            CNN_KLAUNCH(s, "gacc_vec_add", (gacc_vec<false><<<grid, kBlock, 0, s>>>((float4*)acc, (const float4*)grads, n4, n)), "n=%zu", n);
-        }
-    } else {
-        const unsigned grid = stream_grid(n, kBlock);
-        if (first) {
-            CNN_KLAUNCH(s, "gacc_scalar_first", (gacc_scalar<true><<<grid, kBlock, 0, s>>>(acc, grads, n)), "tail n=%zu", n);
-        } else {
-            CNN_KLAUNCH(s, "gacc_scalar_add", (gacc_scalar<false><<<grid, kBlock, 0, s>>>(acc, grads, n)), "tail n=%zu", n);
-        }
-    }
-    return CNN_AMD_OK;
+    const bool aligned = aligned16(acc) && aligned16(grads);
+    return first ? launch_stream(s, "gacc_vec_first", gacc_vec<true>, "gacc_scalar_first", gacc_scalar<true>, kTailRides, aligned, n, -1, GaccOp<true>{acc, grads})
+                 : launch_stream(s, "gacc_vec_add", gacc_vec<false>, "gacc_scalar_add", gacc_scalar<false>, kTailRides, aligned, n, -1, GaccOp<false>{acc, grads});
 }
 
 float cnn_ema_decay_at(float decay, int warmup, uint64_t updates_done) {
@@ -769,22 +713,15 @@ int cnn_ema_update(float* ema, const float* params, size_t n, float decay, const
     if (int rc = check_decay_ranges("cnn_ema_update", n, avg_ranges, avg_ranges_dev, n_ranges)) return rc;
     hipStream_t s = as_stream(stream);
     const bool aligned = aligned16(ema) && aligned16(params);
-    if (decay == 0.f || n_ranges == 0) {  // nothing is averaged: the copy of the bits
-        return launch_update(
-            s, "ema_vec_copy", "ema_scalar_copy", aligned, n, 0,
-            [&](unsigned grid, size_t n4) { gacc_vec<true><<<grid, kBlock, 0, s>>>((float4*)ema, (const float4*)params, n4, n); },
-            [&](unsigned grid) { gacc_scalar<true><<<grid, kBlock, 0, s>>>(ema, params, n); });
-    }
+    if (decay == 0.f || n_ranges == 0)  // nothing is averaged: the copy of the bits
+        return launch_stream(s, "ema_vec_copy", gacc_vec<true>, "ema_scalar_copy", gacc_scalar<true>, kTailRides, aligned, n, 0, GaccOp<true>{ema, params});
     EmaArgs a;
     a.decay = decay;
     a.omd = 1.f - decay;
     a.nr = (int)n_ranges;
     return with_ranges(a.nr, avg_ranges, avg_ranges_dev, [&](const auto& r) {
         using Ranges = std::decay_t<decltype(r)>;
-        return launch_update(
-            s, "ema_vec", "ema_scalar", aligned, n, a.nr,
-            [&](unsigned grid, size_t n4) { ema_vec<Ranges><<<grid, kBlock, 0, s>>>((float4*)ema, (const float4*)params, n4, n, a, r); },
-            [&](unsigned grid) { ema_scalar<Ranges><<<grid, kBlock, 0, s>>>(ema, params, n, a, r); });
+        return launch_stream(s, "ema_vec", ema_vec<Ranges>, "ema_scalar", ema_scalar<Ranges>, kTailRides, aligned, n, a.nr, EmaOp<Ranges>{ema, params, a, r});
     });
 }
 
@@ -792,11 +729,7 @@ int cnn_arena_swap(float* a, float* b, size_t n, void* stream) {
     CNN_REQUIRE(a && b, "cnn_arena_swap: null pointer");
     CNN_REQUIRE(n != 0, "cnn_arena_swap: n=0");
     CNN_REQUIRE(!floats_overlap(a, b, n), "cnn_arena_swap: a and b are the same buffer or overlap");
-    hipStream_t s = as_stream(stream);
-    return launch_update(
-        s, "aswap_vec", "aswap_scalar", aligned16(a) && aligned16(b), n, 0,
-        [&](unsigned grid, size_t n4) { aswap_vec<<<grid, kBlock, 0, s>>>((float4*)a, (float4*)b, n4, n); },
-        [&](unsigned grid) { aswap_scalar<<<grid, kBlock, 0, s>>>(a, b, n); });
+    return launch_stream(as_stream(stream), "aswap_vec", aswap_vec, "aswap_scalar", aswap_scalar, kTailRides, aligned16(a) && aligned16(b), n, 0, SwapOp{a, b});
 }
 
 // (the two update entries differ in when n == 0 returns: this one returns OK before it looks at any argument, cnn_adam_update validates
@@ -840,8 +773,12 @@ int cnn_adam_update(float* params, const float* grads, float* exp_avg, float* ex
     AdamArgs a;
     a.s = adam_scalars(*opt, grad_scale);
     a.nr = opt->weight_decay != 0.f ? (int)n_ranges : 0;
-    return with_ranges(a.nr, decay_ranges, decay_ranges_dev,
-                       [&](const auto& r) { return launch_adam(params, grads, exp_avg, exp_avg_sq, n, a, previous, r, s); });
+    const bool aligned = aligned16(params) && aligned16(grads) && aligned16(exp_avg) && aligned16(exp_avg_sq) && (previous == nullptr || aligned16(previous));
+    return with_ranges(a.nr, decay_ranges, decay_ranges_dev, [&](const auto& r) {
+        using Ranges = std::decay_t<decltype(r)>;
+        return launch_stream(s, "adam_vec", adam_vec<Ranges>, "adam_scalar", adam_scalar<Ranges>, kTailRides, aligned, n, a.nr,
+                             AdamOp<Ranges>{params, grads, exp_avg, exp_avg_sq, previous, a, r});
+    });
 }
 
 size_t cnn_clip_grad_norm_workspace_bytes(size_t n) {
@@ -861,21 +798,19 @@ int cnn_clip_grad_norm(float* grads, size_t n, float max_norm, float grad_scale,
     CNN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0, "cnn_clip_grad_norm: the workspace must be 8-byte aligned");
     hipStream_t s = as_stream(stream);
     double* partial = (double*)workspace;
-    const bool vec = aligned16(grads);
-    const unsigned grid = clip_grid(vec ? n / 4 : n);
-    if (vec) {
-        CNN_KLAUNCH(s, "clip_partial_vec", (clip_partial<true><<<grid, kBlock, 0, s>>>(grads, n, partial)), "n=%zu", n);
-    } else {
-        CNN_KLAUNCH(s, "clip_partial_scalar", (clip_partial<false><<<grid, kBlock, 0, s>>>(grads, n, partial)), "n=%zu", n);
-    }
-    CNN_KLAUNCH(s, "clip_finish", (clip_finish<<<1, kBlock, 0, s>>>(partial, (int)grid, max_norm, grad_scale, grad_scale != 1.0f, stats_dev)),
-                "partials=%u", grid);
-    if (vec) {
-        CNN_KLAUNCH(s, "clip_scale_vec", (clip_scale<true><<<grid, kBlock, 0, s>>>(grads, n, stats_dev)), "n=%zu", n);
-    } else {
-        CNN_KLAUNCH(s, "clip_scale_scalar", (clip_scale<false><<<grid, kBlock, 0, s>>>(grads, n, stats_dev)), "n=%zu", n);
-    }
-    return CNN_AMD_OK;
+    const bool aligned = aligned16(grads);
+    unsigned partials = 0;  // the grid of the first pass
+    if (int rc = launch_stream(
+            s, "clip_partial_vec", "clip_partial_scalar", kClip, aligned, n, -1,
+            [&](unsigned grid, size_t) { clip_partial<true><<<grid, kBlock, 0, s>>>(grads, n, partial), partials = grid; },
+            [&](unsigned grid, size_t) { clip_partial<false><<<grid, kBlock, 0, s>>>(grads, n, partial), partials = grid; }))
+        return rc;
+    CNN_KLAUNCH(s, "clip_finish", (clip_finish<<<1, kBlock, 0, s>>>(partial, (int)partials, max_norm, grad_scale, grad_scale != 1.0f, stats_dev)),
+                "partials=%u", partials);
+    return launch_stream(
+        s, "clip_scale_vec", "clip_scale_scalar", kClip, aligned, n, -1,
+        [&](unsigned grid, size_t) { clip_scale<true><<<grid, kBlock, 0, s>>>(grads, n, stats_dev); },
+        [&](unsigned grid, size_t) { clip_scale<false><<<grid, kBlock, 0, s>>>(grads, n, stats_dev); });
 }
 
 int cnn_softmax_xent(const float* logits, const int32_t* labels, float* probs, float* delta, float* loss_sum, int B,
@@ -894,7 +829,7 @@ int cnn_dropout_forward(const float* x, float* y, int B, int C, int H, int W, in
     CNN_REQUIRE(x && y && B > 0 && C > 0 && H > 0 && W > 0 && dropped_channels >= 0 && dropped_channels <= C, "cnn_dropout_forward: bad arguments");
     const size_t n = (size_t)B * C * H * W;
     hipStream_t s = as_stream(stream);
-    CNN_KLAUNCH(s, "dropout_fwd", (dropout_fwd<<<stream_grid(n, kBlock), kBlock, 0, s>>>(x, y, n, C, H * W, dropped_channels, training, keep)),
+    CNN_KLAUNCH(s, "dropout_fwd", (dropout_fwd<<<stream_grid(n, kBlock), kBlock, 0, s>>>(DropoutFwdOp{x, y, C, H * W, dropped_channels, training, keep}, n)),
                 "n=%zu", n);
     return CNN_AMD_OK;
 }
@@ -903,7 +838,7 @@ int cnn_dropout_backward(float* dy_inout, int B, int C, int H, int W, int droppe
     CNN_REQUIRE(dy_inout && B > 0 && C > 0 && H > 0 && W > 0 && dropped_channels >= 0 && dropped_channels <= C, "cnn_dropout_backward: bad arguments");
     const size_t n = (size_t)B * C * H * W;
     hipStream_t s = as_stream(stream);
-    CNN_KLAUNCH(s, "dropout_bwd", (dropout_bwd<<<stream_grid(n, kBlock), kBlock, 0, s>>>(dy_inout, n, C, H * W, dropped_channels)), "n=%zu", n);
+    CNN_KLAUNCH(s, "dropout_bwd", (dropout_bwd<<<stream_grid(n, kBlock), kBlock, 0, s>>>(DropoutBwdOp{dy_inout, C, H * W, dropped_channels}, n)), "n=%zu", n);
     return CNN_AMD_OK;
 }
 
