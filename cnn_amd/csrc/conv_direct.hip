@@ -924,16 +924,21 @@ __global__ __launch_bounds__(kBlock) void conv_fwd_pk_3_16_3_2(const float* __re
 // The separate kernels move 558 MB (conv reads x, writes y and relu(y)) + 250 MB (pool reads relu(y), writes pooled and
 // mask); nothing downstream reads y or relu(y) again (the backward pass needs pooled + mask only, see
 // cnn_maxpool2d_backward_relu), so this kernel writes ONLY pooled and mask: 154 MB in, 100 MB out.
-// Lane pairs (2i, 2i+1) own one pooling window: lane j of the pair computes the conv outputs of window column j for both
+// PK8: the mask is the packed one-byte form (include/cnn_amd.h, CNN_CONV2D_POOL_MASK_PACKED): rows of `pitch8` bytes.
+// DBG: tuning ablations: 1 no FMAs, 2 one weight fetch for all taps.
+// Two bodies with bit-identical results (tests/test_gpu_first_block_forward_windows.py), chosen by the launcher:
+//
+// fwd_pool_pair_body (CNN_AMD_FWD_POOL_PAIR=1, the kernel up to profiles/first_block_forward.md): lane pairs (2i, 2i+1) own one
+// pooling window: lane j of the pair computes the conv outputs of window column j for both
 // window rows (5 input rows x 3 floats x 3 channels = 45 loads for 2 x 27 taps), in exactly the tap order of
 // conv_fwd_pk_3_16_3_2 (bit-identical y), applies bias and ReLU, swaps values with its neighbour through DPP and the
 // even lane scans the window in the reference's order (pool2d.cpp:67-75: first maximum wins, strict '<').
-// PK8: the mask is the packed one-byte form (include/cnn_amd.h, CNN_CONV2D_POOL_MASK_PACKED): rows of `pitch8` bytes.
-template <int DBG, bool PK8>  // DBG: tuning ablations: 1 no FMAs, 2 one weight fetch for all taps
-__global__ __launch_bounds__(kBlock) void conv_fwd_pool_pk_3_16_3_2(const float* __restrict__ x, const v2f* __restrict__ wp,
-                                                                    float* __restrict__ pooled, int32_t* __restrict__ mask,
-                                                                    int B, int H, int W, int Ho, int Wo, int PHo, int PWo,
-                                                                    int items_per_img, unsigned m_ipi, unsigned m_prow, int pitch8) {
+// One wave-item = 64 window columns = 32 windows of one image.
+template <int DBG, bool PK8>
+__device__ __forceinline__ void fwd_pool_pair_body(const float* __restrict__ x, const v2f* __restrict__ wp,
+                                                   float* __restrict__ pooled, int32_t* __restrict__ mask,
+                                                   int B, int H, int W, int Ho, int Wo, int PHo, int PWo,
+                                                   int items_per_img, unsigned m_ipi, unsigned m_prow, int pitch8) {
     constexpr int CI = 3, CO = 16, K = 3;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1043,6 +1048,152 @@ __global__ __launch_bounds__(kBlock) void conv_fwd_pool_pk_3_16_3_2(const float*
             }
         }
     }
+}
+
+// fwd_pool_window_body (the default): ONE lane owns a whole pooling window (ph, pw); one wave-item = 64 consecutive windows of one
+// image (rows of windows are crossed, the image index stays wave-uniform).  The lane loads the window's 5 rows x 5 floats x 3
+// channels (the elements the lane pair read), and computes the window's four conv outputs in two passes of 8 channels: 16 accumulator
+// pairs per pass, and every weight pair fetched into SGPRs feeds 4 packed FMAs instead of 2.  Each output accumulates its 27 taps in
+// the order of conv_fwd_pk_3_16_3_2 (fma(w, p, acc) from +0, then + bias), so y is bit-identical.  The epilogue runs once per window,
+// in the lane, without DPP: against the pair body a window costs 864 packed FMAs either way, but one bias / ReLU / scan / mask
+// epilogue instead of two, of which the odd lane's was thrown away (instruction counts: profiles/first_block_forward.md).
+struct __attribute__((packed, aligned(4))) f5u { float a, b, c, d, e; };
+
+template <int DBG, bool PK8>
+__device__ __forceinline__ void fwd_pool_window_body(const float* __restrict__ x, const v2f* __restrict__ wp,
+                                                     float* __restrict__ pooled, int32_t* __restrict__ mask,
+                                                     int B, int H, int W, int Ho, int Wo, int PHo, int PWo,
+                                                     int items_per_img, unsigned m_ipi, unsigned m_prow, int pitch8) {
+    constexpr int CI = 3, CO = 16, K = 3, CP = 4;  // CP: channel pairs per pass
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long long items = (long long)B * items_per_img;
+    const int PP = PHo * PWo;  // windows per image
+    const int out_bytes = (int)((unsigned)B * CO * PP * 4u);
+    const int mask_bytes = PK8 ? (int)((unsigned)B * CO * PHo * pitch8) : out_bytes;
+    const __amdgpu_buffer_rsrc_t rpool = __builtin_amdgcn_make_buffer_rsrc((void*)pooled, 0, out_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rmask = __builtin_amdgcn_make_buffer_rsrc((void*)(mask ? mask : (int32_t*)pooled), 0, mask ? mask_bytes : out_bytes, 0x00020000);
+    const int PP4 = PP * 4, PP1 = PHo * pitch8;
+    for (int it = xcd_swizzle(blockIdx.x, gridDim.x) * kWaves + wave; it < (int)items; it += gridDim.x * kWaves) {
+        const int b = fast_div(it, m_ipi, items_per_img);
+        const int n = (it - b * items_per_img) * 64 + lane;  // window of this image = ph * PWo + pw
+        const bool live = n < PP;
+        const int ph = fast_div(live ? n : 0, m_prow, PWo), pw = (live ? n : 0) - ph * PWo;
+        // x[.][4ph + r][4pw .. 4pw+4]: one 20-byte load per input row.  Plain global loads (scalar row base + per-lane offset): every
+        // address of a live lane is inside the image (4ph + 4 <= H - 1, 4pw + 4 <= W - 1), a lane that owns no window re-reads the
+        // first elements of the rows and stores nothing.  Rows are only 4-byte aligned in general (W need not be a multiple of 4).
+        const unsigned vo = (unsigned)(4 * ph * W + 4 * pw);  // x[.][4ph][4pw], in floats
+        // kept as register PAIRS, the form v_pk_fma_f32 broadcasts a half of (op_sel): columns 0..3 of a row as two pairs, the fifth
+        // columns of two rows together
+        v2f pq[CI][5][2], p5[(CI * 5 + 1) / 2];
+        p5[(CI * 5 - 1) / 2] = v2f{0.f, 0.f};
+#pragma unroll
+        for (int ci = 0; ci < CI; ++ci)
+#pragma unroll
+            for (int r = 0; r < 5; ++r) {
+                const float* rowp = x + (size_t)((b * CI + ci) * H + r) * W;  // wave-uniform
+                const f5u pr = *(const f5u*)(rowp + vo);
+                pq[ci][r][0] = v2f{pr.a, pr.b};
+                pq[ci][r][1] = v2f{pr.c, pr.d};
+                if ((ci * 5 + r) & 1) p5[(ci * 5 + r) / 2].y = pr.e;
+                else p5[(ci * 5 + r) / 2].x = pr.e;
+            }
+        auto px = [&](int ci, int r, int k) -> float {  // x[ci][4ph + r][4pw + k]
+            const v2f v = k < 4 ? pq[ci][r][k >> 1] : p5[(ci * 5 + r) / 2];
+            return ((k < 4 ? k : ci * 5 + r) & 1) ? v.y : v.x;
+        };
+        // raw buffer stores: one per-lane byte offset + a scalar channel offset; lanes that own no window store out of range = nowhere
+        const unsigned so_lane = live ? (unsigned)n * 4u : kBufOOB;
+        const unsigned so8 = live ? (unsigned)(ph * pitch8 + pw) : kBufOOB;  // (the pad bytes pw >= PWo of a row are never written)
+        const int mbase = 2 * ph * Wo + 2 * pw;
+#pragma unroll
+        for (int h = 0; h < CO / (2 * CP); ++h) {  // channels 8h .. 8h + 7
+            v2f acc[4][CP];                       // [window pixel 2 * dr + dc][channel pair]
+            // (no instruction: the passes sit in different basic blocks (the branches around the mask stores), and a {p, p} operand
+            //  that hipcc shares between two blocks becomes a register pair filled by two v_mov instead of an op_sel on the FMA: 100
+            //  moves and 40 registers; a patch value the second pass cannot recognise is broadcast in the instruction again)
+#pragma unroll
+            for (int ci = 0; ci < CI; ++ci)
+#pragma unroll
+                for (int r = 0; r < 5; ++r) asm("" : "+v"(pq[ci][r][0]), "+v"(pq[ci][r][1]));
+#pragma unroll
+            for (int i = 0; i < (CI * 5 + 1) / 2; ++i) asm("" : "+v"(p5[i]));
+#pragma unroll
+            for (int o = 0; o < 4; ++o)
+#pragma unroll
+                for (int c = 0; c < CP; ++c) acc[o][c] = v2f{0.f, 0.f};
+#pragma unroll
+            for (int t = 0; t < CI * K * K; ++t) {
+                if (DBG != 2 || t == 0) asm volatile("" ::: "memory");  // stream the weight s_loads tap by tap (see conv_dgrad_pk)
+                const int ci = t / 9, kx = (t - ci * 9) / 3, ky = t - ci * 9 - kx * 3;
+                const v2f* qw = wp + (DBG == 2 ? 0 : t) * (CO / 2) + h * CP;
+#pragma unroll
+                for (int o = 0; o < 4; ++o) {
+                    const float p = px(ci, 2 * (o >> 1) + kx, 2 * (o & 1) + ky);
+                    const v2f pv = {p, p};
+                    if (DBG == 1) {
+                        acc[o][t & (CP - 1)] += pv;
+                        continue;
+                    }
+#pragma unroll
+                    for (int c = 0; c < CP; ++c) acc[o][c] = __builtin_elementwise_fma(qw[c], pv, acc[o][c]);
+                }
+            }
+            asm volatile("" ::: "memory");
+            const v2f* qb = wp + CI * K * K * (CO / 2) + h * CP;
+            float bestv[2 * CP];
+            int offv[2 * CP];
+#pragma unroll
+            for (int c = 0; c < CP; ++c) {
+                const v2f bs = qb[c];
+                const v2f v00 = acc[0][c] + bs, v01 = acc[1][c] + bs, v10 = acc[2][c] + bs, v11 = acc[3][c] + bs;
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    const float a = e ? v00.y : v00.x, pa = e ? v01.y : v01.x, d = e ? v10.y : v10.x, pd = e ? v11.y : v11.x;
+                    // ReLU (relu.cpp:21-26: a >= 0 ? a : 0) then the scan with strict '<', in three steps that never change a bit:
+                    // * max(a, 0) is the ReLU of a: NaN -> 0 both ways, and a is never -0 (an accumulator that starts at +0 never
+                    //   becomes -0 under round-to-nearest, and +0 + bias is -0 for no bias), the one input on which they differ.
+                    // * `best < relu(v)` is `best < v` for best >= 0: both are false for v <= 0 and for NaN, and relu(v) = v
+                    //   otherwise; the value taken is v itself.  So only the first pixel needs its ReLU spelled out.
+                    // * best == 0 at the end means that no '<' held, i.e. off == 0: `| mark` is a select.
+                    float best = __builtin_fmaxf(a, 0.f);
+                    int off = 0;
+                    const bool c1 = best < pa;
+                    best = c1 ? pa : best; off = c1 ? 1 : off;
+                    const bool c2 = best < d;
+                    best = c2 ? d : best; off = c2 ? (PK8 ? 2 : Wo) : off;
+                    const bool c3 = best < pd;
+                    best = c3 ? pd : best; off = c3 ? (PK8 ? 3 : Wo + 1) : off;
+                    bestv[2 * c + e] = best;
+                    // bit 7 / bit 31 = "this window's pooled value is <= 0" (see the pair body); PK8: off is the byte's code
+                    // 2 * (row of the maximum) + column, else the flat offset 0 | 1 | Wo | Wo + 1 inside the window
+                    offv[2 * c + e] = best <= 0.f ? (PK8 ? 0x80 : (int)0x80000000) : off;
+                }
+            }
+            const int soff = (b * CO + h * 2 * CP) * PP4;
+#pragma unroll
+            for (int c = 0; c < 2 * CP; ++c) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, bestv[c]), rpool, (int)so_lane, soff + c * PP4, 0);
+            if (mask && !PK8) {
+#pragma unroll
+                for (int c = 0; c < 2 * CP; ++c)  // ((channel plane + mbase) < 2^31: adding bit 31 sets it)
+                    __builtin_amdgcn_raw_buffer_store_b32((h * 2 * CP + c) * Ho * Wo + mbase + offv[c], rmask, (int)so_lane, soff + c * PP4, 0);
+            }
+            if (mask && PK8) {
+                const int soff8 = (b * CO + h * 2 * CP) * PP1;
+#pragma unroll
+                for (int c = 0; c < 2 * CP; ++c) __builtin_amdgcn_raw_buffer_store_b8((unsigned char)offv[c], rmask, (int)so8, soff8 + c * PP1, 0);
+            }
+        }
+    }
+}
+
+template <int DBG, bool PK8, bool PAIR>
+__global__ __launch_bounds__(kBlock) void conv_fwd_pool_pk_3_16_3_2(const float* __restrict__ x, const v2f* __restrict__ wp,
+                                                                    float* __restrict__ pooled, int32_t* __restrict__ mask,
+                                                                    int B, int H, int W, int Ho, int Wo, int PHo, int PWo,
+                                                                    int items_per_img, unsigned m_ipi, unsigned m_prow, int pitch8) {
+    if (PAIR) fwd_pool_pair_body<DBG, PK8>(x, wp, pooled, mask, B, H, W, Ho, Wo, PHo, PWo, items_per_img, m_ipi, m_prow, pitch8);
+    else fwd_pool_window_body<DBG, PK8>(x, wp, pooled, mask, B, H, W, Ho, Wo, PHo, PWo, items_per_img, m_ipi, m_prow, pitch8);
 }
 
 // packed one-byte pool mask -> the int32 flat index of cnn_maxpool2d_forward (bit 7 -> bit 31), for readers outside the fused block
@@ -1305,21 +1456,30 @@ int direct_conv_pool_forward(const cnn_conv2d_desc* d, const float* x, const flo
     const int PHo = Ho / 2, PWo = Wo / 2;
     if (!prepared)
         CNN_KLAUNCH(s, "pack_fwd_weights", (pack_fwd_weights_3_16_3_2<<<1, 256, 0, s>>>(w, bias, (float*)ws)), CONV_TAG(d));
-    const int ipi = (2 * PHo * PWo + 63) / 64;
+    // CNN_AMD_FWD_POOL_PAIR=1 (A/B switch, same results): the lane-pair body, 32 windows per wave-item instead of 64
+    const bool pair = CNN_OPT_INT("FWD_POOL_PAIR", 0) != 0;
+    const int ipi = ((pair ? 2 : 1) * PHo * PWo + 63) / 64;
     const long long witems = (long long)d->B * ipi;
     const int dbg = CNN_MEASURE_INT("DBG", 0);
     const bool pk8 = (d->flags & CNN_CONV2D_POOL_MASK_PACKED) != 0;
     CNN_REQUIRE(!pk8 || direct_pool_mask_packed_ok(d), "cnn_conv2d_relu_maxpool2_forward: packed pool mask not available (cnn_conv2d_pool_mask_packed_supported)");
     const int pitch8 = pool_mask_pitch(PWo);
-#define FP_LAUNCH(DBG_, PK8_)                                                                                                  \
+#define FP_LAUNCH(DBG_, PK8_, PAIR_)                                                                                           \
     CNN_KLAUNCH(s, PK8_ ? "conv_fwd_pool_pk<3,16,3,2>+m8" : "conv_fwd_pool_pk<3,16,3,2>",                                      \
-                (conv_fwd_pool_pk_3_16_3_2<DBG_, PK8_><<<wave_grid(witems), kBlock, 0, s>>>(x, (const v2f*)ws, pooled, mask, d->B, d->H, d->W, Ho, \
+                (conv_fwd_pool_pk_3_16_3_2<DBG_, PK8_, PAIR_><<<wave_grid(witems), kBlock, 0, s>>>(x, (const v2f*)ws, pooled, mask, d->B, d->H, d->W, Ho, \
                                                                                      Wo, PHo, PWo, ipi, div_magic(ipi), div_magic(PWo), pitch8)),  \
                 CONV_TAG(d))
-    if (pk8) FP_LAUNCH(0, true);
-    else if (dbg == 1) FP_LAUNCH(1, false);
-    else if (dbg == 2) FP_LAUNCH(2, false);
-    else FP_LAUNCH(0, false);
+    if (pair) {
+        if (pk8) FP_LAUNCH(0, true, true);
+        else if (dbg == 1) FP_LAUNCH(1, false, true);
+        else if (dbg == 2) FP_LAUNCH(2, false, true);
+        else FP_LAUNCH(0, false, true);
+    } else {
+        if (pk8) FP_LAUNCH(0, true, false);
+        else if (dbg == 1) FP_LAUNCH(1, false, false);
+        else if (dbg == 2) FP_LAUNCH(2, false, false);
+        else FP_LAUNCH(0, false, false);
+    }
 #undef FP_LAUNCH
     return CNN_AMD_OK;
 }

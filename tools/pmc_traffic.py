@@ -26,8 +26,8 @@ def canonical(name):
     m = re.match(r"(igemm_kernel|wgrad_kernel)<(\d+,\d+,\d+,\d+,\d+,\d+),(true|false),(true|false)>$", name)
     if m:
         return f"{m.group(1)}<{m.group(2)}>"
-    m = re.match(r"conv_fwd_pool_pk_3_16_3_2<\d+(?:,(true|false))?>$", name)
-    if m:  # (second parameter: the packed one-byte pool mask)
+    m = re.match(r"conv_fwd_pool_pk_3_16_3_2<\d+(?:,(true|false))?(?:,(?:true|false))?>$", name)
+    if m:  # (second parameter: the packed one-byte pool mask; third: the lane-pair body, same key)
         return "conv_fwd_pool_pk<3,16,3,2>" + ("+m8" if m.group(1) == "true" else "")
     m = re.match(r"conv_dgrad_pool_pk_3_16_3_2<\d+,(true|false)>$", name)
     if m:

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The three kernels of conv_layer_1's block, alone (prepared filters, batch 256): forward (with the ablations of CNN_AMD_DBG), data
+"""The three kernels of conv_layer_1's block, alone (prepared filters, batch 256): forward (both bodies, with the ablations of CNN_AMD_DBG), data
 gradient and weight gradient, each with the int32 and the packed pool mask.  usage: python tools/time_first_block.py [B=256]"""
 import os
 import sys
@@ -42,9 +42,13 @@ for packed in (False, True):
     dx = torch.empty_like(x)
     gw, gb = torch.empty_like(w), torch.empty_like(b)
     tag = "packed mask" if packed else "int32 mask "
-    for dbg in ((None,) if packed else (None, "1", "2")):
-        capi.set_option("DBG", dbg)
-        timed(f"forward {tag} DBG={dbg}", lambda: conv.relu_maxpool2_forward(x, None, None, pooled, mask, prepared_fwd=pf), "conv_fwd_pool_pk")
+    for pair in ("1", None):  # the lane-pair body (FWD_POOL_PAIR=1), then the window-per-lane body
+        capi.set_option("FWD_POOL_PAIR", pair)
+        for dbg in ((None,) if packed else (None, "1", "2")):
+            if dbg is not None and not capi.load().cnn_amd_measure_build():
+                continue  # (the ablations exist in libcnn_amd_measure.so only)
+            capi.set_option("DBG", dbg)
+            timed(f"forward {tag} PAIR={pair} DBG={dbg}", lambda: conv.relu_maxpool2_forward(x, None, None, pooled, mask, prepared_fwd=pf), "conv_fwd_pool_pk")
     capi.set_option("DBG", None)
     conv.relu_maxpool2_forward(x, None, None, pooled, mask, prepared_fwd=pf)
     timed(f"data gradient {tag}", lambda: conv.backward_data_pooled2(dpool, mask, None, None, dx, prepared_dgrad=pd), "conv_dgrad_pk")
