@@ -143,6 +143,7 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 // two adjacent floats stored with ONE dwordx2 even when only 4-byte aligned (odd row pitch): global memory accesses may
 // be unaligned on gfx950, and hipcc emits global_store_dwordx2 for this type
 struct __attribute__((packed, aligned(4))) f2u { float x, y; };
+struct __attribute__((packed, aligned(4))) f4u { float x, y, z, w; };
 struct __attribute__((packed, aligned(4))) f3u { float x, y, z; };
 
 __device__ void pack_dgrad_3_16_3_2_body(const float* __restrict__ w, float* __restrict__ wp, int tid) {
@@ -623,47 +624,53 @@ __global__ void pack_batch(const PackBatch pb) {
 //   3. the forward / data-gradient filter images of the updated filters (pack_fwd_3_16_3_2_body / pack_dgrad_3_16_3_2_body), read
 //      from the LDS copy of the new values.
 constexpr int kFinThreads = 1024, kFinLanes = 8, kFinN = 16 * 28;
-__global__ __launch_bounds__(kFinThreads) void first_layer_finish(const float* __restrict__ slabs, int nslots, float divisor,
+__global__ __launch_bounds__(kFinThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void first_layer_finish(const float* __restrict__ slabs, int nslots, float divisor,
                                                                   float* __restrict__ gw, float* __restrict__ gb, float* __restrict__ w,
                                                                   float* __restrict__ bias, float lr, float scale, int scaled,
                                                                   float* __restrict__ fwd_img, float* __restrict__ dgrad_img,
                                                                   float* __restrict__ w_keep, float* __restrict__ bias_keep) {
     __shared__ float red[kFinLanes][kFinN];
     __shared__ float wl[16 * 27], bl[16];
-    constexpr int PAIRS = kFinLanes * kFinN, PER = (PAIRS + kFinThreads - 1) / kFinThreads;  // (element, slot-lane) pairs per thread
-    float acc[PER];
-    int idx[PER], sl[PER];
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const int pr = threadIdx.x + q * kFinThreads;
-        acc[q] = 0.f;
-        sl[q] = pr / kFinN;
-        idx[q] = pr - sl[q] * kFinN;
-    }
-    const bool last_live = threadIdx.x + (PER - 1) * kFinThreads < PAIRS;
-    if (!last_live) idx[PER - 1] = 0, sl[PER - 1] = 0;  // (loads something valid, stores nothing)
-    // branch-free batches: every load of kBatch slot rounds is issued before the first add (the adds keep their order)
-    constexpr int kBatch = 8;
+    // a thread owns four neighbouring elements of one slot-lane: 112 quads x 8 slot-lanes = 896 of the 1024 threads, one 16-byte load
+    // per slot (the workgroup is bound by its load instructions -- 460 KB through one CU -- not by their latency alone: with one
+    // 4-byte load per (element, slot), 64 of them in flight per thread took 12.2 us alone against 11.2 us with 32 in flight).
+    // hipcc: 74 VGPRs, no scratch, no spills, 4 waves / SIMD (the 16 waves of the workgroup; amdgpu_waves_per_eu keeps the scheduler
+    // from trading the sixteen loads in flight for an occupancy the single workgroup cannot use -- 60 VGPRs, 5 .. 10 in flight without)
+    constexpr int QUADS = kFinN / 4;
+    const bool live = threadIdx.x < kFinLanes * QUADS;
+    const int pr = live ? threadIdx.x : 0;  // (the rest loads something valid, stores nothing)
+    const int sl = pr / QUADS, quad = pr - sl * QUADS;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    // what step 2 needs of the old parameters depends on nothing computed here: requested in front of the first slab batch by the
+    // threads that use it (one filter value or one bias value each), consumed behind the barrier
+    const int pi = threadIdx.x < kFinN ? threadIdx.x : 0, prow = pi / 28, pcol = pi - prow * 28;
+    const float* const pold = pcol < 27 ? w + (prow * 27 + pcol) : (bias ? bias + prow : w);
+    const float old_v = *pold;
+    // branch-free batches: every load of kBatch slot rounds is issued before the first add (the adds keep their order: a slot-lane
+    // adds its slots in ascending order); 128 slots per batch, so the 256 slabs of a whole-chip weight gradient are two dependent trips
+    constexpr int kBatch = 16;
     for (int s0 = 0; s0 < nslots; s0 += kBatch * kFinLanes) {
-        float v[kBatch][PER];
+        f4u v[kBatch];
 #pragma unroll
-        for (int u = 0; u < kBatch; ++u)
+        for (int u = 0; u < kBatch; ++u) {
+            const int s = s0 + u * kFinLanes + sl;
+            v[u] = *reinterpret_cast<const f4u*>(slabs + (size_t)(s < nslots ? s : 0) * kFinN + 4 * quad);
+        }
 #pragma unroll
-            for (int q = 0; q < PER; ++q) {
-                const int s = s0 + u * kFinLanes + sl[q];
-                v[u][q] = slabs[(size_t)(s < nslots ? s : 0) * kFinN + idx[q]];
-            }
-#pragma unroll
-        for (int u = 0; u < kBatch; ++u)
-#pragma unroll
-            for (int q = 0; q < PER; ++q) {
-                const float sum = acc[q] + v[u][q];
-                acc[q] = (s0 + u * kFinLanes + sl[q] < nslots) ? sum : acc[q];
-            }
+        for (int u = 0; u < kBatch; ++u) {
+            const bool in_range = s0 + u * kFinLanes + sl < nslots;
+            const float s0v = acc[0] + v[u].x, s1v = acc[1] + v[u].y, s2v = acc[2] + v[u].z, s3v = acc[3] + v[u].w;
+            acc[0] = in_range ? s0v : acc[0];
+            acc[1] = in_range ? s1v : acc[1];
+            acc[2] = in_range ? s2v : acc[2];
+            acc[3] = in_range ? s3v : acc[3];
+        }
     }
+    if (live) {
 #pragma unroll
-    for (int q = 0; q < PER; ++q)
-        if (q + 1 < PER || last_live) red[sl[q]][idx[q]] = acc[q];
+        for (int c = 0; c < 4; ++c) red[sl][4 * quad + c] = acc[c];
+    }
     __syncthreads();
     if (threadIdx.x < kFinN) {
         const int i = threadIdx.x;
@@ -675,14 +682,14 @@ __global__ __launch_bounds__(kFinThreads) void first_layer_finish(const float* _
         if (col < 27) {
             const int j = row * 27 + col;
             gw[j] = g;
-            const float old = w[j];
+            const float old = old_v;
             if (w_keep) w_keep[j] = old;  // (the filters the last forward pass used: Conv2D::get_output() re-materialisation)
             const float v = sgd_one(old, g, lr, scale, scaled != 0);
             w[j] = v;
             wl[j] = v;
         } else {
             if (gb) gb[row] = g;
-            const float oldb = bias ? bias[row] : 0.f;
+            const float oldb = bias ? old_v : 0.f;
             if (bias && bias_keep) bias_keep[row] = oldb;
             const float v = bias ? sgd_one(oldb, g, lr, scale, scaled != 0) : 0.f;
             if (bias) bias[row] = v;

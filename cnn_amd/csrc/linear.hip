@@ -73,159 +73,231 @@ __device__ __forceinline__ float clamped_exp_l(float v) {
 // the layer in front (x <= 0 ? 0 : dx).  The critical path of a train step then has ONE head kernel between the last forward
 // convolution and the first data gradient; the weight / bias gradient of the layer (which needs every sample's delta) runs
 // beside the convolutions' weight gradients (linear_bwd_fused<.., false>).
-template <bool BATCH, int DX>
+//
+// S = samples per workgroup (S > 1: out == 3 only, the launcher's rule).  Workgroup g owns samples g*S .. min(B, g*S + S) - 1: a
+// thread fetches its W rows ONCE and uses them for all S samples -- the W rows are three quarters of the S = 1 kernel's load
+// requests, and they are the same for every sample.  Per sample nothing changes: the same thread-to-element map, the same FMA
+// order, wave_sum, the waves in order, + bias, the same sequential softmax (in S lanes at once), the same dx expression.  A
+// sample slot behind the batch's end (s >= ns) computes sample g*S once more -- its loads stay inside the operands -- and stores
+// nothing.  bias and the labels depend on nothing computed: they are requested in front of the first operand batch by the threads
+// that use them, not behind the barriers where they are used.
+template <bool BATCH, int DX, int S>
 __global__ __launch_bounds__(kBlock) void linear_fwd_softmax_xent(const float* __restrict__ x, const float* __restrict__ w,
                                                                   const float* __restrict__ bias, const int32_t* __restrict__ labels,
                                                                   float* __restrict__ y, float* __restrict__ probs,
-                                                                  float* __restrict__ delta, float* __restrict__ loss_terms, int in,
-                                                                  int out, float* __restrict__ dx) {
-    __shared__ float part[kBlock / kWave][kOutTile];
-    __shared__ float logit[kOutTile];
-    __shared__ float dl[kOutTile];
+                                                                  float* __restrict__ delta, float* __restrict__ loss_terms, int B,
+                                                                  int in, int out, float* __restrict__ dx) {
+    static_assert(S == 1 || BATCH, "several samples per workgroup: the batched 3-output path only");
+    constexpr int NJ = S > 1 ? 3 : kOutTile;
+    __shared__ float part[S][kBlock / kWave][NJ];
+    __shared__ float logit[S][NJ];
+    __shared__ float dl[S][NJ];
     constexpr int UK = 18;
-    float xk[UK];  // (BATCH && out == 3 && in == UK * kBlock: the thread's x values and W rows stay in registers for the dx pass)
+    float xk[S][UK];  // (BATCH && out == 3 && in == UK * kBlock: the thread's x values and W rows stay in registers for the dx pass)
     w3 wk[UK];
     bool kept = false;
-    const int b = blockIdx.x;
-    const float* xb = x + (size_t)b * in;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float acc[kOutTile];
+    const int b0 = blockIdx.x * S;
+    const int ns = min(S, B - b0);
+    // the thread's (sample slot, output) in the reduction behind the first barrier; its bias value and, for threads 0 .. S-1, the
+    // label of sample b0 + threadIdx.x are on their way before anything else
+    const int ts = S > 1 ? (int)threadIdx.x / 3 : 0, tj = S > 1 ? (int)threadIdx.x - ts * 3 : (int)threadIdx.x;
+    const bool reducer = S > 1 ? threadIdx.x < S * 3 : (int)threadIdx.x < out;
+    const float bias_v = bias[reducer ? tj : 0];
+    const int label_v = labels[b0 + ((int)threadIdx.x < ns ? (int)threadIdx.x : 0)];
+    const float* xs[S];
 #pragma unroll
-    for (int j = 0; j < kOutTile; ++j) acc[j] = 0.f;
+    for (int s = 0; s < S; ++s) xs[s] = x + (size_t)(b0 + (s < ns ? s : 0)) * in;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float acc[S][NJ];
+#pragma unroll
+    for (int s = 0; s < S; ++s)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) acc[s][j] = 0.f;
     int i = threadIdx.x;
     if (BATCH && out == 3) {
-        // the reference net's head: every load of 18 iterations (one 4-byte x value + one 12-byte W row each) is issued before
-        // the first FMA -- in the train step this kernel shares the chip with an HBM-bound kernel, and each dependent round
+        // the reference net's head: every load of 18 iterations (one 12-byte W row + one 4-byte x value per sample each) is issued
+        // before the first FMA -- in the train step this kernel shares the chip with an HBM-bound kernel, and each dependent round
         // trip costs microseconds there.  Same products, same order as the generic loop below.
         constexpr int U = UK;
-        for (; i + (U - 1) * kBlock < in; i += U * kBlock) {
-            float xv[U];
-            w3 wv[U];
+        auto batch = [&](float (&xv)[S][U], w3 (&wv)[U]) {
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                xv[u] = xb[i + u * kBlock];
+#pragma unroll
+                for (int s = 0; s < S; ++s) xv[s][u] = xs[s][i + u * kBlock];
                 wv[u] = *reinterpret_cast<const w3*>(w + (size_t)(i + u * kBlock) * 3);
             }
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                acc[0] = __builtin_fmaf(xv[u], wv[u].a, acc[0]);  // explicit: contraction must not depend on the loop shape
-                acc[1] = __builtin_fmaf(xv[u], wv[u].b, acc[1]);
-                acc[2] = __builtin_fmaf(xv[u], wv[u].c, acc[2]);
-            }
-            if (DX != 0 && in == U * kBlock) {
-                kept = true;
+            for (int s = 0; s < S; ++s)
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    xk[u] = xv[u];
-                    wk[u] = wv[u];
+                    acc[s][0] = __builtin_fmaf(xv[s][u], wv[u].a, acc[s][0]);  // explicit: contraction must not depend on the loop shape
+                    acc[s][1] = __builtin_fmaf(xv[s][u], wv[u].b, acc[s][1]);
+                    acc[s][2] = __builtin_fmaf(xv[s][u], wv[u].c, acc[s][2]);
                 }
+            i += U * kBlock;
+        };
+        if (DX != 0 && in == U * kBlock) {  // the one batch there is goes straight into the registers the dx pass reads
+            kept = true;
+            batch(xk, wk);
+        } else {
+            while (i + (U - 1) * kBlock < in) {
+                float xv[S][U];
+                w3 wv[U];
+                batch(xv, wv);
             }
         }
     }
     if (BATCH && out == 3) {  // what the 18-wide loop left (the stacks' heads: in = 98 * 256): four iterations' loads at once, same order
         constexpr int U = 4;
         for (; i + (U - 1) * kBlock < in; i += U * kBlock) {
-            float xv[U];
+            float xv[S][U];
             w3 wv[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                xv[u] = xb[i + u * kBlock];
+#pragma unroll
+                for (int s = 0; s < S; ++s) xv[s][u] = xs[s][i + u * kBlock];
                 wv[u] = *reinterpret_cast<const w3*>(w + (size_t)(i + u * kBlock) * 3);
             }
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                acc[0] = __builtin_fmaf(xv[u], wv[u].a, acc[0]);
-                acc[1] = __builtin_fmaf(xv[u], wv[u].b, acc[1]);
-                acc[2] = __builtin_fmaf(xv[u], wv[u].c, acc[2]);
-            }
+            for (int s = 0; s < S; ++s)
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    acc[s][0] = __builtin_fmaf(xv[s][u], wv[u].a, acc[s][0]);
+                    acc[s][1] = __builtin_fmaf(xv[s][u], wv[u].b, acc[s][1]);
+                    acc[s][2] = __builtin_fmaf(xv[s][u], wv[u].c, acc[s][2]);
+                }
         }
     }
 #pragma unroll 6
     for (; i < in; i += kBlock) {
-        const float xv = xb[i];
         const float* wr = w + (size_t)i * out;
 #pragma unroll
-        for (int j = 0; j < kOutTile; ++j)
-            if (j < out) acc[j] = __builtin_fmaf(xv, wr[j], acc[j]);
+        for (int s = 0; s < S; ++s) {
+            const float xv = xs[s][i];
+#pragma unroll
+            for (int j = 0; j < NJ; ++j)
+                if (j < out) acc[s][j] = __builtin_fmaf(xv, wr[j], acc[s][j]);
+        }
     }
 #pragma unroll
-    for (int j = 0; j < kOutTile; ++j) {
-        const float s = wave_sum(acc[j]);
-        if (lane == 0) part[wave][j] = s;
+    for (int s = 0; s < S; ++s)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const float r = wave_sum(acc[s][j]);
+            if (lane == 0) part[s][wave][j] = r;
+        }
+    __syncthreads();
+    if (reducer) {
+        float r = 0.f;
+        for (int wv = 0; wv < kBlock / kWave; ++wv) r += part[ts][wv][tj];
+        r += bias_v;
+        if (ts < ns) y[(size_t)(b0 + ts) * out + tj] = r;
+        logit[ts][tj] = r;
     }
     __syncthreads();
-    if (threadIdx.x < out) {
-        float s = 0.f;
-        for (int wv = 0; wv < kBlock / kWave; ++wv) s += part[wv][threadIdx.x];
-        s += bias[threadIdx.x];
-        y[(size_t)b * out + threadIdx.x] = s;
-        logit[threadIdx.x] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {  // the reference's sequential per-sample arithmetic (same as softmax_xent_kernel)
-        float mx = logit[0];
+    if ((int)threadIdx.x < ns) {  // the reference's sequential per-sample arithmetic (same as softmax_xent_kernel), a lane per sample
+        const int sl = threadIdx.x;
+        const size_t b = (size_t)(b0 + sl);
+        float mx = logit[sl][0];
         for (int i = 1; i < out; ++i)
-            if (logit[i] > mx) mx = logit[i];
+            if (logit[sl][i] > mx) mx = logit[sl][i];
         float sum = 0.f;
-        for (int i = 0; i < out; ++i) sum += clamped_exp_l(logit[i] - mx);
-        const int label = labels[b];
+        for (int i = 0; i < out; ++i) sum += clamped_exp_l(logit[sl][i] - mx);
+        const int label = label_v;
         float term = 0.f;
         for (int i = 0; i < out; ++i) {
-            float pr = clamped_exp_l(logit[i] - mx) / sum;
+            float pr = clamped_exp_l(logit[sl][i] - mx) / sum;
             if (isnan(pr)) pr = 0.f;
             const float yv = (i == label) ? 1.f : 0.f;
-            if (probs) probs[(size_t)b * out + i] = pr;
-            delta[(size_t)b * out + i] = pr - yv;
-            if (DX != 0) dl[i] = pr - yv;
+            if (probs) probs[b * out + i] = pr;
+            delta[b * out + i] = pr - yv;
+            if (DX != 0) dl[sl][i] = pr - yv;
             term += logf(pr) * yv;
         }
         loss_terms[b] = term;
     }
     if constexpr (DX != 0) {
         __syncthreads();
-        float* dxb = dx + (size_t)b * in;
         if (kept) {  // out == 3, in == 18 * 256: no loads at all
-            const float d0 = dl[0], d1 = dl[1], d2 = dl[2];
 #pragma unroll
-            for (int u = 0; u < UK; ++u) {
-                float sj = 0.f;  // (linear_bwd_fused's expression, term by term)
-                sj = __builtin_fmaf(d0, wk[u].a, sj);  // (explicit: the contraction must not depend on the loop shape)
-                sj = __builtin_fmaf(d1, wk[u].b, sj);
-                sj = __builtin_fmaf(d2, wk[u].c, sj);
-                dxb[threadIdx.x + u * kBlock] = (DX == 2 && xk[u] <= 0.f) ? 0.f : sj;
+            for (int s = 0; s < S; ++s) {
+                if (s >= ns) break;
+                float* dxb = dx + (size_t)(b0 + s) * in;
+                const float d0 = dl[s][0], d1 = dl[s][1], d2 = dl[s][2];
+#pragma unroll
+                for (int u = 0; u < UK; ++u) {
+                    float sj = 0.f;  // (linear_bwd_fused's expression, term by term)
+                    sj = __builtin_fmaf(d0, wk[u].a, sj);  // (explicit: the contraction must not depend on the loop shape)
+                    sj = __builtin_fmaf(d1, wk[u].b, sj);
+                    sj = __builtin_fmaf(d2, wk[u].c, sj);
+                    dxb[threadIdx.x + u * kBlock] = (DX == 2 && xk[s][u] <= 0.f) ? 0.f : sj;
+                }
             }
         } else {
             int i2 = threadIdx.x;
             if (BATCH && out == 3) {  // (round 6) seven iterations' loads in flight (the stacks' heads: 98 iterations per thread, one round trip each before)
                 constexpr int U = 7;
-                const float d0 = dl[0], d1 = dl[1], d2 = dl[2];
+                float d[S][3];
+#pragma unroll
+                for (int s = 0; s < S; ++s) d[s][0] = dl[s < ns ? s : 0][0], d[s][1] = dl[s < ns ? s : 0][1], d[s][2] = dl[s < ns ? s : 0][2];
                 for (; i2 + (U - 1) * kBlock < in; i2 += U * kBlock) {
                     w3 wv[U];
-                    float xv[U];
+                    float xv[S][U];
 #pragma unroll
                     for (int u = 0; u < U; ++u) {
                         wv[u] = *reinterpret_cast<const w3*>(w + (size_t)(i2 + u * kBlock) * 3);
-                        xv[u] = DX == 2 ? xb[i2 + u * kBlock] : 1.f;
+#pragma unroll
+                        for (int s = 0; s < S; ++s) xv[s][u] = DX == 2 ? xs[s][i2 + u * kBlock] : 1.f;
                     }
 #pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        float sj = 0.f;
-                        sj = __builtin_fmaf(d0, wv[u].a, sj);
-                        sj = __builtin_fmaf(d1, wv[u].b, sj);
-                        sj = __builtin_fmaf(d2, wv[u].c, sj);
-                        dxb[i2 + u * kBlock] = (DX == 2 && xv[u] <= 0.f) ? 0.f : sj;
+                    for (int s = 0; s < S; ++s) {
+                        if (s >= ns) break;
+                        float* dxb = dx + (size_t)(b0 + s) * in;
+#pragma unroll
+                        for (int u = 0; u < U; ++u) {
+                            float sj = 0.f;
+                            sj = __builtin_fmaf(d[s][0], wv[u].a, sj);
+                            sj = __builtin_fmaf(d[s][1], wv[u].b, sj);
+                            sj = __builtin_fmaf(d[s][2], wv[u].c, sj);
+                            dxb[i2 + u * kBlock] = (DX == 2 && xv[s][u] <= 0.f) ? 0.f : sj;
+                        }
                     }
                 }
             }
             for (; i2 < in; i2 += kBlock) {
                 const float* wr = w + (size_t)i2 * out;
-                float sj = 0.f;
 #pragma unroll
-                for (int j = 0; j < kOutTile; ++j)
-                    if (j < out) sj = __builtin_fmaf(dl[j], wr[j], sj);
-                dxb[i2] = (DX == 2 && xb[i2] <= 0.f) ? 0.f : sj;
+                for (int s = 0; s < S; ++s) {
+                    if (s >= ns) break;
+                    float sj = 0.f;
+#pragma unroll
+                    for (int j = 0; j < NJ; ++j)
+                        if (j < out) sj = __builtin_fmaf(dl[s][j], wr[j], sj);
+                    dx[(size_t)(b0 + s) * in + i2] = (DX == 2 && xs[s][i2] <= 0.f) ? 0.f : sj;
+                }
             }
         }
+    }
+}
+
+// Samples per workgroup of the head with the data gradient (CNN_AMD_HEAD_SAMPLES = 1 | 2 | 4 | 8; 1 = one workgroup per sample, the
+// grid up to here).  Only 3-output layers take more than one.  profiles/loss_head.md has the registers and the times per S.
+constexpr int kHeadSamples = 2;  // (in the reference net's step at batch 256: 32.4 us against 36.8 at 1, 51.5 at 4, 57.2 at 8)
+int head_samples(int out) {  // 0: a value no kernel is built for
+    const int S = CNN_OPT_INT("HEAD_SAMPLES", kHeadSamples);
+    if (S != 1 && S != 2 && S != 4 && S != 8) return 0;
+    return out == 3 ? S : 1;
+}
+
+template <int DX>
+void launch_head_dx(int S, hipStream_t s, const float* x, const float* w, const float* bias, const int32_t* labels, float* logits,
+                    float* probs, float* delta, float* loss_terms, int B, int in, int out, float* dx) {
+    const dim3 grid(ceil_div(B, S)), block(kBlock);
+    switch (S) {
+    case 8: launch_pub(linear_fwd_softmax_xent<true, DX, 8>, grid, block, 0, s, x, w, bias, labels, logits, probs, delta, loss_terms, B, in, out, dx); break;
+    case 4: launch_pub(linear_fwd_softmax_xent<true, DX, 4>, grid, block, 0, s, x, w, bias, labels, logits, probs, delta, loss_terms, B, in, out, dx); break;
+    case 2: launch_pub(linear_fwd_softmax_xent<true, DX, 2>, grid, block, 0, s, x, w, bias, labels, logits, probs, delta, loss_terms, B, in, out, dx); break;
+    default: launch_pub(linear_fwd_softmax_xent<true, DX, 1>, grid, block, 0, s, x, w, bias, labels, logits, probs, delta, loss_terms, B, in, out, dx); break;
     }
 }
 
@@ -460,14 +532,15 @@ int cnn_linear_forward_softmax_xent(const float* x, const float* w, const float*
     CNN_REQUIRE(B > 0 && in > 0 && out > 0 && out <= kOutTile, "cnn_linear_forward_softmax_xent: B=%d in=%d out=%d (out <= %d)", B, in, out,
                 kOutTile);
     hipStream_t s = as_stream(stream);
+    // (always one sample per workgroup: not on the train step's path, and the reference the S > 1 kernels are tested against)
     const OptVal e = CNN_OPT_VAL("NO_HEAD_BATCH");  // A/B switch: the plain 6-deep loop for every layer width
     if (e && atoi(e) != 0)
         CNN_KLAUNCH(s, "linear_fwd+softmax_xent",
-                    (linear_fwd_softmax_xent<false, 0><<<B, kBlock, 0, s>>>(x, w, bias, labels, logits, probs, delta, loss_terms, in, out, nullptr)),
+                    (linear_fwd_softmax_xent<false, 0, 1><<<B, kBlock, 0, s>>>(x, w, bias, labels, logits, probs, delta, loss_terms, B, in, out, nullptr)),
                     "B%d in%d out%d", B, in, out);
     else
         CNN_KLAUNCH(s, "linear_fwd+softmax_xent",
-                    (linear_fwd_softmax_xent<true, 0><<<B, kBlock, 0, s>>>(x, w, bias, labels, logits, probs, delta, loss_terms, in, out, nullptr)),
+                    (linear_fwd_softmax_xent<true, 0, 1><<<B, kBlock, 0, s>>>(x, w, bias, labels, logits, probs, delta, loss_terms, B, in, out, nullptr)),
                     "B%d in%d out%d", B, in, out);
     return CNN_AMD_OK;
 }
@@ -479,13 +552,15 @@ int cnn_linear_forward_softmax_xent_dx(const float* x, const float* w, const flo
     CNN_REQUIRE(B > 0 && in > 0 && out > 0 && out <= kOutTile, "cnn_linear_forward_softmax_xent_dx: B=%d in=%d out=%d (out <= %d)", B, in, out,
                 kOutTile);
     hipStream_t s = as_stream(stream);
+    const int S = head_samples(out);
+    CNN_REQUIRE(S > 0, "cnn_linear_forward_softmax_xent_dx: CNN_AMD_HEAD_SAMPLES must be 1, 2, 4 or 8");
     if (relu_below)
         CNN_KLAUNCH(s, "linear_fwd+softmax_xent+dx+relu",
-                    (launch_pub(linear_fwd_softmax_xent<true, 2>, dim3(B), dim3(kBlock), 0, s, x, w, bias, labels, logits, probs, delta, loss_terms, in, out, dx)),
+                    (launch_head_dx<2>(S, s, x, w, bias, labels, logits, probs, delta, loss_terms, B, in, out, dx)),
                     "B%d in%d out%d", B, in, out);
     else
         CNN_KLAUNCH(s, "linear_fwd+softmax_xent+dx",
-                    (launch_pub(linear_fwd_softmax_xent<true, 1>, dim3(B), dim3(kBlock), 0, s, x, w, bias, labels, logits, probs, delta, loss_terms, in, out, dx)),
+                    (launch_head_dx<1>(S, s, x, w, bias, labels, logits, probs, delta, loss_terms, B, in, out, dx)),
                     "B%d in%d out%d", B, in, out);
     return CNN_AMD_OK;
 }
