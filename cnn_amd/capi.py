@@ -26,6 +26,17 @@ class ConvDesc(C.Structure):
 POOL_MASK_PACKED = 1  # CNN_CONV2D_POOL_MASK_PACKED (include/cnn_amd.h)
 
 
+class MixDesc(C.Structure):
+    """mirror of cnn_mix_desc"""
+
+    _fields_ = [("mode", C.c_int), ("lam", C.c_float), ("pair_rule", C.c_int), ("pair_shift", C.c_int), ("y0", C.c_int), ("y1", C.c_int),
+                ("x0", C.c_int), ("x1", C.c_int)]
+
+
+PAIR_NONE, PAIR_FLIP, PAIR_ROLL = 0, 1, 2  # CNN_PAIR_*
+MIX_MIXUP, MIX_CUTMIX = 1, 2  # CNN_MIX_*
+
+
 class SgdOptions(C.Structure):
     """mirror of cnn_sgd_options"""
 
@@ -194,6 +205,12 @@ SIGNATURES = {
     "cnn_softmax_xent": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, _P]),
     "cnn_linear_forward_softmax_xent": (C.c_int, [_P] * 8 + [C.c_int] * 3 + [_P]),
     "cnn_loss_from_terms": (C.c_int, [_P, _P, C.c_int, _P]),
+    "cnn_soft_targets": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, _P]),
+    "cnn_batch_mix": (C.c_int, [C.POINTER(MixDesc), _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "cnn_cutmix_lambda": (C.c_float, [C.c_int] * 6),
+    "cnn_softmax_xent_soft": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, _P]),
+    "cnn_linear_forward_softmax_xent_soft": (C.c_int, [_P] * 8 + [C.c_int] * 3 + [_P]),
+    "cnn_linear_forward_softmax_xent_soft_dx": (C.c_int, [_P] * 9 + [C.c_int] * 4 + [_P]),
     "cnn_conv2d_backward_weight_side": (C.c_int, [_D, _P, _P, _P, _P, C.c_float, _P, C.c_size_t, _P]),
     "cnn_device_alloc": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t]),
     "cnn_device_free": (C.c_int, [_P]),
@@ -892,6 +909,50 @@ def softmax_xent(logits, labels, want_probs=True):
     loss = torch.empty((1,), dtype=torch.float32, device=logits.device)
     check(load().cnn_softmax_xent(_ptr(logits), _ptr(labels), _ptr(probs), _ptr(delta), _ptr(loss), B, n, _stream()), "cnn_softmax_xent")
     return probs, delta, loss
+
+
+def softmax_xent_soft(logits, targets, want_probs=True):
+    """cnn_softmax_xent_soft: cnn_softmax_xent against a dense float32 [B][classes] target tensor"""
+    import torch
+
+    _need_gpu(logits, targets)
+    B, n = logits.shape
+    probs = torch.empty_like(logits) if want_probs else None
+    delta = torch.empty_like(logits)
+    loss = torch.empty((1,), dtype=torch.float32, device=logits.device)
+    check(load().cnn_softmax_xent_soft(_ptr(logits), _ptr(targets), _ptr(probs), _ptr(delta), _ptr(loss), B, n, _stream()), "cnn_softmax_xent_soft")
+    return probs, delta, loss
+
+
+def soft_targets(labels, classes, smoothing=0.0, lam=1.0, pair_rule=PAIR_NONE, pair_shift=0, out=None):
+    """cnn_soft_targets: labels int32 [B] (device) -> float32 [B][classes] target rows: label smoothing, and the mix lam * own +
+    (1 - lam) * partner's under a pair rule (PAIR_FLIP: B - 1 - b, PAIR_ROLL: (b + pair_shift) % B)"""
+    import torch
+
+    _need_gpu(labels, out)
+    B = labels.shape[0]
+    if out is None:
+        out = torch.empty((B, classes), dtype=torch.float32, device=labels.device)
+    check(load().cnn_soft_targets(_ptr(labels), _ptr(out), B, int(classes), float(smoothing), float(lam), int(pair_rule), int(pair_shift), _stream()),
+          "cnn_soft_targets")
+    return out
+
+
+def cutmix_lambda(H, W, y0, y1, x0, x1):
+    """cnn_cutmix_lambda: the weight of the sample itself under a CutMix box (host only)"""
+    return float(load().cnn_cutmix_lambda(int(H), int(W), int(y0), int(y1), int(x0), int(x1)))
+
+
+def batch_mix(mix, src, dst=None):
+    """cnn_batch_mix: mixup / CutMix of a float32 [B][C][H][W] device batch with its partner samples, out of place; mix: a MixDesc"""
+    import torch
+
+    _need_gpu(src, dst)
+    B, Cc, H, W = src.shape
+    if dst is None:
+        dst = torch.empty_like(src)
+    check(load().cnn_batch_mix(C.byref(mix), _ptr(src), _ptr(dst), B, Cc, H, W, _stream()), "cnn_batch_mix")
+    return dst
 
 
 def set_option(name, value):

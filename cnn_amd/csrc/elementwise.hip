@@ -1,6 +1,6 @@
 // elementwise.hip -- HBM-bound streaming kernels: ReLU fwd/bwd (relu.cpp:21-26,35-40), dropout, the SGD step (conv2d.cpp:205-217,
 // linear.cpp:95-102), the optimizer steps, the clip, the gradient accumulation, the parameter average and the buffer exchange on the
-// flat arena (additions), and the softmax / cross-entropy and Grad-CAM glue (func.cpp:16-73, alexnet.cpp:107-140), which have shapes
+// flat arena (additions), mixup / CutMix of a batch and the soft target rows (additions), and the softmax / cross-entropy and Grad-CAM glue (func.cpp:16-73, alexnet.cpp:107-140), which have shapes
 // of their own.
 //
 // Every streaming kernel here has ONE shape (stream_walk) over the flat range [0, n):
@@ -451,8 +451,10 @@ __device__ __forceinline__ float clamped_exp(float v) {
 // One workgroup; thread t owns samples t, t+256, ...  Per-sample arithmetic is the reference's sequential
 // loop (func.cpp:22-33, 63-68); the loss terms are then added in ascending sample order by one lane so the
 // fp32 loss sum has the reference's order (func.cpp:60-71).
+// SOFT (cnn_softmax_xent_soft): `labels` is a dense [B][classes] fp32 target tensor, yv = targets[b][i]; the same expressions otherwise.
+template <bool SOFT>
 __global__ __launch_bounds__(kBlock) void softmax_xent_kernel(const float* __restrict__ logits,
-                                                              const int32_t* __restrict__ labels,
+                                                              const std::conditional_t<SOFT, float, int32_t>* __restrict__ labels,
                                                               float* __restrict__ probs, float* __restrict__ delta,
                                                               float* __restrict__ loss_sum, int B, int classes) {
     __shared__ float terms[kBlock];
@@ -467,11 +469,14 @@ __global__ __launch_bounds__(kBlock) void softmax_xent_kernel(const float* __res
                 if (in[i] > mx) mx = in[i];
             float sum = 0.f;
             for (int i = 0; i < classes; ++i) sum += clamped_exp(in[i] - mx);
-            const int label = labels[b];
+            int label = 0;
+            if constexpr (!SOFT) label = labels[b];
             for (int i = 0; i < classes; ++i) {
                 float p = clamped_exp(in[i] - mx) / sum;
                 if (isnan(p)) p = 0.f;
-                const float yv = (i == label) ? 1.f : 0.f;
+                float yv;
+                if constexpr (SOFT) yv = labels[(size_t)b * classes + i];
+                else yv = (i == label) ? 1.f : 0.f;
                 if (probs) probs[(size_t)b * classes + i] = p;
                 delta[(size_t)b * classes + i] = p - yv;  // no 1/B here (func.cpp:64)
                 term += logf(p) * yv;                     // func.cpp:65, incl. its log(0)*0 = NaN behaviour
@@ -486,6 +491,127 @@ __global__ __launch_bounds__(kBlock) void softmax_xent_kernel(const float* __res
         __syncthreads();
     }
     if (threadIdx.x == 0 && loss_sum) loss_sum[0] = -running;
+}
+
+// ---- soft targets from labels (cnn_soft_targets) --------------------------------------------------------------------------------------
+// the partner of sample b under a pair rule (include/cnn_amd.h); `rule` is never CNN_PAIR_NONE here
+__device__ __forceinline__ int pair_of(int b, int B, int rule, int shift) {
+    if (rule == CNN_PAIR_FLIP) return B - 1 - b;
+    const int p = b + (shift - B);  // (b + shift) % B without the division: 1 <= shift < B
+    return p < 0 ? p + B : p;
+}
+struct SoftTargetArgs {
+    int B, classes, rule, shift;
+    float u, hot, lam, oml;  // u = smoothing / classes, hot = (1 - smoothing) + u, oml = 1 - lam: the host's fp32 values
+    bool smooth;             // smoothing != 0
+};
+// A lane per target value: t[b][j] = base(labels[b], j), or lam * base(labels[b], j) + oml * base(labels[p(b)], j) -- two products and one
+// sum, each rounded.  A label outside [0, classes) matches no j.
+__global__ __launch_bounds__(kBlock) void soft_targets_kernel(const int32_t* __restrict__ labels, float* __restrict__ targets, const SoftTargetArgs a) {
+#pragma clang fp contract(off)
+    const size_t n = (size_t)a.B * a.classes, stride = (size_t)gridDim.x * kBlock;
+    for (size_t e = (size_t)blockIdx.x * kBlock + threadIdx.x; e < n; e += stride) {
+        const int b = (int)(e / (size_t)a.classes), j = (int)(e - (size_t)b * a.classes);
+        const auto base = [&](int label) { return a.smooth ? (j == label ? a.hot : a.u) : (j == label ? 1.f : 0.f); };
+        const float own = base(labels[b]);
+        if (a.rule == CNN_PAIR_NONE) {
+            targets[e] = own;
+        } else {
+            const float other = base(labels[pair_of(b, a.B, a.rule, a.shift)]);
+            const float po = a.lam * own;
+            const float pp = a.oml * other;
+            targets[e] = po + pp;
+        }
+    }
+}
+
+// ---- mixup / CutMix of a batch with its partner samples (cnn_batch_mix) ---------------------------------------------------------------
+// Out of place: dst[b] from src[b] and src[p(b)].  The grid's rows walk the samples, so the partner is uniform in a workgroup and costs
+// no per-element division; inside a sample the columns of the grid run stream_walk over its C*H*W elements -- the float4 form when
+// every sample starts 16-byte aligned (both pointers aligned, C*H*W % 4 == 0), the scalar form otherwise.
+struct BmixArgs {
+    size_t ns;  // elements per sample
+    int B, rule, shift;
+};
+__device__ __forceinline__ float mix_one(float a, float p, float lam, float oml) {
+#pragma clang fp contract(off)
+    const float la = lam * a;
+    const float op = oml * p;
+    return la + op;
+}
+// mixup: reads the sample and its partner, writes the mix (12 B per element)
+struct MixupOp {
+    const float* own;
+    const float* partner;
+    float* out;
+    float lam, oml;
+    template <class V>
+    __device__ __forceinline__ void run(size_t i) const {
+        V av = at<V>(own, i);
+        const V pv = at<V>(partner, i);
+        each<V>([&](float& ae, float pe) { ae = mix_one(ae, pe, lam, oml); }, av, pv);
+        at<V>(out, i) = av;
+    }
+};
+// CutMix: a copy of the bits, from the partner inside the box and from the sample outside (8 B per element: a float4 that lies wholly
+// inside or outside requests one of the two lines, only one that the box's edge cuts requests both).  Row and column of an element come
+// from two 32-bit divisions per float4 (or per element in the scalar form); a float4 that runs over the end of its row (W % 4 != 0) takes
+// them per element.
+struct CutBox {
+    uint32_t H, W, y0, y1, x0, x1;
+    __device__ __forceinline__ bool holds(uint32_t e) const {
+        const uint32_t row = e / W, x = e - row * W, y = row % H;
+        return y >= y0 && y < y1 && x >= x0 && x < x1;
+    }
+};
+struct CutmixOp {
+    const float* own;
+    const float* partner;
+    float* out;
+    CutBox box;
+    template <class V>
+    __device__ __forceinline__ void run(size_t i) const {
+        if constexpr (std::is_same<V, float>::value) {
+            at<V>(out, i) = box.holds((uint32_t)i) ? partner[i] : own[i];
+        } else {
+            const uint32_t e = (uint32_t)i * 4u;
+            const uint32_t row = e / box.W, x = e - row * box.W, y = row % box.H;
+            unsigned bits = 0;
+            if (x + 3 < box.W) {  // the four elements share a row
+                if (y >= box.y0 && y < box.y1)
+#pragma unroll
+                    for (uint32_t j = 0; j < 4; ++j) bits |= (x + j >= box.x0 && x + j < box.x1) ? (1u << j) : 0u;
+            } else {
+#pragma unroll
+                for (uint32_t j = 0; j < 4; ++j) bits |= box.holds(e + j) ? (1u << j) : 0u;
+            }
+            V v;
+            if (bits == 0u) {
+                v = at<V>(own, i);
+            } else if (bits == 15u) {
+                v = at<V>(partner, i);
+            } else {
+                v = at<V>(own, i);
+                const V pv = at<V>(partner, i);
+                each_bit<V>(bits, [](float& ve, float pe, bool inside) { ve = inside ? pe : ve; }, v, pv);
+            }
+            at<V>(out, i) = v;
+        }
+    }
+};
+template <bool kVec>
+__global__ __launch_bounds__(kBlock) void bmix_mixup(const float* __restrict__ src, float* __restrict__ dst, const BmixArgs a, float lam, float oml) {
+    for (int b = blockIdx.y; b < a.B; b += gridDim.y) {
+        const MixupOp op{src + (size_t)b * a.ns, src + (size_t)pair_of(b, a.B, a.rule, a.shift) * a.ns, dst + (size_t)b * a.ns, lam, oml};
+        stream_walk<kVec>(op, 0, a.ns);
+    }
+}
+template <bool kVec>
+__global__ __launch_bounds__(kBlock) void bmix_cutmix(const float* __restrict__ src, float* __restrict__ dst, const BmixArgs a, const CutBox box) {
+    for (int b = blockIdx.y; b < a.B; b += gridDim.y) {
+        const CutmixOp op{src + (size_t)b * a.ns, src + (size_t)pair_of(b, a.B, a.rule, a.shift) * a.ns, dst + (size_t)b * a.ns, box};
+        stream_walk<kVec>(op, 0, a.ns);
+    }
 }
 
 // ---- host side: the one launcher of the streaming shape -----------------------------------------------------------------------------
@@ -819,9 +945,103 @@ int cnn_softmax_xent(const float* logits, const int32_t* labels, float* probs, f
     CNN_REQUIRE(B > 0 && classes > 0, "cnn_softmax_xent: B=%d classes=%d", B, classes);
     hipStream_t s = as_stream(stream);
     CNN_KLAUNCH(s, "softmax_xent_kernel",
-                (softmax_xent_kernel<<<1, kBlock, 0, s>>>(logits, labels, probs, delta, loss_sum, B, classes)), "B=%d classes=%d",
+                (softmax_xent_kernel<false><<<1, kBlock, 0, s>>>(logits, labels, probs, delta, loss_sum, B, classes)), "B=%d classes=%d",
                 B, classes);
     return CNN_AMD_OK;
+}
+
+int cnn_softmax_xent_soft(const float* logits, const float* targets, float* probs, float* delta, float* loss_sum, int B, int classes,
+                          void* stream) {
+    CNN_REQUIRE(logits && targets && delta, "cnn_softmax_xent_soft: null pointer");
+    CNN_REQUIRE(B > 0 && classes > 0, "cnn_softmax_xent_soft: B=%d classes=%d", B, classes);
+    hipStream_t s = as_stream(stream);
+    CNN_KLAUNCH(s, "softmax_xent_soft_kernel",
+                (softmax_xent_kernel<true><<<1, kBlock, 0, s>>>(logits, targets, probs, delta, loss_sum, B, classes)), "B=%d classes=%d", B,
+                classes);
+    return CNN_AMD_OK;
+}
+
+// the partner rule of cnn_soft_targets / cnn_batch_mix, checked on the host: the rule is known, a ROLL shift lies in [1, B)
+static int check_pair_rule(const char* entry, int B, int pair_rule, int pair_shift) {
+    CNN_REQUIRE(pair_rule == CNN_PAIR_NONE || pair_rule == CNN_PAIR_FLIP || pair_rule == CNN_PAIR_ROLL, "%s: unknown pair_rule=%d", entry, pair_rule);
+    CNN_REQUIRE(pair_rule != CNN_PAIR_ROLL || (pair_shift >= 1 && pair_shift < B), "%s: CNN_PAIR_ROLL shift=%d outside [1, B=%d)", entry, pair_shift, B);
+    return CNN_AMD_OK;
+}
+
+int cnn_soft_targets(const int32_t* labels, float* targets, int B, int classes, float smoothing, float lam, int pair_rule, int pair_shift,
+                     void* stream) {
+    CNN_REQUIRE(labels && targets, "cnn_soft_targets: null pointer");
+    CNN_REQUIRE(B > 0 && classes > 0, "cnn_soft_targets: B=%d classes=%d", B, classes);
+    CNN_REQUIRE(smoothing >= 0.f && smoothing < 1.f, "cnn_soft_targets: smoothing=%g outside [0, 1)", (double)smoothing);
+    CNN_REQUIRE(lam >= 0.f && lam <= 1.f, "cnn_soft_targets: lam=%g outside [0, 1]", (double)lam);
+    if (int rc = check_pair_rule("cnn_soft_targets", B, pair_rule, pair_shift)) return rc;
+    SoftTargetArgs a;
+    a.B = B;
+    a.classes = classes;
+    a.smooth = smoothing != 0.f;
+    const volatile float u = smoothing / (float)classes;  // (volatile: every operation rounded to fp32 on its own)
+    const volatile float keep = 1.f - smoothing;
+    a.u = u;
+    a.hot = keep + u;
+    a.lam = lam;
+    a.oml = 1.f - lam;
+    a.rule = lam == 1.f ? CNN_PAIR_NONE : pair_rule;
+    a.shift = pair_shift;
+    hipStream_t s = as_stream(stream);
+    const size_t n = (size_t)B * classes;
+    CNN_KLAUNCH(s, "soft_targets_kernel", (soft_targets_kernel<<<stream_grid(n, kBlock), kBlock, 0, s>>>(labels, targets, a)), "B=%d classes=%d rule=%d", B,
+                classes, a.rule);
+    return CNN_AMD_OK;
+}
+
+float cnn_cutmix_lambda(int H, int W, int y0, int y1, int x0, int x1) {
+    return (float)(1.0 - (double)((long long)(y1 - y0) * (x1 - x0)) / ((double)H * W));
+}
+
+int cnn_batch_mix(const cnn_mix_desc* d, const float* src, float* dst, int B, int C, int H, int W, void* stream) {
+    CNN_REQUIRE(d && src && dst, "cnn_batch_mix: null pointer");
+    CNN_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, "cnn_batch_mix: B=%d C=%d H=%d W=%d", B, C, H, W);
+    CNN_REQUIRE((long long)C * H * W < (1ll << 31), "cnn_batch_mix: a sample of C=%d H=%d W=%d exceeds 2^31 - 1 elements", C, H, W);
+    CNN_REQUIRE(d->mode == CNN_MIX_MIXUP || d->mode == CNN_MIX_CUTMIX, "cnn_batch_mix: unknown mode=%d", d->mode);
+    if (int rc = check_pair_rule("cnn_batch_mix", B, d->pair_rule, d->pair_shift)) return rc;
+    if (d->mode == CNN_MIX_MIXUP)
+        CNN_REQUIRE(d->lam >= 0.f && d->lam <= 1.f, "cnn_batch_mix: lam=%g outside [0, 1]", (double)d->lam);
+    else
+        CNN_REQUIRE(0 <= d->y0 && d->y0 <= d->y1 && d->y1 <= H && 0 <= d->x0 && d->x0 <= d->x1 && d->x1 <= W,
+                    "cnn_batch_mix: box y=[%d, %d) x=[%d, %d) outside the %d x %d plane or reversed", d->y0, d->y1, d->x0, d->x1, H, W);
+    const size_t ns = (size_t)C * H * W, n = ns * (size_t)B;
+    CNN_REQUIRE(!floats_overlap(dst, src, n), "cnn_batch_mix: dst and src are the same buffer or overlap");
+    hipStream_t s = as_stream(stream);
+    const bool aligned = aligned16(src) && aligned16(dst);
+    const bool empty_box = d->mode == CNN_MIX_CUTMIX && (d->y0 == d->y1 || d->x0 == d->x1);
+    if (d->pair_rule == CNN_PAIR_NONE || empty_box || (d->mode == CNN_MIX_MIXUP && d->lam == 1.f))  // nothing is mixed: the copy of the bits
+        return launch_stream(s, "bmix_copy_vec", gacc_vec<true>, "bmix_copy_scalar", gacc_scalar<true>, kTailRides, aligned, n, -1, GaccOp<true>{dst, src});
+    // a sample per grid row (the partner is workgroup-uniform), the walker inside the sample; the float4 form where every sample starts
+    // 16-byte aligned
+    BmixArgs a;
+    a.ns = ns;
+    a.B = B;
+    a.rule = d->pair_rule;
+    a.shift = d->pair_shift;
+    const auto grid = [&](size_t work_items) {
+        const unsigned gy = (unsigned)(B < 65535 ? B : 65535);
+        const unsigned want = stream_grid(work_items * gy, kBlock), gx = (want + gy - 1) / gy;
+        const unsigned need = (unsigned)((work_items + kBlock - 1) / kBlock);
+        return dim3(gx < need ? gx : need, gy);
+    };
+    const bool vec = aligned && ns % 4 == 0;
+    if (d->mode == CNN_MIX_MIXUP) {
+        const float lam = d->lam, oml = 1.f - d->lam;
+        return launch_stream(
+            s, "bmix_mixup_vec", "bmix_mixup_scalar", kTailRides, vec, ns, -1,
+            [&](unsigned, size_t) { bmix_mixup<true><<<grid(ns / 4), kBlock, 0, s>>>(src, dst, a, lam, oml); },
+            [&](unsigned, size_t) { bmix_mixup<false><<<grid(ns), kBlock, 0, s>>>(src, dst, a, lam, oml); });
+    }
+    const CutBox box{(uint32_t)H, (uint32_t)W, (uint32_t)d->y0, (uint32_t)d->y1, (uint32_t)d->x0, (uint32_t)d->x1};
+    return launch_stream(
+        s, "bmix_cutmix_vec", "bmix_cutmix_scalar", kTailRides, vec, ns, -1,
+        [&](unsigned, size_t) { bmix_cutmix<true><<<grid(ns / 4), kBlock, 0, s>>>(src, dst, a, box); },
+        [&](unsigned, size_t) { bmix_cutmix<false><<<grid(ns), kBlock, 0, s>>>(src, dst, a, box); });
 }
 
 int cnn_dropout_forward(const float* x, float* y, int B, int C, int H, int W, int dropped_channels, int training, float keep,

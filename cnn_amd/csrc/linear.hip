@@ -2,6 +2,7 @@
 // The reference net's layer is 4608 -> 3: a skinny contraction that is HBM-bound on x (4*in bytes per sample),
 // so these are wave-reduction / streaming kernels, not MFMA tiles.
 #include <cfloat>
+#include <type_traits>
 
 #include "common.h"
 
@@ -81,9 +82,26 @@ __device__ __forceinline__ float clamped_exp_l(float v) {
 // sample slot behind the batch's end (s >= ns) computes sample g*S once more -- its loads stay inside the operands -- and stores
 // nothing.  bias and the labels depend on nothing computed: they are requested in front of the first operand batch by the threads
 // that use them, not behind the barriers where they are used.
-template <bool BATCH, int DX, int S>
+//
+// SOFT (cnn_linear_forward_softmax_xent_soft*): `labels` is a dense [B][out] fp32 target tensor and yv = targets[b][i] takes the place of
+// (i == label ? 1 : 0); nothing else changes -- delta = pr - yv and term += logf(pr) * yv are the same expressions in the same order, so a
+// one-hot target tensor gives the hard-label kernel's bits.  A sample's `out` target values are requested where the label is: in front
+// of the first operand batch, by the lane that runs the sample's softmax (a slot behind the batch's end reads sample b0's row).
+template <bool SOFT>
+using head_label_t = std::conditional_t<SOFT, float, int32_t>;
+
+// element i of a small register array without dynamic indexing (a select chain; i < N)
+template <int N>
+__device__ __forceinline__ float pick(const float (&v)[N], int i) {
+    float r = v[0];
+#pragma unroll
+    for (int j = 1; j < N; ++j) r = i == j ? v[j] : r;
+    return r;
+}
+
+template <bool BATCH, int DX, int S, bool SOFT = false>
 __global__ __launch_bounds__(kBlock) void linear_fwd_softmax_xent(const float* __restrict__ x, const float* __restrict__ w,
-                                                                  const float* __restrict__ bias, const int32_t* __restrict__ labels,
+                                                                  const float* __restrict__ bias, const head_label_t<SOFT>* __restrict__ labels,
                                                                   float* __restrict__ y, float* __restrict__ probs,
                                                                   float* __restrict__ delta, float* __restrict__ loss_terms, int B,
                                                                   int in, int out, float* __restrict__ dx) {
@@ -103,7 +121,15 @@ __global__ __launch_bounds__(kBlock) void linear_fwd_softmax_xent(const float* _
     const int ts = S > 1 ? (int)threadIdx.x / 3 : 0, tj = S > 1 ? (int)threadIdx.x - ts * 3 : (int)threadIdx.x;
     const bool reducer = S > 1 ? threadIdx.x < S * 3 : (int)threadIdx.x < out;
     const float bias_v = bias[reducer ? tj : 0];
-    const int label_v = labels[b0 + ((int)threadIdx.x < ns ? (int)threadIdx.x : 0)];
+    int label_v = 0;
+    float target_v[NJ];
+    if constexpr (SOFT) {
+        const float* trow = labels + (size_t)(b0 + ((int)threadIdx.x < ns ? (int)threadIdx.x : 0)) * out;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) target_v[j] = trow[j < out ? j : 0];
+    } else {
+        label_v = labels[b0 + ((int)threadIdx.x < ns ? (int)threadIdx.x : 0)];
+    }
     const float* xs[S];
 #pragma unroll
     for (int s = 0; s < S; ++s) xs[s] = x + (size_t)(b0 + (s < ns ? s : 0)) * in;
@@ -208,7 +234,9 @@ __global__ __launch_bounds__(kBlock) void linear_fwd_softmax_xent(const float* _
         for (int i = 0; i < out; ++i) {
             float pr = clamped_exp_l(logit[sl][i] - mx) / sum;
             if (isnan(pr)) pr = 0.f;
-            const float yv = (i == label) ? 1.f : 0.f;
+            float yv;
+            if constexpr (SOFT) yv = pick(target_v, i);
+            else yv = (i == label) ? 1.f : 0.f;
             if (probs) probs[b * out + i] = pr;
             delta[b * out + i] = pr - yv;
             if (DX != 0) dl[sl][i] = pr - yv;
@@ -289,15 +317,15 @@ int head_samples(int out) {  // 0: a value no kernel is built for
     return out == 3 ? S : 1;
 }
 
-template <int DX>
-void launch_head_dx(int S, hipStream_t s, const float* x, const float* w, const float* bias, const int32_t* labels, float* logits,
+template <int DX, bool SOFT>
+void launch_head_dx(int S, hipStream_t s, const float* x, const float* w, const float* bias, const head_label_t<SOFT>* labels, float* logits,
                     float* probs, float* delta, float* loss_terms, int B, int in, int out, float* dx) {
     const dim3 grid(ceil_div(B, S)), block(kBlock);
     switch (S) {
-    case 8: launch_pub(linear_fwd_softmax_xent<true, DX, 8>, grid, block, 0, s, x, w, bias, labels, logits, probs, delta, loss_terms, B, in, out, dx); break;
-    case 4: launch_pub(linear_fwd_softmax_xent<true, DX, 4>, grid, block, 0, s, x, w, bias, labels, logits, probs, delta, loss_terms, B, in, out, dx); break;
-    case 2: launch_pub(linear_fwd_softmax_xent<true, DX, 2>, grid, block, 0, s, x, w, bias, labels, logits, probs, delta, loss_terms, B, in, out, dx); break;
-    default: launch_pub(linear_fwd_softmax_xent<true, DX, 1>, grid, block, 0, s, x, w, bias, labels, logits, probs, delta, loss_terms, B, in, out, dx); break;
+    case 8: launch_pub(linear_fwd_softmax_xent<true, DX, 8, SOFT>, grid, block, 0, s, x, w, bias, labels, logits, probs, delta, loss_terms, B, in, out, dx); break;
+    case 4: launch_pub(linear_fwd_softmax_xent<true, DX, 4, SOFT>, grid, block, 0, s, x, w, bias, labels, logits, probs, delta, loss_terms, B, in, out, dx); break;
+    case 2: launch_pub(linear_fwd_softmax_xent<true, DX, 2, SOFT>, grid, block, 0, s, x, w, bias, labels, logits, probs, delta, loss_terms, B, in, out, dx); break;
+    default: launch_pub(linear_fwd_softmax_xent<true, DX, 1, SOFT>, grid, block, 0, s, x, w, bias, labels, logits, probs, delta, loss_terms, B, in, out, dx); break;
     }
 }
 
@@ -478,6 +506,45 @@ static void launch_bwd_fused(hipStream_t s, int variant, const float* x, const f
     }
 }
 
+// the two head entries, hard labels (SOFT = false: `labels` int32 [B]) or dense targets (SOFT = true: fp32 [B][out]); `entry` / `name`:
+// the entry's name in messages, the kernel's in the launch log
+template <bool SOFT>
+int head_forward(const char* entry, const char* name, const float* x, const float* w, const float* bias, const head_label_t<SOFT>* labels,
+                        float* logits, float* probs, float* delta, float* loss_terms, int B, int in, int out, void* stream) {
+    CNN_REQUIRE(x && w && bias && labels && logits && delta && loss_terms, "%s: null pointer", entry);
+    CNN_REQUIRE(B > 0 && in > 0 && out > 0 && out <= kOutTile, "%s: B=%d in=%d out=%d (out <= %d)", entry, B, in, out, kOutTile);
+    hipStream_t s = as_stream(stream);
+    // (always one sample per workgroup: not on the train step's path, and the reference the S > 1 kernels are tested against)
+    const OptVal e = CNN_OPT_VAL("NO_HEAD_BATCH");  // A/B switch: the plain 6-deep loop for every layer width
+    if (e && atoi(e) != 0)
+        CNN_KLAUNCH(s, name,
+                    (linear_fwd_softmax_xent<false, 0, 1, SOFT><<<B, kBlock, 0, s>>>(x, w, bias, labels, logits, probs, delta, loss_terms, B, in, out, nullptr)),
+                    "B%d in%d out%d", B, in, out);
+    else
+        CNN_KLAUNCH(s, name,
+                    (linear_fwd_softmax_xent<true, 0, 1, SOFT><<<B, kBlock, 0, s>>>(x, w, bias, labels, logits, probs, delta, loss_terms, B, in, out, nullptr)),
+                    "B%d in%d out%d", B, in, out);
+    return CNN_AMD_OK;
+}
+
+template <bool SOFT>
+int head_forward_dx(const char* entry, const char* name, const char* name_relu, const float* x, const float* w, const float* bias,
+                           const head_label_t<SOFT>* labels, float* logits, float* probs, float* delta, float* loss_terms, float* dx, int relu_below,
+                           int B, int in, int out, void* stream) {
+    CNN_REQUIRE(x && w && bias && labels && logits && delta && loss_terms && dx, "%s: null pointer", entry);
+    CNN_REQUIRE(B > 0 && in > 0 && out > 0 && out <= kOutTile, "%s: B=%d in=%d out=%d (out <= %d)", entry, B, in, out, kOutTile);
+    hipStream_t s = as_stream(stream);
+    const int S = head_samples(out);
+    CNN_REQUIRE(S > 0, "%s: CNN_AMD_HEAD_SAMPLES must be 1, 2, 4 or 8", entry);
+    if (relu_below)
+        CNN_KLAUNCH(s, name_relu, (launch_head_dx<2, SOFT>(S, s, x, w, bias, labels, logits, probs, delta, loss_terms, B, in, out, dx)), "B%d in%d out%d", B,
+                    in, out);
+    else
+        CNN_KLAUNCH(s, name, (launch_head_dx<1, SOFT>(S, s, x, w, bias, labels, logits, probs, delta, loss_terms, B, in, out, dx)), "B%d in%d out%d", B, in,
+                    out);
+    return CNN_AMD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -528,41 +595,28 @@ static int linear_backward_impl(const float* x, const float* dy, const float* w,
 
 int cnn_linear_forward_softmax_xent(const float* x, const float* w, const float* bias, const int32_t* labels, float* logits,
                                     float* probs, float* delta, float* loss_terms, int B, int in, int out, void* stream) {
-    CNN_REQUIRE(x && w && bias && labels && logits && delta && loss_terms, "cnn_linear_forward_softmax_xent: null pointer");
-    CNN_REQUIRE(B > 0 && in > 0 && out > 0 && out <= kOutTile, "cnn_linear_forward_softmax_xent: B=%d in=%d out=%d (out <= %d)", B, in, out,
-                kOutTile);
-    hipStream_t s = as_stream(stream);
-    // (always one sample per workgroup: not on the train step's path, and the reference the S > 1 kernels are tested against)
-    const OptVal e = CNN_OPT_VAL("NO_HEAD_BATCH");  // A/B switch: the plain 6-deep loop for every layer width
-    if (e && atoi(e) != 0)
-        CNN_KLAUNCH(s, "linear_fwd+softmax_xent",
-                    (linear_fwd_softmax_xent<false, 0, 1><<<B, kBlock, 0, s>>>(x, w, bias, labels, logits, probs, delta, loss_terms, B, in, out, nullptr)),
-                    "B%d in%d out%d", B, in, out);
-    else
-        CNN_KLAUNCH(s, "linear_fwd+softmax_xent",
-                    (linear_fwd_softmax_xent<true, 0, 1><<<B, kBlock, 0, s>>>(x, w, bias, labels, logits, probs, delta, loss_terms, B, in, out, nullptr)),
-                    "B%d in%d out%d", B, in, out);
-    return CNN_AMD_OK;
+    return head_forward<false>("cnn_linear_forward_softmax_xent", "linear_fwd+softmax_xent", x, w, bias, labels, logits, probs, delta, loss_terms, B, in, out,
+                               stream);
+}
+
+int cnn_linear_forward_softmax_xent_soft(const float* x, const float* w, const float* bias, const float* targets, float* logits,
+                                         float* probs, float* delta, float* loss_terms, int B, int in, int out, void* stream) {
+    return head_forward<true>("cnn_linear_forward_softmax_xent_soft", "linear_fwd+softmax_xent_soft", x, w, bias, targets, logits, probs, delta, loss_terms, B,
+                              in, out, stream);
 }
 
 int cnn_linear_forward_softmax_xent_dx(const float* x, const float* w, const float* bias, const int32_t* labels, float* logits,
                                        float* probs, float* delta, float* loss_terms, float* dx, int relu_below, int B, int in, int out,
                                        void* stream) {
-    CNN_REQUIRE(x && w && bias && labels && logits && delta && loss_terms && dx, "cnn_linear_forward_softmax_xent_dx: null pointer");
-    CNN_REQUIRE(B > 0 && in > 0 && out > 0 && out <= kOutTile, "cnn_linear_forward_softmax_xent_dx: B=%d in=%d out=%d (out <= %d)", B, in, out,
-                kOutTile);
-    hipStream_t s = as_stream(stream);
-    const int S = head_samples(out);
-    CNN_REQUIRE(S > 0, "cnn_linear_forward_softmax_xent_dx: CNN_AMD_HEAD_SAMPLES must be 1, 2, 4 or 8");
-    if (relu_below)
-        CNN_KLAUNCH(s, "linear_fwd+softmax_xent+dx+relu",
-                    (launch_head_dx<2>(S, s, x, w, bias, labels, logits, probs, delta, loss_terms, B, in, out, dx)),
-                    "B%d in%d out%d", B, in, out);
-    else
-        CNN_KLAUNCH(s, "linear_fwd+softmax_xent+dx",
-                    (launch_head_dx<1>(S, s, x, w, bias, labels, logits, probs, delta, loss_terms, B, in, out, dx)),
-                    "B%d in%d out%d", B, in, out);
-    return CNN_AMD_OK;
+    return head_forward_dx<false>("cnn_linear_forward_softmax_xent_dx", "linear_fwd+softmax_xent+dx", "linear_fwd+softmax_xent+dx+relu", x, w, bias, labels,
+                                  logits, probs, delta, loss_terms, dx, relu_below, B, in, out, stream);
+}
+
+int cnn_linear_forward_softmax_xent_soft_dx(const float* x, const float* w, const float* bias, const float* targets, float* logits,
+                                            float* probs, float* delta, float* loss_terms, float* dx, int relu_below, int B, int in, int out,
+                                            void* stream) {
+    return head_forward_dx<true>("cnn_linear_forward_softmax_xent_soft_dx", "linear_fwd+softmax_xent_soft+dx", "linear_fwd+softmax_xent_soft+dx+relu", x, w,
+                                 bias, targets, logits, probs, delta, loss_terms, dx, relu_below, B, in, out, stream);
 }
 
 int cnn_loss_from_terms(const float* loss_terms, float* loss_sum, int B, void* stream) {

@@ -343,8 +343,11 @@ public:
     bool loss_head_supported() const { return out_channels <= 8; }
     // with_dx: the same kernel also writes this layer's data gradient (cnn_linear_forward_softmax_xent_dx: a sample's row needs only
     // that sample's delta); backward() then only launches the weight / bias gradient, on the library's side stream
+    // targets_dev != nullptr: dense targets, float [B][out] on the device, take the labels' place (labels_dev is not read): the
+    // cnn_linear_forward_softmax_xent_soft* entries, delta = p - target, loss term sum_j log p[j] * target[j]
     std::vector<tensor> forward_loss_head(const std::vector<tensor>& input, const int* labels_dev, data_type* probs_dev,
-                                          data_type* delta_dev, data_type* loss_terms_dev, bool with_dx = false);
+                                          data_type* delta_dev, data_type* loss_terms_dev, bool with_dx = false,
+                                          const data_type* targets_dev = nullptr);
     int out_features() const { return out_channels; }
     int in_features() const { return in_channels; }
     LinearLayer(std::string _name, const int _in_channels, const int _out_channels);
@@ -783,6 +786,32 @@ public:
     // recent step (-(1/B) * sum log p[label], func.cpp:67,71) -- the only call here that synchronises.
     void train_step(const std::vector<tensor>& input, const int* labels_dev, const data_type learning_rate);
     data_type last_loss();
+    // Soft targets: label smoothing, mixup and CutMix without leaving the fused step.  The three entries below and train_step share one
+    // body (run_step): the route -- fused loss head, fused step tail, deferred first-layer data gradient, every optimizer, clipping,
+    // accumulation, the average, set_comm -- depends on none of them.  A step against soft targets runs the soft loss head
+    // (cnn_linear_forward_softmax_xent_soft[_dx] where loss_head_supported(), cnn_linear_forward + cnn_softmax_xent_soft otherwise);
+    // last_loss() works unchanged: -(1/B) * sum_b sum_j t[b][j] * log p[b][j], the terms added in sample order.
+    //
+    // set_label_smoothing(eps), eps in [0, 1) (anything else is reported and aborts, as in the other setters; 0, the default, is off):
+    // every later train_step / forward_backward trains against the rows of cnn_soft_targets(labels, eps) -- (1 - eps) + eps / classes at
+    // the label, eps / classes elsewhere.  They are built on the device into a container-owned [B][classes] buffer by ONE small launch at
+    // the START of the step: it depends on nothing the step computes, so it never sits between the last convolution and the head.  With
+    // eps == 0 the step is the hard-label one: the same kernels, the same launch log, the same bits.
+    void set_label_smoothing(data_type eps);
+    data_type label_smoothing() const { return smoothing; }
+    // One step on a mixed batch: cnn_batch_mix of `input` into container-owned storage (mix.mode: CNN_MIX_MIXUP with mix.lam, or
+    // CNN_MIX_CUTMIX with the box; mix.pair_rule / pair_shift choose the partners, inside this replica's batch under set_comm), the
+    // targets lam * target(label) + (1 - lam) * target(partner's label) with the label smoothing set above, then the ordinary step.
+    // MIXUP: lam = mix.lam.  CUTMIX: lam = cnn_cutmix_lambda(H, W, box) -- the container computes it, the caller's field cannot disagree
+    // with the box.  A bad descriptor is reported by cnn_batch_mix and aborts like every failed library call.  Afterwards
+    // Layer::get_output(), the input delta and grad_cam() describe the MIXED batch.  MEMORY: one extra input batch, allocated by the
+    // first call and kept (154 MB at 256 x 3 x 224 x 224).
+    void train_step_mixed(const std::vector<tensor>& input, const int* labels_dev, const cnn_mix_desc& mix, const data_type learning_rate);
+    // One step against caller-provided dense targets, float [B][classes] on the device (distillation, per-sample mixing); the buffer
+    // must stay untouched until the step's kernels have run (it is read by the head kernel).  Label smoothing does not apply.
+    void train_step_soft(const std::vector<tensor>& input, const data_type* targets_dev, const data_type learning_rate);
+    // the target rows of the last step that trained against soft targets ([B][classes], device); null before the first one
+    const data_type* last_targets_device() const { return last_targets; }
     // TEST SUPPORT (tests/test_gpu_optimizer.py's host-stepped reference net; no product path calls it): train_step without its SGD
     // step, as the plain sequence (forward(), the loss kernel, backward(): no fused loss head, no fused step tail) -- the gradients of the
     // batch are left in the arena, last_loss() works.
@@ -795,6 +824,21 @@ public:
     void flush_deferred();
 private:
     void ensure_loss_buffers(int B, int classes);
+    // the body of every train step: labels_dev (hard labels) or targets_dev (dense targets), exactly one of them non-null
+    void run_step(const std::vector<tensor>& input, const int* labels_dev, const data_type* targets_dev, const data_type learning_rate);
+    // cnn_soft_targets into the container's buffer on architectures::stream; returns the buffer
+    const data_type* build_targets(const int* labels_dev, int B, int classes, data_type lam, int pair_rule, int pair_shift);
+    data_type smoothing = 0;
+    data_type* target_rows = nullptr;          // [loss_batch][classes], allocated by the first step that needs it
+    const data_type* last_targets = nullptr;
+    // the mixed batch of train_step_mixed.  ONE buffer, rewritten by the next mixed step's first launch on architectures::stream: every
+    // reader of a step's input is ordered on that stream before the step returns -- the first layer's forward and weight-gradient kernels
+    // run on it (fused_tail launches the block's weight gradient there on both of its branches; the plain sequence, which clipping,
+    // accumulation, the average and the bucketed exchange take, forks weight gradients to the library's side stream and joins it in
+    // backward() / flush_bucket() before the step), the deferred data gradient reads d(pool), the mask and the filter image but not the
+    // input, and a later get_output() re-computation is enqueued on the same stream before the next step's mix.
+    BatchBuffer mixed_input;
+    BatchBuffer mix_stage;  // (a host-resident input batch is staged here first)
     BatchBuffer loss_probs, loss_delta, logits_stage;   // [B][classes] each
     data_type* loss_terms = nullptr;      // [B] log p[label] (fused head) ...
     data_type* loss_sum = nullptr;        // ... or the ordered sum (unfused head); [1]

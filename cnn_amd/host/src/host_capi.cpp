@@ -31,6 +31,16 @@ std::vector<tensor>& host_batch(Handle* h, int B, int C, int H, int W) {
     }
     return h->host_input;
 }
+// zero-copy views of a caller-owned contiguous device batch, one set per batch buffer
+std::vector<tensor>& device_views(Handle* h, float* x_dev, int B, int H, int W) {
+    auto& views = h->device_inputs[x_dev];
+    if ((int)views.size() != B) {
+        views.clear();
+        const size_t len = (size_t)h->in_C * H * W;
+        for (int b = 0; b < B; ++b) views.emplace_back(Tensor3D::device_view(h->in_C, H, W, x_dev + len * b, "input_" + std::to_string(b)));
+    }
+    return views;
+}
 }  // namespace
 
 extern "C" {
@@ -304,6 +314,24 @@ void cnnh_net_forward_backward_device_loss(void* hv, float* x_dev, const int* la
         for (int b = 0; b < B; ++b) views.emplace_back(Tensor3D::device_view(h->in_C, H, W, x_dev + len * b, "input_" + std::to_string(b)));
     }
     h->net->forward_backward(views, labels_dev);
+}
+// Sequential::set_label_smoothing / train_step_mixed / train_step_soft / last_targets_device: the soft-target steps (architectures.h).
+// cnnh_net_get_targets copies the [B][classes] rows of the last soft step to the host: 1 before the first one.
+void cnnh_net_set_label_smoothing(void* hv, float eps) { ((Handle*)hv)->net->set_label_smoothing(eps); }
+void cnnh_net_train_step_mixed(void* hv, float* x_dev, const int* labels_dev, int B, int H, int W, const cnn_mix_desc* mix, float lr) {
+    Handle* h = (Handle*)hv;
+    h->net->train_step_mixed(device_views(h, x_dev, B, H, W), labels_dev, *mix, lr);
+}
+void cnnh_net_train_step_soft(void* hv, float* x_dev, const float* targets_dev, int B, int H, int W, float lr) {
+    Handle* h = (Handle*)hv;
+    h->net->train_step_soft(device_views(h, x_dev, B, H, W), targets_dev, lr);
+}
+int cnnh_net_get_targets(void* hv, float* host, int B) {
+    Handle* h = (Handle*)hv;
+    if (h->net->last_targets_device() == nullptr) return 1;
+    must(cnn_memcpy_d2h(host, h->net->last_targets_device(), sizeof(float) * (size_t)B * h->classes, stream), "cnn_memcpy_d2h");
+    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
+    return 0;
 }
 float cnnh_net_last_loss(void* hv) { return ((Handle*)hv)->net->last_loss(); }
 // the delta with respect to the network INPUT (the first layer's data gradient, conv2d.cpp:168-199; alexnet.cpp:55 discards it) of

@@ -830,7 +830,7 @@ std::vector<tensor> LinearLayer::forward(const std::vector<tensor>& input) {
 }
 
 std::vector<tensor> LinearLayer::forward_loss_head(const std::vector<tensor>& input, const int* labels_dev, data_type* probs_dev,
-                                                   data_type* delta_dev, data_type* loss_terms_dev, bool with_dx) {
+                                                   data_type* delta_dev, data_type* loss_terms_dev, bool with_dx, const data_type* targets_dev) {
     Tensor3D::device_work_enqueued();  // host copies of device views made before this call are stale from here on
     const int B = (int)input.size();
     delta_shape = input[0]->get_shape();
@@ -845,16 +845,26 @@ std::vector<tensor> LinearLayer::forward_loss_head(const std::vector<tensor>& in
             delta_buf.allocate(batch, std::get<0>(delta_shape), std::get<1>(delta_shape), std::get<2>(delta_shape), "linear_delta");
         // (this kernel is now the last one in front of the next layer's weight-gradient fork: it carries the event)
         if (publish_backward) must(cnn_amd_publish_next_kernel(stream), "cnn_amd_publish_next_kernel");
-        must(cnn_linear_forward_softmax_xent_dx(x, pb.params, pb.params + (size_t)in_channels * out_channels, labels_dev, out_buf.base, probs_dev,
-                                                delta_dev, loss_terms_dev, delta_buf.base, (relu_below != nullptr && fuse_layers) ? 1 : 0, B,
-                                                in_channels, out_channels, stream),
-             "cnn_linear_forward_softmax_xent_dx");
+        const int relu = (relu_below != nullptr && fuse_layers) ? 1 : 0;
+        if (targets_dev != nullptr)
+            must(cnn_linear_forward_softmax_xent_soft_dx(x, pb.params, pb.params + (size_t)in_channels * out_channels, targets_dev, out_buf.base, probs_dev,
+                                                         delta_dev, loss_terms_dev, delta_buf.base, relu, B, in_channels, out_channels, stream),
+                 "cnn_linear_forward_softmax_xent_soft_dx");
+        else
+            must(cnn_linear_forward_softmax_xent_dx(x, pb.params, pb.params + (size_t)in_channels * out_channels, labels_dev, out_buf.base, probs_dev,
+                                                    delta_dev, loss_terms_dev, delta_buf.base, relu, B, in_channels, out_channels, stream),
+                 "cnn_linear_forward_softmax_xent_dx");
         head_dx_done.arm();
         return first_n(output, B);
     }
-    must(cnn_linear_forward_softmax_xent(x, pb.params, pb.params + (size_t)in_channels * out_channels, labels_dev, out_buf.base, probs_dev,
-                                         delta_dev, loss_terms_dev, B, in_channels, out_channels, stream),
-         "cnn_linear_forward_softmax_xent");
+    if (targets_dev != nullptr)
+        must(cnn_linear_forward_softmax_xent_soft(x, pb.params, pb.params + (size_t)in_channels * out_channels, targets_dev, out_buf.base, probs_dev,
+                                                  delta_dev, loss_terms_dev, B, in_channels, out_channels, stream),
+             "cnn_linear_forward_softmax_xent_soft");
+    else
+        must(cnn_linear_forward_softmax_xent(x, pb.params, pb.params + (size_t)in_channels * out_channels, labels_dev, out_buf.base, probs_dev,
+                                             delta_dev, loss_terms_dev, B, in_channels, out_channels, stream),
+             "cnn_linear_forward_softmax_xent");
     return first_n(output, B);
 }
 

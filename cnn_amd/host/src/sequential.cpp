@@ -198,6 +198,7 @@ Sequential::~Sequential() {
         cnn_device_free(grad_arena);
     }
     if (loss_terms) cnn_device_free(loss_terms);
+    if (target_rows) cnn_device_free(target_rows);
     if (loss_sum) cnn_device_free(loss_sum);
     if (bn_comm) cnn_comm_destroy(bn_comm);
     if (comm_stream) cnn_stream_destroy(comm_stream);
@@ -621,26 +622,89 @@ void Sequential::forward_backward(const std::vector<tensor>& input, const int* l
     const int B = (int)input.size();
     const int classes = head->out_features();
     ensure_loss_buffers(B, classes);
+    // (label smoothing: the target rows are on their way before the forward pass starts)
+    const data_type* targets = smoothing != 0 ? build_targets(labels_dev, B, classes, 1.f, CNN_PAIR_NONE, 0) : nullptr;
+    if (targets != nullptr) last_targets = targets;
     const bool was_lazy = lazy_host_sync;
     lazy_host_sync = true;
     std::vector<tensor> output = forward(input);
     lazy_host_sync = was_lazy;
     const data_type* logits = batch_device_pointer(output, logits_stage, "logits");
-    must(cnn_softmax_xent(logits, labels_dev, loss_probs.base, loss_delta.base, loss_sum, B, classes, stream), "cnn_softmax_xent");
+    if (targets != nullptr)
+        must(cnn_softmax_xent_soft(logits, targets, loss_probs.base, loss_delta.base, loss_sum, B, classes, stream), "cnn_softmax_xent_soft");
+    else
+        must(cnn_softmax_xent(logits, labels_dev, loss_probs.base, loss_delta.base, loss_sum, B, classes, stream), "cnn_softmax_xent");
     loss_in_terms = false;
     loss_last_B = B;
     std::vector<tensor> delta(loss_delta.views.begin(), loss_delta.views.begin() + B);
     backward(delta);
 }
 
+void Sequential::set_label_smoothing(const data_type eps) {
+    if (!(eps >= 0 && eps < 1)) {
+        std::fprintf(stderr, "cnn_amd host: set_label_smoothing: eps=%g outside [0, 1) (0 = off)\n", (double)eps);
+        std::abort();
+    }
+    smoothing = eps;
+}
+
+// the rows of this step's soft targets, from the labels: one small launch on the compute stream, in front of everything else of the step
+const data_type* Sequential::build_targets(const int* labels_dev, const int B, const int classes, const data_type lam, const int pair_rule,
+                                           const int pair_shift) {
+    assert(loss_batch >= B);
+    if (target_rows == nullptr) target_rows = (data_type*)dev_alloc(sizeof(data_type) * (size_t)loss_batch * classes);
+    must(cnn_soft_targets(labels_dev, target_rows, B, classes, smoothing, lam, pair_rule, pair_shift, stream), "cnn_soft_targets");
+    return target_rows;
+}
+
+// the logits layer of a train step (its out_features() is the class count)
+static LinearLayer* loss_head_of(const std::list<std::shared_ptr<Layer> >& layers) {
+    auto* head = layers.empty() ? nullptr : dynamic_cast<LinearLayer*>(layers.back().get());
+    assert(head != nullptr && "train_step: the last layer must be a LinearLayer (the logits)");
+    return head;
+}
+
 // cnn.cpp:79-90 without leaving the device
 void Sequential::train_step(const std::vector<tensor>& input, const int* labels_dev, const data_type learning_rate) {
-    assert(!input.empty() && labels_dev != nullptr && !layers_sequence.empty());
-    auto* head = dynamic_cast<LinearLayer*>(layers_sequence.back().get());
-    assert(head != nullptr && "train_step: the last layer must be a LinearLayer (the logits)");
+    assert(!input.empty() && labels_dev != nullptr);
+    if (smoothing == 0) return run_step(input, labels_dev, nullptr, learning_rate);  // (the hard-label step, launch for launch)
+    const int B = (int)input.size(), classes = loss_head_of(layers_sequence)->out_features();
+    ensure_loss_buffers(B, classes);
+    run_step(input, nullptr, build_targets(labels_dev, B, classes, 1.f, CNN_PAIR_NONE, 0), learning_rate);
+}
+
+void Sequential::train_step_soft(const std::vector<tensor>& input, const data_type* targets_dev, const data_type learning_rate) {
+    assert(!input.empty() && targets_dev != nullptr);
+    run_step(input, nullptr, targets_dev, learning_rate);
+}
+
+void Sequential::train_step_mixed(const std::vector<tensor>& input, const int* labels_dev, const cnn_mix_desc& mix, const data_type learning_rate) {
+    assert(!input.empty() && labels_dev != nullptr);
+    const int B = (int)input.size(), classes = loss_head_of(layers_sequence)->out_features();
+    const int C = input[0]->C, H = input[0]->H, W = input[0]->W;
+    ensure_loss_buffers(B, classes);
+    if ((int)mixed_input.views.size() < B || mixed_input.sample_len != (size_t)C * H * W || mixed_input.views[0]->H != H ||
+        mixed_input.views[0]->W != W) {
+        flush_deferred();  // (nothing of an earlier step may still read storage that is about to be replaced)
+        must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
+        mixed_input.allocate(B, C, H, W, "mixed_input");
+    }
+    const data_type* src = batch_device_pointer(input, mix_stage, "train_step_mixed");
+    must(cnn_batch_mix(&mix, src, mixed_input.base, B, C, H, W, stream), "cnn_batch_mix");
+    // (the box decides CutMix's weight, never the caller's field)
+    const data_type lam = mix.mode == CNN_MIX_CUTMIX ? cnn_cutmix_lambda(H, W, mix.y0, mix.y1, mix.x0, mix.x1) : mix.lam;
+    const data_type* targets = build_targets(labels_dev, B, classes, lam, mix.pair_rule, mix.pair_shift);
+    const std::vector<tensor> mixed(mixed_input.views.begin(), mixed_input.views.begin() + B);
+    run_step(mixed, nullptr, targets, learning_rate);
+}
+
+void Sequential::run_step(const std::vector<tensor>& input, const int* labels_dev, const data_type* targets_dev, const data_type learning_rate) {
+    assert(!input.empty() && (labels_dev != nullptr) != (targets_dev != nullptr) && !layers_sequence.empty());
+    LinearLayer* head = loss_head_of(layers_sequence);
     const int B = (int)input.size();
     const int classes = head->out_features();
     ensure_loss_buffers(B, classes);
+    if (targets_dev != nullptr) last_targets = targets_dev;
     if (print_info) input[0]->print_shape();
     unswap_ema();  // (a step trains the training weights: an average swapped in for evaluation goes back first)
     if (finalized && fuse_layers && !filters_prepared) {
@@ -667,7 +731,7 @@ void Sequential::train_step(const std::vector<tensor>& input, const int* labels_
         }
         if (release_here) must(cnn_amd_publish_next_kernel(stream), "cnn_amd_publish_next_kernel");
         if (layer.get() == head && fused_head)
-            output = head->forward_loss_head(output, labels_dev, loss_probs.base, loss_delta.base, loss_terms, head_dx);
+            output = head->forward_loss_head(output, labels_dev, loss_probs.base, loss_delta.base, loss_terms, head_dx, targets_dev);
         else
             output = layer->forward(output);
         if (release_here) {
@@ -694,7 +758,10 @@ void Sequential::train_step(const std::vector<tensor>& input, const int* labels_
     lazy_host_sync = was_lazy;
     if (!fused_head) {
         const data_type* logits = batch_device_pointer(output, logits_stage, "logits");
-        must(cnn_softmax_xent(logits, labels_dev, loss_probs.base, loss_delta.base, loss_sum, B, classes, stream), "cnn_softmax_xent");
+        if (targets_dev != nullptr)
+            must(cnn_softmax_xent_soft(logits, targets_dev, loss_probs.base, loss_delta.base, loss_sum, B, classes, stream), "cnn_softmax_xent_soft");
+        else
+            must(cnn_softmax_xent(logits, labels_dev, loss_probs.base, loss_delta.base, loss_sum, B, classes, stream), "cnn_softmax_xent");
     }
     loss_in_terms = fused_head;
     loss_last_B = B;

@@ -79,6 +79,10 @@ SIGNATURES = {
     "cnnh_net_train_step_device_loss": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float]),
     "cnnh_net_forward_backward_device_loss": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "cnnh_net_last_loss": (C.c_float, [C.c_void_p]),
+    "cnnh_net_set_label_smoothing": (None, [C.c_void_p, C.c_float]),
+    "cnnh_net_train_step_mixed": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(capi.MixDesc), C.c_float]),
+    "cnnh_net_train_step_soft": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float]),
+    "cnnh_net_get_targets": (C.c_int, [C.c_void_p, _F, C.c_int]),
     "cnnh_net_flush": (None, [C.c_void_p]),
     "cnnh_net_input_delta": (C.c_int, [C.c_void_p, _F, C.c_size_t]),
     "cnnh_net_layer_output": (C.c_int, [C.c_void_p, C.c_char_p, _F, C.c_size_t]),
@@ -105,6 +109,26 @@ def load():
 
 def _fp(a):
     return a.ctypes.data_as(_F)
+
+
+def mix_params(rng, H, W, mixup_alpha=0.8, cutmix_alpha=1.0, switch_prob=0.5, pair_rule=capi.PAIR_FLIP, pair_shift=0):
+    """One batch's mixing parameters, sampled on the host the way timm's Mixup does: lam ~ Beta(a, a) from `rng` (a
+    numpy.random.Generator); CutMix with probability switch_prob when both alphas are positive (always when only cutmix_alpha is),
+    mixup otherwise.  CutMix: a box of side ratio sqrt(1 - lam) around a uniform centre, clipped to the plane; the descriptor's lam is
+    then the clipped box's own (cnn_cutmix_lambda).  Returns a capi.MixDesc for HostNet.train_step_mixed / capi.batch_mix."""
+    if mixup_alpha <= 0 and cutmix_alpha <= 0:
+        raise capi.CnnAmdError("mix_params: one of mixup_alpha and cutmix_alpha must be positive")
+    use_cutmix = cutmix_alpha > 0 and (mixup_alpha <= 0 or float(rng.random()) < switch_prob)
+    alpha = cutmix_alpha if use_cutmix else mixup_alpha
+    lam = min(1.0, max(0.0, float(rng.beta(alpha, alpha))))
+    if not use_cutmix:
+        return capi.MixDesc(capi.MIX_MIXUP, lam, pair_rule, pair_shift, 0, 0, 0, 0)
+    ratio = float(np.sqrt(1.0 - lam))
+    cut_h, cut_w = int(H * ratio), int(W * ratio)
+    cy, cx = int(rng.integers(0, H)), int(rng.integers(0, W))
+    y0, y1 = min(max(cy - cut_h // 2, 0), H), min(max(cy + cut_h // 2, 0), H)
+    x0, x1 = min(max(cx - cut_w // 2, 0), W), min(max(cx + cut_w // 2, 0), W)
+    return capi.MixDesc(capi.MIX_CUTMIX, capi.cutmix_lambda(H, W, y0, y1, x0, x1), pair_rule, pair_shift, y0, y1, x0, x1)
 
 
 class HostNet:
@@ -378,6 +402,34 @@ class HostNet:
 
     def last_loss(self):
         return float(self.lib.cnnh_net_last_loss(self.h))
+
+    def set_label_smoothing(self, eps):
+        """Sequential::set_label_smoothing: every later train_step / forward_backward trains against smoothed target rows built on the
+        device (cnn_soft_targets) through the soft loss head; 0 (the default) is the hard-label step, launch for launch"""
+        if not 0.0 <= float(eps) < 1.0:
+            raise capi.CnnAmdError(f"set_label_smoothing({eps}): eps in [0, 1)")
+        self.lib.cnnh_net_set_label_smoothing(self.h, float(eps))
+
+    def train_step_mixed(self, x_dev, labels_dev, lr, mix):
+        """Sequential::train_step_mixed: cnn_batch_mix of the batch (mix: a capi.MixDesc, e.g. from mix_params) into container-owned
+        storage, the mixed and smoothed targets, then the ordinary step on the mixed batch; x_dev is not written"""
+        B, _, H, W = x_dev.shape
+        self._mix = mix  # (kept alive across the call)
+        self.lib.cnnh_net_train_step_mixed(self.h, C.c_void_p(x_dev.data_ptr()), C.c_void_p(labels_dev.data_ptr()), B, H, W, C.byref(mix), float(lr))
+
+    def train_step_soft(self, x_dev, targets_dev, lr):
+        """Sequential::train_step_soft: one step against caller-provided dense targets, float32 [B][classes] on the device"""
+        B, _, H, W = x_dev.shape
+        assert tuple(targets_dev.shape) == (B, self.classes) and targets_dev.is_contiguous()
+        self._targets = targets_dev  # (read by the head kernel: kept alive until the next step)
+        self.lib.cnnh_net_train_step_soft(self.h, C.c_void_p(x_dev.data_ptr()), C.c_void_p(targets_dev.data_ptr()), B, H, W, float(lr))
+
+    def last_targets(self, B):
+        """the [B][classes] target rows of the last soft step, on the host; synchronises"""
+        out = np.empty((B, self.classes), np.float32)
+        if self.lib.cnnh_net_get_targets(self.h, _fp(out), int(B)) != 0:
+            raise capi.CnnAmdError("last_targets before the first step against soft targets")
+        return out
 
     def input_delta(self, shape):
         """the delta with respect to the network input of the last backward pass (the first layer's data gradient)"""

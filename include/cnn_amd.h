@@ -644,6 +644,65 @@ int cnn_linear_forward_softmax_xent_dx(const float* x, const float* w, const flo
                                        void* stream);
 int cnn_loss_from_terms(const float* loss_terms, float* loss_sum, int B, void* stream);
 
+/* ---- soft targets: label smoothing, mixup and CutMix on the device --------------------------------------------------------------
+ * The partner rule shared by cnn_soft_targets and cnn_batch_mix: which sample p(b) of the same batch sample b is mixed with.  It takes no
+ * index array, so the host checks it:
+ *     CNN_PAIR_NONE :  no partner
+ *     CNN_PAIR_FLIP :  p(b) = B - 1 - b            (timm; pair_shift is ignored; the middle sample of an odd batch is its own partner and
+ *                                                   goes through the same arithmetic as any other)
+ *     CNN_PAIR_ROLL :  p(b) = (b + shift) % B      with 1 <= shift < B (torchvision: shift 1) */
+enum { CNN_PAIR_NONE = 0, CNN_PAIR_FLIP = 1, CNN_PAIR_ROLL = 2 };
+
+/* Dense target rows from labels: targets[B][classes] for the soft loss entries below.  fp32, every operation rounded separately, no FMA.
+ * Host scalars of the call:   u = smoothing / (float)classes     hot = (1.f - smoothing) + u     oml = 1.f - lam
+ *     base(l, j) = smoothing == 0 ? (j == l ? 1.f : 0.f) : (j == l ? hot : u)
+ *     pair_rule == CNN_PAIR_NONE or lam == 1 :  targets[b][j] = base(labels[b], j)
+ *     otherwise                              :  targets[b][j] = lam * base(labels[b], j) + oml * base(labels[p(b)], j)
+ *                                                                two products and one sum
+ * A label outside [0, classes) matches no j, as in the hard-label kernels; the labels are device memory and are not checked.  Checked
+ * before the launch: no null pointer, B > 0, classes > 0, smoothing in [0, 1) and lam in [0, 1] (a NaN fails either), a known rule, a
+ * ROLL shift in [1, B).  One small launch (its name begins with soft_targets). */
+int cnn_soft_targets(const int32_t* labels, float* targets /* [B][classes] */, int B, int classes, float smoothing, float lam,
+                     int pair_rule, int pair_shift, void* stream);
+
+/* mixup / CutMix of a contiguous NCHW batch with its partner samples, OUT OF PLACE: dst and src must not overlap (checked; a partner
+ * read beside an in-place write would be a race), src is not written.  One launch (its name begins with bmix_).
+ *     CNN_MIX_MIXUP  :  dst[b][e] = lam * src[b][e] + oml * src[p(b)][e]        oml = 1.f - lam on the host; fp32, two products and one
+ *                                                                               sum, each rounded, no FMA, denormals kept; 12 bytes per
+ *                                                                               element
+ *     CNN_MIX_CUTMIX :  dst[b][c][y][x] = (y0 <= y < y1 && x0 <= x < x1) ? src[p(b)][c][y][x] : src[b][c][y][x]
+ *                                                                               a copy of the bits, lam is ignored (cnn_cutmix_lambda gives
+ *                                                                               the box's); 16-byte groups wholly inside or outside the box
+ *                                                                               request one source only: towards 8 bytes per element
+ * pair_rule == CNN_PAIR_NONE, MIXUP with lam == 1 and CUTMIX with an empty box are the copy of the bits (as cnn_ema_update at decay 0):
+ * -0.0, infinities, NaN payloads and denormals come out as they went in.  Any pointer alignment and any sample size: the float4 kernels
+ * run when both pointers are 16-byte aligned and C*H*W % 4 == 0 (every sample, hence every partner, then starts aligned), the scalar
+ * kernels otherwise, same results.  Checked before the launch: no null pointer, B, C, H, W > 0, C*H*W < 2^31, a known mode and rule, a ROLL
+ * shift in [1, B), MIXUP: lam in [0, 1] (a NaN fails), CUTMIX: 0 <= y0 <= y1 <= H and 0 <= x0 <= x1 <= W (an empty box is a copy). */
+enum { CNN_MIX_MIXUP = 1, CNN_MIX_CUTMIX = 2 };
+typedef struct cnn_mix_desc {
+    int mode;                  /* CNN_MIX_MIXUP | CNN_MIX_CUTMIX */
+    float lam;                 /* MIXUP: weight of the sample itself */
+    int pair_rule, pair_shift; /* CNN_PAIR_* */
+    int y0, y1, x0, x1;        /* CUTMIX: the box [y0, y1) x [x0, x1) of every plane that comes from the partner */
+} cnn_mix_desc;
+int cnn_batch_mix(const cnn_mix_desc* d, const float* src, float* dst, int B, int C, int H, int W, void* stream);
+/* the weight of the sample itself under a CutMix box: (float)(1.0 - (double)((y1 - y0) * (x1 - x0)) / ((double)H * W)) -- pure host code */
+float cnn_cutmix_lambda(int H, int W, int y0, int y1, int x0, int x1);
+
+/* cnn_softmax_xent, cnn_linear_forward_softmax_xent and cnn_linear_forward_softmax_xent_dx against a dense target tensor
+ * targets[B][classes] (fp32, e.g. from cnn_soft_targets) instead of labels: yv = targets[b][i] takes the place of (i == label ? 1 : 0)
+ * and nothing else changes -- delta[b][i] = probs[b][i] - yv, the sample's loss term is sum_i logf(probs[b][i]) * yv in ascending i
+ * (the reference's log(0) * 0 = NaN included), same kernels, same order.  A one-hot target tensor therefore reproduces the hard-label
+ * entry bit for bit in logits, probs, delta, loss terms and dx. */
+int cnn_softmax_xent_soft(const float* logits, const float* targets, float* probs, float* delta, float* loss_sum, int B, int classes,
+                          void* stream);
+int cnn_linear_forward_softmax_xent_soft(const float* x, const float* w, const float* bias, const float* targets, float* logits,
+                                         float* probs, float* delta, float* loss_terms, int B, int in, int out, void* stream);
+int cnn_linear_forward_softmax_xent_soft_dx(const float* x, const float* w, const float* bias, const float* targets, float* logits,
+                                            float* probs, float* delta, float* loss_terms, float* dx, int relu_below, int B, int in,
+                                            int out, void* stream);
+
 /* ---- device memory / transfer helpers (the host layer classes use only these) ------------------------ */
 int cnn_device_alloc(void** ptr, size_t bytes);
 int cnn_device_free(void* ptr);
