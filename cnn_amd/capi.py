@@ -33,6 +33,12 @@ class MixDesc(C.Structure):
                 ("x0", C.c_int), ("x1", C.c_int)]
 
 
+class EvalResult(C.Structure):
+    """mirror of cnn_eval_result: the head of the evaluation state block"""
+
+    _fields_ = [("samples", C.c_uint64), ("top1", C.c_uint64), ("topk", C.c_uint64), ("ignored", C.c_uint64), ("loss_sum", C.c_double)]
+
+
 PAIR_NONE, PAIR_FLIP, PAIR_ROLL = 0, 1, 2  # CNN_PAIR_*
 MIX_MIXUP, MIX_CUTMIX = 1, 2  # CNN_MIX_*
 
@@ -211,6 +217,9 @@ SIGNATURES = {
     "cnn_softmax_xent_soft": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, _P]),
     "cnn_linear_forward_softmax_xent_soft": (C.c_int, [_P] * 8 + [C.c_int] * 3 + [_P]),
     "cnn_linear_forward_softmax_xent_soft_dx": (C.c_int, [_P] * 9 + [C.c_int] * 4 + [_P]),
+    "cnn_eval_state_bytes": (C.c_size_t, [C.c_int]),
+    "cnn_eval_accumulate": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "cnn_eval_read": (C.c_int, [_P, C.c_int, C.POINTER(EvalResult), _P, _P]),
     "cnn_conv2d_backward_weight_side": (C.c_int, [_D, _P, _P, _P, _P, C.c_float, _P, C.c_size_t, _P]),
     "cnn_device_alloc": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t]),
     "cnn_device_free": (C.c_int, [_P]),
@@ -922,6 +931,39 @@ def softmax_xent_soft(logits, targets, want_probs=True):
     loss = torch.empty((1,), dtype=torch.float32, device=logits.device)
     check(load().cnn_softmax_xent_soft(_ptr(logits), _ptr(targets), _ptr(probs), _ptr(delta), _ptr(loss), B, n, _stream()), "cnn_softmax_xent_soft")
     return probs, delta, loss
+
+
+def eval_state_bytes(classes):
+    """cnn_eval_state_bytes: the size of the evaluation state block of `classes` classes (host only)"""
+    n = int(load().cnn_eval_state_bytes(int(classes)))
+    if n == 0:
+        raise CnnAmdError("cnn_eval_state_bytes: " + load().cnn_amd_last_error().decode())
+    return n
+
+
+def eval_accumulate(logits, labels, state, k=1, pred=None):
+    """cnn_eval_accumulate: one batch of float32 [B][classes] logits and int32 [B] labels (device) into the state block -- loss, top-1 /
+    top-k and confusion counts, one launch, no read-back; pred: optional int32 [B] device tensor that receives the predictions"""
+    _need_gpu(logits, labels, state, pred)
+    B, n = logits.shape
+    check(load().cnn_eval_accumulate(_ptr(logits), _ptr(labels), _ptr(pred), _ptr(state), B, n, int(k), _stream()), "cnn_eval_accumulate")
+    return pred
+
+
+def eval_read(state, classes, want_confusion=True):
+    """cnn_eval_read: the one call that copies the state back (synchronises) -> dict of samples, top1, topk, ignored, loss_sum and, with
+    want_confusion, confusion (numpy uint64 [classes][classes], row = label, column = prediction)"""
+    import numpy as np
+
+    _need_gpu(state)
+    res = EvalResult()
+    conf = np.zeros((classes, classes), dtype=np.uint64) if want_confusion else None
+    check(load().cnn_eval_read(_ptr(state), int(classes), C.byref(res), conf.ctypes.data_as(C.c_void_p) if want_confusion else None, _stream()),
+          "cnn_eval_read")
+    out = {"samples": int(res.samples), "top1": int(res.top1), "topk": int(res.topk), "ignored": int(res.ignored), "loss_sum": float(res.loss_sum)}
+    if want_confusion:
+        out["confusion"] = conf
+    return out
 
 
 def soft_targets(labels, classes, smoothing=0.0, lam=1.0, pair_rule=PAIR_NONE, pair_shift=0, out=None):

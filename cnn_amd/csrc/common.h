@@ -4,6 +4,7 @@
 #include <hip/hip_ext.h>
 
 #include <atomic>
+#include <cfloat>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -401,6 +402,14 @@ __device__ __forceinline__ float lars_one(float p, float g, float& v, float rati
     }
     const float step = lr * u;
     return p - step;
+}
+
+// the reference's exp of a softmax row (func.cpp:6-12): shared by softmax_xent_kernel (elementwise.hip) and eval_accumulate
+// (metrics.hip), whose loss terms must have the same bits
+__device__ __forceinline__ float clamped_exp(float v) {
+    if (v >= 88.f) return FLT_MAX;
+    if (v <= -50.f) return 0.f;
+    return expf(v);
 }
 
 constexpr int kWave = 64;         // CDNA wavefront

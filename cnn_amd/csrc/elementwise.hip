@@ -441,13 +441,6 @@ __global__ __launch_bounds__(kBlock) void clip_scale(float* __restrict__ g, size
     stream_walk<kVec>(op, 0, n);
 }
 
-// func.cpp:6-12
-__device__ __forceinline__ float clamped_exp(float v) {
-    if (v >= 88.f) return FLT_MAX;
-    if (v <= -50.f) return 0.f;
-    return expf(v);
-}
-
 // One workgroup; thread t owns samples t, t+256, ...  Per-sample arithmetic is the reference's sequential
 // loop (func.cpp:22-33, 63-68); the loss terms are then added in ascending sample order by one lane so the
 // fp32 loss sum has the reference's order (func.cpp:60-71).

@@ -444,6 +444,14 @@ public:
     std::vector<tensor> backward(std::vector<tensor>& delta) override;
 };
 
+// what Sequential::eval_result returns: cnn_eval_result's totals and the two figures a caller derives from them
+struct EvalResult {
+    uint64_t samples = 0, top1 = 0, topk = 0, ignored = 0;
+    double loss_sum = 0;
+    double mean_loss() const { return loss_sum / (double)samples; }
+    double accuracy() const { return (double)top1 / (double)samples; }
+};
+
 // The reference's model container is a strictly sequential std::list<std::shared_ptr<Layer>> (architectures.h:200) that
 // forward walks front to back (alexnet.cpp:41-42), backward back to front (:53-55), update / save / load front to back
 // (:63-64, :73-74, :86-87).  Sequential is that container for ANY layer list (the reference hard-wires one list in
@@ -459,7 +467,8 @@ public:
 //   * clipping by the global gradient norm (set_grad_clip) in front of whichever step is active;
 //   * gradient accumulation over micro-batches (set_grad_accumulation): k container steps, one optimizer step on their summed gradients;
 //   * an exponential moving average of the parameters (set_ema) behind every optimizer step, swapped into the arena for evaluation
-//     and export (swap_ema), with a state file of its own (save_ema_state / load_ema_state).
+//     and export (swap_ema), with a state file of its own (save_ema_state / load_ema_state);
+//   * evaluation on the device (eval_begin / eval_step / eval_result): loss, top-1 / top-k and confusion counts, one read-back at the end.
 class Sequential {
 public:
     bool print_info = false;
@@ -812,6 +821,27 @@ public:
     void train_step_soft(const std::vector<tensor>& input, const data_type* targets_dev, const data_type learning_rate);
     // the target rows of the last step that trained against soft targets ([B][classes], device); null before the first one
     const data_type* last_targets_device() const { return last_targets; }
+    // Evaluation that never leaves the device (the reference's ClassificationEvaluator loop: forward, argmax, compare, on the host per
+    // batch).  eval_begin / eval_step ... / eval_result; the arithmetic is cnn_eval_accumulate's (include/cnn_amd.h).
+    // eval_begin(top_k): the class count is the last LinearLayer's out_features(); the first call allocates the state block
+    // (cnn_eval_state_bytes), every call clears it (one cnn_memset_zero on architectures::stream) and sets k for the top-k count.
+    // top_k outside [1, classes] is reported and aborts, as in the other setters.
+    void eval_begin(int top_k = 1);
+    // One batch: forward() with no_grad and lazy_host_sync set (both restored on every path), then ONE cnn_eval_accumulate on the
+    // logits, on architectures::stream.  No D2H copy, no synchronise: it never blocks.  labels_dev: int32 [B] on the device; a label
+    // outside [0, classes) -- the -1 of a padded last batch -- is counted as ignored and nowhere else.  Under no_grad BatchNorm2D uses
+    // its moving statistics and Dropout scales.  It evaluates whatever the arena holds: after swap_ema() that is the average, and it
+    // does not swap back.  On layer outputs it has exactly forward()'s effects and nothing else: parameters, gradients, the
+    // accumulator and its phase, optimizer state, the step counter, the shadow and the moving statistics are untouched (like every
+    // forward() it first orders a data gradient the last train_step deferred).  The [batch] prediction buffer is allocated by the
+    // first step and grows with a larger batch.  Aborts with a message when eval_begin was never called.  Under set_comm every
+    // replica counts ITS shard and nothing is exchanged: the caller adds the integers (and the loss sums) of the replicas.
+    void eval_step(const std::vector<tensor>& input, const int* labels_dev);
+    // the totals since eval_begin; like last_loss() it synchronises (cnn_eval_read).  confusion (optional) receives classes * classes
+    // counts, row = label, column = prediction.
+    EvalResult eval_result(std::vector<uint64_t>* confusion = nullptr);
+    // int32 [B] predictions of the last eval_step (device); null before the first one
+    const int* last_predictions_device() const { return eval_pred; }
     // TEST SUPPORT (tests/test_gpu_optimizer.py's host-stepped reference net; no product path calls it): train_step without its SGD
     // step, as the plain sequence (forward(), the loss kernel, backward(): no fused loss head, no fused step tail) -- the gradients of the
     // batch are left in the arena, last_loss() works.
@@ -844,6 +874,10 @@ private:
     data_type* loss_sum = nullptr;        // ... or the ordered sum (unfused head); [1]
     bool loss_in_terms = false;
     int loss_batch = 0, loss_last_B = 0;
+    // ---- evaluation on the device (eval_begin / eval_step / eval_result) ----
+    void* eval_state = nullptr;   // cnn_eval_state_bytes(eval_classes) bytes, allocated by the first eval_begin
+    int* eval_pred = nullptr;     // [eval_batch] predictions of the last eval_step
+    int eval_classes = 0, eval_k = 1, eval_batch = 0;
 };
 
 // The reference's fixed network (alexnet.cpp:10-33).  forward / backward / update_gradients / save_weights / load_weights are

@@ -334,6 +334,33 @@ int cnnh_net_get_targets(void* hv, float* host, int B) {
     return 0;
 }
 float cnnh_net_last_loss(void* hv) { return ((Handle*)hv)->net->last_loss(); }
+// Sequential::eval_begin / eval_step / eval_result / last_predictions_device: evaluation on the device (architectures.h).
+// cnnh_net_eval_step_device takes device pointers like cnnh_net_train_step_device_loss and never blocks; cnnh_net_eval_result is the one
+// read-back -- out: cnn_eval_result, confusion (nullable): classes * classes counts; cnnh_net_get_predictions copies the [B] predictions of
+// the last step to the host: 1 before the first one.
+void cnnh_net_eval_begin(void* hv, int top_k) { ((Handle*)hv)->net->eval_begin(top_k); }
+void cnnh_net_eval_step_device(void* hv, float* x_dev, const int* labels_dev, int B, int H, int W) {
+    Handle* h = (Handle*)hv;
+    h->net->eval_step(device_views(h, x_dev, B, H, W), labels_dev);
+}
+void cnnh_net_eval_result(void* hv, cnn_eval_result* out, uint64_t* confusion) {
+    Handle* h = (Handle*)hv;
+    std::vector<uint64_t> conf;
+    const EvalResult r = h->net->eval_result(confusion ? &conf : nullptr);
+    out->samples = r.samples;
+    out->top1 = r.top1;
+    out->topk = r.topk;
+    out->ignored = r.ignored;
+    out->loss_sum = r.loss_sum;
+    if (confusion) std::memcpy(confusion, conf.data(), sizeof(uint64_t) * conf.size());
+}
+int cnnh_net_get_predictions(void* hv, int* host, int B) {
+    Handle* h = (Handle*)hv;
+    if (h->net->last_predictions_device() == nullptr) return 1;
+    must(cnn_memcpy_d2h(host, h->net->last_predictions_device(), sizeof(int) * (size_t)B, stream), "cnn_memcpy_d2h");
+    must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
+    return 0;
+}
 // the delta with respect to the network INPUT (the first layer's data gradient, conv2d.cpp:168-199; alexnet.cpp:55 discards it) of
 // the last backward pass -- after flush_deferred(), because train_step may have deferred that kernel.  0 ok, 1 no such tensor, 2 cap
 int cnnh_net_input_delta(void* hv, float* out, size_t cap_floats) {

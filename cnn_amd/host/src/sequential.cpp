@@ -200,6 +200,8 @@ Sequential::~Sequential() {
     if (loss_terms) cnn_device_free(loss_terms);
     if (target_rows) cnn_device_free(target_rows);
     if (loss_sum) cnn_device_free(loss_sum);
+    if (eval_state) cnn_device_free(eval_state);
+    if (eval_pred) cnn_device_free(eval_pred);
     if (bn_comm) cnn_comm_destroy(bn_comm);
     if (comm_stream) cnn_stream_destroy(comm_stream);
     if (ev_grads) cnn_event_destroy(ev_grads);
@@ -800,6 +802,67 @@ data_type Sequential::last_loss() {
     must(cnn_memcpy_d2h(&host, loss_sum, sizeof(data_type), stream), "cnn_memcpy_d2h");
     must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
     return host / (data_type)loss_last_B;
+}
+
+// ---- evaluation on the device -----------------------------------------------------------------------------------------------
+void Sequential::eval_begin(const int top_k) {
+    const int classes = loss_head_of(layers_sequence)->out_features();
+    if (top_k < 1 || top_k > classes) {
+        std::fprintf(stderr, "cnn_amd host: eval_begin: top_k=%d outside [1, classes=%d]\n", top_k, classes);
+        std::abort();
+    }
+    if (eval_state == nullptr) {
+        eval_state = dev_alloc(cnn_eval_state_bytes(classes));
+        eval_classes = classes;
+    }
+    eval_k = top_k;
+    must(cnn_memset_zero(eval_state, cnn_eval_state_bytes(eval_classes), stream), "cnn_memset_zero");
+}
+
+void Sequential::eval_step(const std::vector<tensor>& input, const int* labels_dev) {
+    assert(!input.empty() && labels_dev != nullptr);
+    if (eval_state == nullptr) {
+        std::fprintf(stderr, "cnn_amd host: eval_step before eval_begin\n");
+        std::abort();
+    }
+    const int B = (int)input.size();
+    if (eval_batch < B) {  // (an earlier step's kernel may still write the buffer that goes)
+        if (eval_pred != nullptr) {
+            must(cnn_stream_synchronize(stream), "cnn_stream_synchronize");
+            must(cnn_device_free(eval_pred), "cnn_device_free");
+        }
+        eval_pred = (int*)dev_alloc(sizeof(int) * (size_t)B);
+        eval_batch = B;
+    }
+    struct Flags {  // no_grad and lazy_host_sync as the caller had them, on every path out
+        const bool grad = no_grad, lazy = lazy_host_sync;
+        ~Flags() {
+            no_grad = grad;
+            lazy_host_sync = lazy;
+        }
+    } restore;
+    no_grad = true;
+    lazy_host_sync = true;
+    const std::vector<tensor> output = forward(input);
+    const data_type* logits = batch_device_pointer(output, logits_stage, "logits");
+    must(cnn_eval_accumulate(logits, labels_dev, eval_pred, eval_state, B, eval_classes, eval_k, stream), "cnn_eval_accumulate");
+}
+
+EvalResult Sequential::eval_result(std::vector<uint64_t>* confusion) {
+    if (eval_state == nullptr) {
+        std::fprintf(stderr, "cnn_amd host: eval_result before eval_begin\n");
+        std::abort();
+    }
+    if (confusion != nullptr) confusion->assign((size_t)eval_classes * eval_classes, 0);
+    cnn_eval_result r;
+    must(cnn_eval_read(eval_state, eval_classes, &r, confusion != nullptr ? confusion->data() : nullptr, stream), "cnn_eval_read");
+    EvalResult out;
+    out.samples = r.samples;
+    out.top1 = r.top1;
+    out.topk = r.topk;
+    out.ignored = r.ignored;
+    out.loss_sum = r.loss_sum;
+    return out;
 }
 
 void Sequential::save_weights(const std::filesystem::path& save_path) const {

@@ -83,6 +83,10 @@ SIGNATURES = {
     "cnnh_net_train_step_mixed": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(capi.MixDesc), C.c_float]),
     "cnnh_net_train_step_soft": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float]),
     "cnnh_net_get_targets": (C.c_int, [C.c_void_p, _F, C.c_int]),
+    "cnnh_net_eval_begin": (None, [C.c_void_p, C.c_int]),
+    "cnnh_net_eval_step_device": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "cnnh_net_eval_result": (None, [C.c_void_p, C.POINTER(capi.EvalResult), C.c_void_p]),
+    "cnnh_net_get_predictions": (C.c_int, [C.c_void_p, _I, C.c_int]),
     "cnnh_net_flush": (None, [C.c_void_p]),
     "cnnh_net_input_delta": (C.c_int, [C.c_void_p, _F, C.c_size_t]),
     "cnnh_net_layer_output": (C.c_int, [C.c_void_p, C.c_char_p, _F, C.c_size_t]),
@@ -430,6 +434,52 @@ class HostNet:
         if self.lib.cnnh_net_get_targets(self.h, _fp(out), int(B)) != 0:
             raise capi.CnnAmdError("last_targets before the first step against soft targets")
         return out
+
+    def eval_begin(self, top_k=1):
+        """Sequential::eval_begin: an empty evaluation state on the device (allocated by the first call); top_k in [1, classes]"""
+        if not 1 <= int(top_k) <= self.classes:
+            raise capi.CnnAmdError(f"eval_begin({top_k}): top_k in [1, {self.classes}]")
+        self.lib.cnnh_net_eval_begin(self.h, int(top_k))
+        self._eval_begun = True
+
+    def eval_step(self, x_dev, labels_dev):
+        """Sequential::eval_step: the no-grad forward pass and ONE cnn_eval_accumulate on its logits -- loss, top-1 / top-k and confusion
+        counts stay on the device, nothing is read back and the host never blocks.  x_dev float32 [B][C][H][W], labels_dev int32 [B],
+        both device tensors; a label outside [0, classes), e.g. the -1 of a padded last batch, is counted as ignored only."""
+        if not getattr(self, "_eval_begun", False):
+            raise capi.CnnAmdError("eval_step before eval_begin")
+        B, _, H, W = x_dev.shape
+        self._eval_B = B
+        self.lib.cnnh_net_eval_step_device(self.h, C.c_void_p(x_dev.data_ptr()), C.c_void_p(labels_dev.data_ptr()), B, H, W)
+
+    def eval_result(self):
+        """Sequential::eval_result: the totals since eval_begin -- the one read-back, synchronises.  A dict of samples, top1, topk,
+        ignored, loss_sum, mean_loss, accuracy (NaN without samples) and confusion (numpy uint64 [classes][classes], row = label,
+        column = prediction)"""
+        if not getattr(self, "_eval_begun", False):
+            raise capi.CnnAmdError("eval_result before eval_begin")
+        res = capi.EvalResult()
+        conf = np.zeros((self.classes, self.classes), np.uint64)
+        self.lib.cnnh_net_eval_result(self.h, C.byref(res), conf.ctypes.data_as(C.c_void_p))
+        n = int(res.samples)
+        return {"samples": n, "top1": int(res.top1), "topk": int(res.topk), "ignored": int(res.ignored), "loss_sum": float(res.loss_sum),
+                "mean_loss": float(res.loss_sum) / n if n else float("nan"), "accuracy": int(res.top1) / n if n else float("nan"),
+                "confusion": conf}
+
+    def predictions(self):
+        """the int32 predictions of the last eval_step, on the host; synchronises"""
+        B = getattr(self, "_eval_B", 0)
+        out = np.empty(B, np.int32)
+        if B == 0 or self.lib.cnnh_net_get_predictions(self.h, out.ctypes.data_as(_I), B) != 0:
+            raise capi.CnnAmdError("predictions before the first eval_step")
+        return out
+
+    def evaluate(self, batches, top_k=1):
+        """eval_begin, one eval_step per (x_dev, labels_dev) of the iterable, eval_result"""
+        self.eval_begin(top_k)
+        for x_dev, labels_dev in batches:
+            self.eval_step(x_dev, labels_dev)
+        return self.eval_result()
 
     def input_delta(self, shape):
         """the delta with respect to the network input of the last backward pass (the first layer's data gradient)"""

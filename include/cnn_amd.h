@@ -703,6 +703,41 @@ int cnn_linear_forward_softmax_xent_soft_dx(const float* x, const float* w, cons
                                             float* probs, float* delta, float* loss_terms, float* dx, int relu_below, int B, int in,
                                             int out, void* stream);
 
+/* ---- evaluation on the device: loss, top-1 / top-k and confusion counts without a host round trip per batch ----------------------
+ * The evaluation state is ONE device block whose all-zero bytes are the empty state (clear it with cnn_memset_zero); its layout, 8-byte
+ * words throughout, cnn_eval_state_bytes(classes) = 8 * (4 + 1 + classes * classes) bytes:
+ *     uint64 counts[4]                     samples, top-1 correct, top-k correct, ignored
+ *     double loss_sum                      running sum of the batch loss sums
+ *     uint64 confusion[classes][classes]   row = label, column = prediction
+ * cnn_eval_accumulate adds one batch of logits [B][classes] to it in ONE launch (its name begins with eval_).  Per sample b with logits z
+ * and label y:
+ *     prediction : the first maximum, strict '>' starting at index 0 (Tensor3D::argmax, the max loop of cnn_softmax_xent); written to
+ *                  pred[b] when pred is given, for ignored samples too.  A NaN is never greater: a NaN at index 0 stays the prediction,
+ *                  a NaN elsewhere is never one.
+ *     ignored    : a label outside [0, classes) counts in `ignored` ONLY -- nothing in samples, top-1, top-k, confusion or the loss (a
+ *                  padded last batch: label -1).
+ *     top-1      : pred == y.            confusion[y][pred] += 1.
+ *     top-k      : rank < k with rank = #{j : z[j] > z[y]} + #{j < y : z[j] == z[y]} (ties go to the lower index, as in the
+ *                  prediction: on rows without NaN rank == 0 is the same as pred == y).
+ *     loss term  : logf(p[y]) with exactly cnn_softmax_xent's per-sample expressions in its order -- sequential max, sequential sum of the
+ *                  clamped exp of z[i] - max, p = clamped_exp(z[y] - max) / sum, NaN -> 0.
+ *     batch sum  : the terms of the non-ignored samples added in ascending sample order in fp32, negated: with no label out of range
+ *                  it has the bits of cnn_softmax_xent's loss_sum[0] (while no probability of the row underflows to 0, where that entry's
+ *                  log(0) * 0 gives NaN and this one does not).
+ *     running    : loss_sum += (double)batch_sum, once per launch.
+ * The counts are integer adds.  Nothing depends on a launch shape: the same calls give the same bytes.  The labels are device memory and
+ * are not checked on the host.  Checked before the launch: no null pointer except pred, B > 0, classes > 0, 1 <= k <= classes.
+ * cnn_eval_read is the one call that copies back and synchronises: counts and loss into *out, the confusion matrix into `confusion`
+ * (host, classes * classes values) when it is given.  mean loss = loss_sum / samples, accuracy = top1 / samples. */
+typedef struct cnn_eval_result {
+    uint64_t samples, top1, topk, ignored;
+    double loss_sum;
+} cnn_eval_result;
+size_t cnn_eval_state_bytes(int classes); /* pure host code; 0 and a message for classes <= 0 */
+int cnn_eval_accumulate(const float* logits, const int32_t* labels, int32_t* pred /* [B], nullable */, void* state, int B, int classes, int k,
+                        void* stream);
+int cnn_eval_read(const void* state, int classes, cnn_eval_result* out, uint64_t* confusion /* nullable, host */, void* stream);
+
 /* ---- device memory / transfer helpers (the host layer classes use only these) ------------------------ */
 int cnn_device_alloc(void** ptr, size_t bytes);
 int cnn_device_free(void* ptr);
