@@ -39,6 +39,14 @@ class EvalResult(C.Structure):
     _fields_ = [("samples", C.c_uint64), ("top1", C.c_uint64), ("topk", C.c_uint64), ("ignored", C.c_uint64), ("loss_sum", C.c_double)]
 
 
+class AugmentOp(C.Structure):
+    """mirror of cnn_augment_op"""
+
+    _fields_ = [("kind", C.c_int), ("a", C.c_float), ("b", C.c_float), ("c", C.c_float), ("d", C.c_float)]
+
+
+AUG_HFLIP, AUG_VFLIP, AUG_CROP, AUG_ROTATE = 1, 2, 3, 4  # CNN_AUG_*
+
 PAIR_NONE, PAIR_FLIP, PAIR_ROLL = 0, 1, 2  # CNN_PAIR_*
 MIX_MIXUP, MIX_CUTMIX = 1, 2  # CNN_MIX_*
 
@@ -156,6 +164,11 @@ SIGNATURES = {
     "cnn_batch_stager_submit": (C.c_int, [_P, C.c_int, C.POINTER(C.c_void_p)]),
     "cnn_batch_stager_wait": (C.c_int, [_P, C.c_int, _P]),
     "cnn_batch_stager_release": (C.c_int, [_P, C.c_int, _P]),
+    "cnn_augment_u8": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_float, _P, C.c_int, C.c_int, _P]),
+    "cnn_augment_matrix": (C.c_int, [C.POINTER(AugmentOp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "cnn_batch_stager_create_u8_aug": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "cnn_batch_stager_matrices": (C.c_int, [_P, C.c_int, C.POINTER(C.POINTER(C.c_float))]),
+    "cnn_batch_stager_set_fill": (C.c_int, [_P, C.c_float]),
     "cnn_linear_forward": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "cnn_linear_backward": (C.c_int, [_P] * 6 + [C.c_int] * 3 + [C.c_float, _P]),
     "cnn_linear_backward_relu": (C.c_int, [_P] * 6 + [C.c_int] * 3 + [C.c_float, _P]),
@@ -997,6 +1010,33 @@ def batch_mix(mix, src, dst=None):
     return dst
 
 
+def augment_matrix(ops, Hs, Ws, H, W):
+    """cnn_augment_matrix (host only): ops, a sequence of AugmentOp or (kind, a, b, c, d) tuples (trailing values may be left out),
+    applied in order to the Hs x Ws source, then the resize to H x W -> the six float32 of the output -> source map"""
+    import numpy as np
+
+    arr = (AugmentOp * max(len(ops), 1))()
+    for i, op in enumerate(ops):
+        arr[i] = op if isinstance(op, AugmentOp) else AugmentOp(int(op[0]), *[float(v) for v in op[1:]])
+    m = np.empty(6, dtype=np.float32)
+    check(load().cnn_augment_matrix(arr, len(ops), int(Hs), int(Ws), int(H), int(W), m.ctypes.data_as(C.POINTER(C.c_float))), "cnn_augment_matrix")
+    return m
+
+
+def augment_u8(src_u8, matrices, H, W, fill=0.0, out=None):
+    """cnn_augment_u8: uint8 [B][Hs][Ws][3] and float32 [B][6] device tensors -> the float32 [B][3][H][W] batch, one launch"""
+    import torch
+
+    _need_gpu(src_u8, matrices, out)
+    B, Hs, Ws, ch = src_u8.shape
+    if ch != 3 or src_u8.dtype != torch.uint8 or matrices.dtype != torch.float32 or tuple(matrices.shape) != (B, 6):
+        raise CnnAmdError("augment_u8: src must be uint8 [B][Hs][Ws][3] and matrices float32 [B][6]")
+    if out is None:
+        out = torch.empty((B, 3, int(H), int(W)), dtype=torch.float32, device=src_u8.device)
+    check(load().cnn_augment_u8(_ptr(src_u8), B, Hs, Ws, _ptr(matrices), float(fill), _ptr(out), int(H), int(W), _stream()), "cnn_augment_u8")
+    return out
+
+
 def set_option(name, value):
     """one of the measurement switches of DESIGN.md section 10 (name with or without the CNN_AMD_ prefix); value None removes it.
     The library reads the CNN_AMD_* environment once, at first use: later changes go through here."""
@@ -1093,19 +1133,41 @@ def side_stream_join():
 class BatchStager:
     """cnn_batch_stager_*: `depth` pinned host slots + device buffers, uploads on a copy stream of its own, ordered by events"""
 
-    def __init__(self, batch_bytes=None, depth=2, u8_shape=None):
+    def __init__(self, batch_bytes=None, depth=2, u8_shape=None, source_shape=None, augment=False):
         """u8_shape=(B, H, W): the slots hold interleaved BYTES [B][H][W][3] (cv::Mat CV_8UC3), submit() returns the fp32 planar batch
-        the stager's conversion kernel writes (cnn_batch_stager_create_u8)"""
+        the stager's conversion kernel writes (cnn_batch_stager_create_u8).  augment=True or source_shape=(Hs, Ws): the slots hold
+        [B][Hs][Ws][3] bytes (Hs, Ws = H, W when source_shape is None) and per-sample maps, matrices(slot); submit() returns the
+        [B][3][H][W] batch cnn_augment_u8 writes through them (cnn_batch_stager_create_u8_aug)"""
         self.lib = load()
         self.h = C.c_void_p()
         self.u8 = u8_shape is not None
-        if self.u8:
+        self.aug = bool(augment) or source_shape is not None
+        if self.aug and not self.u8:
+            raise CnnAmdError("BatchStager: augment / source_shape need u8_shape=(B, H, W)")
+        if self.aug:
+            B, H, W = (int(v) for v in u8_shape)
+            Hs, Ws = (H, W) if source_shape is None else (int(v) for v in source_shape)
+            self.B, self.bytes = B, B * Hs * Ws * 3
+            check(self.lib.cnn_batch_stager_create_u8_aug(C.byref(self.h), B, Hs, Ws, H, W, depth), "cnn_batch_stager_create_u8_aug")
+        elif self.u8:
             B, H, W = (int(v) for v in u8_shape)
             self.bytes = B * H * W * 3
             check(self.lib.cnn_batch_stager_create_u8(C.byref(self.h), B, H, W, depth), "cnn_batch_stager_create_u8")
         else:
             self.bytes = int(batch_bytes)
             check(self.lib.cnn_batch_stager_create(C.byref(self.h), self.bytes, depth), "cnn_batch_stager_create")
+
+    def matrices(self, slot):
+        """-> numpy (B, 6) float32 view of the slot's pinned maps (an augmenting stager; acquire() preset them to the plain resize)"""
+        import numpy as np
+
+        p = C.POINTER(C.c_float)()
+        check(self.lib.cnn_batch_stager_matrices(self.h, int(slot), C.byref(p)), "cnn_batch_stager_matrices")
+        return np.ctypeslib.as_array((C.c_float * (self.B * 6)).from_address(C.addressof(p.contents))).reshape(self.B, 6)
+
+    def set_fill(self, fill):
+        """the value of output pixels whose sample position lies outside the source (an augmenting stager; default 0)"""
+        check(self.lib.cnn_batch_stager_set_fill(self.h, float(fill)), "cnn_batch_stager_set_fill")
 
     def acquire(self):
         """-> (numpy view of the pinned slot to fill -- float32, or uint8 for a u8 stager --, slot index); blocks until the slot is free"""

@@ -423,6 +423,13 @@ struct Stager {
     std::vector<void*> dev_f32;
     float* lut = nullptr;  // device: lut[v] = v * 1.f / 255, computed on the host
     int B = 0, H = 0, W = 0;
+    // augmenting u8 staging (cnn_batch_stager_create_u8_aug): `host` / `dev` hold B source images of Hs x Ws x 3 bytes, `mat_host`
+    // (pinned) / `mat_dev` the B * 6 floats of the per-sample maps, `dev_f32` the [B][3][H][W] batch cnn_augment_u8 writes
+    bool aug = false;
+    int Hs = 0, Ws = 0;
+    float fill = 0.f;
+    float resize_map[6] = {1, 0, 0, 0, 1, 0};  // what acquire() presets: the plain resize of the source to W x H
+    std::vector<float*> mat_host, mat_dev;
     std::vector<hipEvent_t> uploaded, consumed;
     std::vector<char> in_use;  // consumed[i] has been recorded at least once
 };
@@ -511,11 +518,60 @@ int cnn_batch_stager_create_u8(void** stager, int B, int H, int W, int depth) {
     return CNN_AMD_OK;
 }
 
+int cnn_batch_stager_create_u8_aug(void** stager, int B, int Hs, int Ws, int H, int W, int depth) {
+    CNN_REQUIRE(stager && B > 0 && B <= 8192 && depth >= 2 && depth <= 16, "cnn_batch_stager_create_u8_aug: bad arguments (B 1..8192, depth 2..16)");
+    float map[6];
+    if (int rc = cnn_augment_matrix(nullptr, 0, Hs, Ws, H, W, map)) return rc;  // (checks the four dimensions)
+    Stager* st = new Stager();
+    st->aug = true;
+    st->bytes = (size_t)B * Hs * Ws * 3;
+    st->depth = depth;
+    st->B = B; st->H = H; st->W = W; st->Hs = Hs; st->Ws = Ws;
+    memcpy(st->resize_map, map, sizeof(map));
+    st->host.assign(depth, nullptr); st->dev.assign(depth, nullptr); st->dev_f32.assign(depth, nullptr);
+    st->mat_host.assign(depth, nullptr); st->mat_dev.assign(depth, nullptr);
+    st->uploaded.assign(depth, nullptr); st->consumed.assign(depth, nullptr);
+    st->in_use.assign(depth, 0);
+    *stager = st;
+    CNN_HIP_CHECK(hipStreamCreateWithFlags(&st->copy, hipStreamNonBlocking));
+    for (int i = 0; i < depth; ++i) {
+        CNN_HIP_CHECK(hipHostMalloc(&st->host[i], st->bytes, hipHostMallocDefault));
+        CNN_HIP_CHECK(hipHostMalloc((void**)&st->mat_host[i], (size_t)B * 6 * sizeof(float), hipHostMallocDefault));
+        CNN_HIP_CHECK(hipMalloc(&st->dev[i], st->bytes));
+        CNN_HIP_CHECK(hipMalloc((void**)&st->mat_dev[i], (size_t)B * 6 * sizeof(float)));
+        CNN_HIP_CHECK(hipMalloc(&st->dev_f32[i], (size_t)B * 3 * H * W * sizeof(float)));
+        CNN_HIP_CHECK(hipEventCreateWithFlags(&st->uploaded[i], hipEventDisableTiming));
+        CNN_HIP_CHECK(hipEventCreateWithFlags(&st->consumed[i], hipEventDisableTiming));
+    }
+    return CNN_AMD_OK;
+}
+
+int cnn_batch_stager_matrices(void* stager, int slot, float** pinned) {
+    Stager* st = static_cast<Stager*>(stager);
+    CNN_REQUIRE(st && pinned && slot >= 0 && slot < st->depth, "cnn_batch_stager_matrices: bad arguments");
+    CNN_REQUIRE(st->aug, "cnn_batch_stager_matrices: not an augmenting stager (cnn_batch_stager_create_u8_aug)");
+    *pinned = st->mat_host[slot];
+    return CNN_AMD_OK;
+}
+
+int cnn_batch_stager_set_fill(void* stager, float fill) {
+    Stager* st = static_cast<Stager*>(stager);
+    CNN_REQUIRE(st, "cnn_batch_stager_set_fill: null stager");
+    CNN_REQUIRE(st->aug, "cnn_batch_stager_set_fill: not an augmenting stager (cnn_batch_stager_create_u8_aug)");
+    CNN_REQUIRE(fill - fill == 0.f, "cnn_batch_stager_set_fill: fill is not finite");
+    st->fill = fill;
+    return CNN_AMD_OK;
+}
+
 int cnn_batch_stager_destroy(void* stager) {
     Stager* st = static_cast<Stager*>(stager);
     if (!st) return CNN_AMD_OK;
     if (st->copy) (void)hipStreamSynchronize(st->copy);
     if (st->lut) (void)hipFree(st->lut);
+    for (float* p : st->mat_host)
+        if (p) (void)hipHostFree(p);
+    for (float* p : st->mat_dev)
+        if (p) (void)hipFree(p);
     for (void* p : st->dev_f32)
         if (p) (void)hipFree(p);
     for (int i = 0; i < st->depth; ++i) {
@@ -537,6 +593,8 @@ int cnn_batch_stager_acquire(void* stager, void** pinned_host, int* slot) {
     // the previous upload out of this slot must have left the host buffer, and its consumer must be done with the device one
     CNN_HIP_CHECK(hipEventSynchronize(st->uploaded[i]));
     if (st->in_use[i]) CNN_HIP_CHECK(hipEventSynchronize(st->consumed[i]));
+    if (st->aug)
+        for (int b = 0; b < st->B; ++b) memcpy(st->mat_host[i] + 6 * (size_t)b, st->resize_map, sizeof(st->resize_map));
     *pinned_host = st->host[i];
     *slot = i;
     return CNN_AMD_OK;
@@ -547,8 +605,15 @@ int cnn_batch_stager_submit(void* stager, int slot, void** device_ptr) {
     CNN_REQUIRE(st && device_ptr && slot >= 0 && slot < st->depth, "cnn_batch_stager_submit: bad arguments");
     if (st->in_use[slot]) CNN_HIP_CHECK(hipStreamWaitEvent(st->copy, st->consumed[slot], 0));
     CNN_HIP_CHECK(hipMemcpyAsync(st->dev[slot], st->host[slot], st->bytes, hipMemcpyHostToDevice, st->copy));
-    if (st->lut != nullptr) {  // bytes -> the fp32 planar batch, behind the copy on the same stream
+    if (st->aug) {  // bytes + per-sample maps -> the fp32 planar batch, behind both copies on the same stream
+        CNN_HIP_CHECK(hipMemcpyAsync(st->mat_dev[slot], st->mat_host[slot], (size_t)st->B * 6 * sizeof(float), hipMemcpyHostToDevice, st->copy));
+        if (int rc = cnn_augment_u8((const unsigned char*)st->dev[slot], st->B, st->Hs, st->Ws, st->mat_dev[slot], st->fill, (float*)st->dev_f32[slot],
+                                    st->H, st->W, st->copy))
+            return rc;
+    } else if (st->lut != nullptr) {  // bytes -> the fp32 planar batch, behind the copy on the same stream
         const int hw = st->H * st->W;
+        const bool timed = ktimer_active();  // (cnn_amd_kernel_timing_enable: tools/augment_bench.py times this launch)
+        if (timed) ktimer_begin(st->copy, "u8hwc_to_f32chw", "B=%d hw=%d", st->B, hw);
         if (hw % 4 == 0) {
             const int hw4 = hw / 4;
             const long long quads = (long long)st->B * hw4;
@@ -559,10 +624,11 @@ int cnn_batch_stager_submit(void* stager, int slot, void** device_ptr) {
             u8hwc_to_f32chw_px<<<stream_grid((size_t)px, 256), 256, 0, st->copy>>>((const unsigned char*)st->dev[slot], (float*)st->dev_f32[slot],
                                                                                    st->lut, hw, px);
         }
+        if (timed) ktimer_end(st->copy);
         CNN_LAUNCH_CHECK();
     }
     CNN_HIP_CHECK(hipEventRecord(st->uploaded[slot], st->copy));
-    *device_ptr = st->lut != nullptr ? st->dev_f32[slot] : st->dev[slot];
+    *device_ptr = (st->aug || st->lut != nullptr) ? st->dev_f32[slot] : st->dev[slot];
     return CNN_AMD_OK;
 }
 

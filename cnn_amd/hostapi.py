@@ -135,6 +135,34 @@ def mix_params(rng, H, W, mixup_alpha=0.8, cutmix_alpha=1.0, switch_prob=0.5, pa
     return capi.MixDesc(capi.MIX_CUTMIX, capi.cutmix_lambda(H, W, y0, y1, x0, x1), pair_rule, pair_shift, y0, y1, x0, x1)
 
 
+def augment_params(rng, B, Hs, Ws, H, W, hflip=0.5, vflip=0.2, crop=0.7, rotate=0.6, crop_min=0.7, max_angle=15.0):
+    """One batch's augmentation maps, sampled on the host the way the reference's ImageAugmentor::make_augment does (pipeline.cpp:40-77)
+    with `rng` (a numpy.random.Generator): per sample the four ops in a shuffled order, each firing with its own probability; crop: a
+    ratio uniform in [crop_min, 1] of the current canvas at a uniform position, rotate: an angle uniform in [-max_angle, max_angle]
+    degrees.  Composition goes through capi.augment_matrix (ops in order, then the resize to H x W).  Returns a (B, 6) float32 array
+    for BatchStager.matrices(slot) / capi.augment_u8."""
+    probs = {capi.AUG_HFLIP: hflip, capi.AUG_VFLIP: vflip, capi.AUG_CROP: crop, capi.AUG_ROTATE: rotate}
+    kinds = np.array(sorted(probs))
+    out = np.empty((B, 6), dtype=np.float32)
+    for b in range(B):
+        ops, cw, ch = [], int(Ws), int(Hs)
+        for kind in rng.permutation(kinds):
+            if not float(rng.random()) < probs[int(kind)]:
+                continue
+            if kind == capi.AUG_CROP:
+                ratio = float(rng.uniform(crop_min, 1.0))
+                w, h = max(1, int(cw * ratio)), max(1, int(ch * ratio))
+                x0, y0 = int(rng.integers(0, cw - w + 1)), int(rng.integers(0, ch - h + 1))
+                ops.append((capi.AUG_CROP, x0, y0, w, h))
+                cw, ch = w, h
+            elif kind == capi.AUG_ROTATE:
+                ops.append((capi.AUG_ROTATE, float(rng.uniform(-max_angle, max_angle))))
+            else:
+                ops.append((int(kind),))
+        out[b] = capi.augment_matrix(ops, Hs, Ws, H, W)
+    return out
+
+
 class HostNet:
     """architectures::Sequential / AlexNet (cnn_amd/host) behind a handle: the C++ Layer API a reference user links against."""
 

@@ -785,6 +785,50 @@ int cnn_batch_stager_submit(void* stager, int slot, void** device_ptr);
 int cnn_batch_stager_wait(void* stager, int slot, void* stream);
 int cnn_batch_stager_release(void* stager, int slot, void* stream);
 
+/* ---- geometric augmentation of uint8 batches on the device (an addition: ImageAugmentor, pipeline.cpp:40-77, runs OpenCV on the host).
+ * Flip, crop, rotate and the resize to the network's size are ONE affine map per sample; one kernel gathers through it while it does the
+ * stager's bytes -> fp32 planar conversion.  Decode, colour jitter and normalisation are not covered, and there is no antialiasing: a
+ * large shrink ratio aliases.
+ * The rule.  Input: interleaved bytes [B][Hs][Ws][3]; output: planar fp32 [B][3][H][W].  Sample b has six floats m[b][0..5] that map
+ * OUTPUT pixel indices to SOURCE pixel indices.  Per output pixel (x, y), all in fp32, every product and sum rounded separately:
+ *     sx = (m0*x + m1*y) + m2            sy = (m3*x + m4*y) + m5
+ *     inside = sx >= -0.5f && sx <= Ws-0.5f && sy >= -0.5f && sy <= Hs-0.5f
+ *     x0f = floorf(sx); fx = sx - x0f;   y0f = floorf(sy); fy = sy - y0f
+ *     x0 = clamp((int)x0f, 0, Ws-1); x1 = clamp((int)x0f + 1, 0, Ws-1)      (same for y)
+ *     t.. = lut[byte]                    (the stager's table: v * 1.f / 255 computed on the host)
+ *     top = t00 + fx*(t01 - t00); bot = t10 + fx*(t11 - t10); out = top + fy*(bot - top)
+ *     out = inside ? out : fill
+ * A position inside the source's pixel area reads edge-replicated taps (a resize), a position outside it gives `fill` (the constant
+ * border of a rotation's corners).  With fx == 0 the rule yields t00 exactly: the identity, flips, integer shifts and quarter turns are
+ * bit-identical to the plain conversion of the permuted image.  tests/augment_ref.py restates the rule in NumPy; the kernel equals it
+ * bit for bit.
+ * cnn_augment_u8: one launch per batch.  Checked before it: no null pointer, B and every dimension in 1..8192 (fp32 holds those indices
+ * exactly), a finite fill.  The matrices are device memory and are not checked on the host; a non-finite entry gives `fill`. */
+int cnn_augment_u8(const unsigned char* src, int B, int Hs, int Ws, const float* matrices_dev /* [B][6] */, float fill, float* dst, int H, int W,
+                   void* stream);
+/* cnn_augment_matrix composes such a map on the host (no GPU call).  The ops apply in order to a canvas that starts as the source, the way
+ * ImageAugmentor::make_augment transforms its cv::Mat: HFLIP / VFLIP mirror the canvas, CROP (a, b, c, d = x0, y0, w, h in the current
+ * canvas) shrinks it, ROTATE (a = degrees, positive = counter-clockwise on the screen as cv::getRotationMatrix2D) turns it about its
+ * centre ((cw-1)/2, (ch-1)/2) and keeps its size.  Last comes the resize of the canvas to W x H with half-pixel centres,
+ * sx = (x + 0.5) * cw / W - 0.5.  Composed in double, rounded to fp32 once.  Rotations by multiples of 90 degrees take sine and cosine
+ * from a table (integers map to integers); n_ops == 0 with equal sizes gives exactly {1,0,0, 0,1,0}.  Rejected: a crop box outside the
+ * current canvas, unknown kinds, non-finite arguments, dimensions outside 1..8192. */
+enum { CNN_AUG_HFLIP = 1, CNN_AUG_VFLIP = 2, CNN_AUG_CROP = 3, CNN_AUG_ROTATE = 4 };
+typedef struct cnn_augment_op {
+    int kind;
+    float a, b, c, d;
+} cnn_augment_op;
+int cnn_augment_matrix(const cnn_augment_op* ops, int n_ops, int Hs, int Ws, int H, int W, float m[6]);
+/* The u8 stager with that kernel in place of the plain conversion: a slot holds B images of Hs x Ws x 3 bytes and B * 6 pinned floats.
+ * acquire() presets the slot's matrices to the plain resize map (the identity when the sizes are equal), so a caller who does not touch
+ * them gets the plain conversion; cnn_batch_stager_matrices() hands out the slot's pinned block to overwrite between acquire() and
+ * submit().  submit() uploads bytes and matrices and runs cnn_augment_u8, all on the stager's stream in front of the event wait() waits
+ * for; it returns the fp32 [B][3][H][W] batch.  cnn_batch_stager_set_fill: the border value of later submits (default 0).  Both return
+ * CNN_AMD_E_BADARG on a stager of the other two kinds. */
+int cnn_batch_stager_create_u8_aug(void** stager, int B, int Hs, int Ws, int H, int W, int depth);
+int cnn_batch_stager_matrices(void* stager, int slot, float** pinned /* [B][6] */);
+int cnn_batch_stager_set_fill(void* stager, float fill);
+
 /* page-locked host memory (async H2D / D2H copies are only asynchronous from / to pinned buffers) */
 int cnn_host_alloc_pinned(void** ptr, size_t bytes);
 int cnn_host_free_pinned(void* ptr);
