@@ -77,11 +77,15 @@ int num_cus() {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
     int n = cached[dev].load(std::memory_order_relaxed);
-    if (n > 0) return n;
-    hipDeviceProp_t prop;
-    n = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    cached[dev].store(n, std::memory_order_relaxed);
-    return n;
+    if (n <= 0) {
+        hipDeviceProp_t prop;
+        n = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+        cached[dev].store(n, std::memory_order_relaxed);
+    }
+    // CNN_AMD_CUS=n (n >= 1): the planners see min(n, the device's count) -- a partitioned card, or a test that wants the
+    // "more blocks than CUs" side of every rule at a small shape.  Never above the device's count; unset, 0 or negative: the device's own.
+    const int want = CNN_OPT_INT("CUS", 0);
+    return (want >= 1 && want < n) ? want : n;
 }
 
 // ---- published kernels (common.h) ---------------------------------------------------------------------------------------------

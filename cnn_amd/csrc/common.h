@@ -113,7 +113,8 @@ inline OptVal opt_val(Option& o) { return OptVal{o.is_set(), o.as_int(0)}; }
 #endif
 bool measure_only_option(const char* name);  // (abi.hip) is `name` one of them
 
-// compute units of the current device (hipDeviceProp_t::multiProcessorCount, cached per device; 256 on MI355X)
+// compute units of the current device (hipDeviceProp_t::multiProcessorCount, cached per device; 256 on MI355X), or the smaller
+// count the switch CUS asks for (abi.hip)
 int num_cus();
 
 #define CNN_HIP_CHECK(expr)                                                                         \

@@ -41,7 +41,9 @@ const char* cnn_amd_device_arch(void);
 /* ---- measurement switches: the A/B switches of DESIGN.md section 10 (kernel-family choices, tile overrides, debug ablations).
  * The library reads the CNN_AMD_* variables of the environment ONCE, when it is first used; afterwards this is the only way to
  * change one (value == NULL removes it).  `name` with or without the "CNN_AMD_" prefix.  Not needed for normal use: the defaults
- * are the product path.  cnn_amd_get_option returns 0 and copies the value when the switch is set, 1 when it is not. */
+ * are the product path.  cnn_amd_get_option returns 0 and copies the value when the switch is set, 1 when it is not.
+ * CUS=n (n >= 1): every planner sizes its grids, slab counts and tile choices for min(n, the device's compute units) -- a partition
+ * of the card, or a test that drives the large-shape branches at a small shape; unset, 0 or negative: the device's own count. */
 int cnn_amd_set_option(const char* name, const char* value);
 int cnn_amd_get_option(const char* name, char* value_out, size_t cap);
 /* Switches that change RESULTS or exist for timing experiments only (a kernel without its stores / DMAs / MFMAs, per-phase cycle

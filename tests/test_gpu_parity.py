@@ -84,13 +84,32 @@ def _conv_inputs(case, seed):
     return x, w, b, dy
 
 
-def _oracle_conv(case, x, w, b, dy):
-    """oracle results; padding = reference conv on the zero-padded input (Tensor3D::pad, data_format.cpp:139-150)"""
+_ORACLE_MEMO = {}
+
+
+def _oracle_conv(case, x, w, b, dy, seed=None):
+    """oracle results; padding = reference conv on the zero-padded input (Tensor3D::pad, data_format.cpp:139-150).
+    seed: the seed x, w, b, dy = _conv_inputs(case, seed) came from, unchanged -- the result is then computed once per (case, seed) and
+    session (tests/test_gpu_cu_counts.py repeats these comparisons at other CU counts) and handed out read-only; the inputs' checksums are
+    kept with the entry and compared on a hit"""
+    if seed is not None:
+        import zlib
+
+        crc = tuple(zlib.crc32(np.ascontiguousarray(a).view(np.uint8)) for a in (x, w, b, dy))
+        if (case, seed) in _ORACLE_MEMO:
+            known, result = _ORACLE_MEMO[(case, seed)]
+            assert known == crc, f"_oracle_conv{case}: seed {seed} was passed with inputs that are not the ones it was first asked with"
+            return result
     B, Ci, H, W, Co, k, s, pad = case
     xp = np.pad(x, ((0, 0), (0, 0), (pad, pad), (pad, pad))) if pad else x
     y = O.conv2d_forward(xp, w, b, s)
     gw, gb, dxp = O.conv2d_backward(xp, dy, w, s)
     dx = dxp[:, :, pad : pad + H, pad : pad + W] if pad else dxp
+    if seed is not None:
+        for a in (y, gw, gb, dxp):
+            a.flags.writeable = False
+        dx = dxp[:, :, pad : pad + H, pad : pad + W] if pad else dxp  # (a view taken after the freeze is read-only too)
+        _ORACLE_MEMO[(case, seed)] = (crc, (y, gw, gb, dx))
     return y, gw, gb, dx
 
 
@@ -99,7 +118,7 @@ def test_conv2d_mfma_vs_oracle(T, case):
     from cnn_amd import capi
 
     x, w, b, dy = _conv_inputs(case, 100)
-    y_ref, gw_ref, gb_ref, dx_ref = _oracle_conv(case, x, w, b, dy)
+    y_ref, gw_ref, gb_ref, dx_ref = _oracle_conv(case, x, w, b, dy, 100)
     conv = capi.Conv2d(*case)
     xd, wd, bd, dyd = dev(T, x), dev(T, w), dev(T, b), dev(T, dy)
     assert_close(host(conv.forward(xd, wd, bd)), y_ref, REL_TOL, "forward")
@@ -154,7 +173,7 @@ def test_conv2d_wgrad_register_direct(T, case, slow, lib_option):
     from cnn_amd import capi
 
     x, w, b, dy = _conv_inputs(case, 400)
-    _, gw_ref, gb_ref, _ = _oracle_conv(case, x, w, b, dy)
+    _, gw_ref, gb_ref, _ = _oracle_conv(case, x, w, b, dy, 400)
     lib_option("WGRAD_SP", "0")  # (this test is about conv_wgrad_rd.hip; the small-plane kernel has test_conv2d_wgrad_small_planes)
     conv = capi.Conv2d(*case)
     xd, dyd = dev(T, x), dev(T, dy)
@@ -199,13 +218,19 @@ SP_CASES = [
 def test_conv2d_wgrad_small_planes(T, case, unit, lib_option):
     """conv_wgrad_sp.hip (LDS-staged output-stationary kernel for 7x7 .. 56x56 planes, cpu/src/conv2d.cpp:117-159) against the
     oracle, with 16-byte and with 4-byte DMA staging, on pointers that are and are not 16-byte aligned"""
+    rep = _wgrad_small_planes(T, case, unit, lib_option)
+    assert any(k.startswith("wgrad_sp<") for k in rep), list(rep)
+
+
+def _wgrad_small_planes(T, case, unit, lib_option):
+    """the comparisons of test_conv2d_wgrad_small_planes -> the launch log of the first weight gradient"""
     from cnn_amd import capi
 
     lib_option("WGRAD_SP", "1")  # (also lifts the 32-channel floor of the default dispatch)
     if unit:
         lib_option("SP_UNIT", "1")
     x, w, b, dy = _conv_inputs(case, 430)
-    _, gw_ref, gb_ref, _ = _oracle_conv(case, x, w, b, dy)
+    _, gw_ref, gb_ref, _ = _oracle_conv(case, x, w, b, dy, 430)
     conv = capi.Conv2d(*case)
     xd, dyd = dev(T, x), dev(T, dy)
     capi.kernel_timing(1)
@@ -213,7 +238,6 @@ def test_conv2d_wgrad_small_planes(T, case, unit, lib_option):
     T.cuda.synchronize()
     rep = capi.kernel_timing_report()
     capi.kernel_timing(0)
-    assert any(k.startswith("wgrad_sp<") for k in rep), list(rep)
     assert_close(host(gw), gw_ref, REL_TOL, "weight grad")
     assert_close(host(gb), gb_ref, REL_TOL, "bias grad")
     if unit == 0:
@@ -226,6 +250,7 @@ def test_conv2d_wgrad_small_planes(T, case, unit, lib_option):
     lib_option("WGRAD_SP", "0")
     gw3, gb3 = conv.backward_weight(xd, dyd, float(case[0]))
     assert_close(host(gw3), gw_ref, REL_TOL, "register-direct weight grad")
+    return rep
 
 
 SP2_CASES = [
@@ -245,11 +270,17 @@ SP2_CASES = [
 def test_conv2d_wgrad_small_planes_stride2(T, case, lib_option):
     """conv_wgrad_sp2.hip (the stride-2 sibling of the LDS-staged output-stationary weight gradient; cpu/src/conv2d.cpp:117-159 with the
     window walk of conv2d.cpp:76-77) against the oracle, on 16-byte aligned and unaligned tensors, and against the kernel it replaces"""
+    rep = _wgrad_small_planes_stride2(T, case, lib_option)
+    assert any(k.startswith("wgrad_sp2<") for k in rep), list(rep)
+
+
+def _wgrad_small_planes_stride2(T, case, lib_option):
+    """the comparisons of test_conv2d_wgrad_small_planes_stride2 -> the launch log of the first weight gradient"""
     from cnn_amd import capi
 
     lib_option("WGRAD_SP2", "2")  # (every instance, any channel count)
     x, w, b, dy = _conv_inputs(case, 470)
-    _, gw_ref, gb_ref, _ = _oracle_conv(case, x, w, b, dy)
+    _, gw_ref, gb_ref, _ = _oracle_conv(case, x, w, b, dy, 470)
     conv = capi.Conv2d(*case)
     xd, dyd = dev(T, x), dev(T, dy)
     capi.kernel_timing(1)
@@ -257,7 +288,6 @@ def test_conv2d_wgrad_small_planes_stride2(T, case, lib_option):
     T.cuda.synchronize()
     rep = capi.kernel_timing_report()
     capi.kernel_timing(0)
-    assert any(k.startswith("wgrad_sp2<") for k in rep), list(rep)
     assert_close(host(gw), gw_ref, REL_TOL, "weight grad")
     assert_close(host(gb), gb_ref, REL_TOL, "bias grad")
     # the same tensors one float further: the DMA sources need 4-byte alignment only -- same sums in the same order
@@ -276,6 +306,7 @@ def test_conv2d_wgrad_small_planes_stride2(T, case, lib_option):
     lib_option("WGRAD_SP2", "0")
     gw3, gb3 = conv.backward_weight(xd, dyd, float(case[0]))
     assert_close(host(gw3), gw_ref, REL_TOL, "the replaced kernel's weight grad")
+    return rep
 
 
 SPA_CASES = [
@@ -304,11 +335,17 @@ def test_conv2d_wgrad_any_size_vs_oracle(T, case, lib_option):
     """conv_wgrad_sp_any.hip (round 6: the runtime-size member of the LDS-staged output-stationary weight gradient, any plane size,
     cpu/src/conv2d.cpp:117-159 / 41-42) against the oracle, on aligned and unaligned tensors, with NaN around the tensors (everything
     outside them is a zero in LDS, never a value), one workgroup per tile walking every stage, and against the kernel it replaces"""
+    rep = _wgrad_any_size(T, case, lib_option)
+    assert any(k.startswith("wgrad_sp_any<") for k in rep), list(rep)
+
+
+def _wgrad_any_size(T, case, lib_option):
+    """the comparisons of test_conv2d_wgrad_any_size_vs_oracle -> the launch log of the first weight gradient"""
     from cnn_amd import capi
 
     lib_option("WGRAD_SP_ANY", "2")  # (also lifts the 32-channel floor of the default dispatch)
     x, w, b, dy = _conv_inputs(case, 475)
-    _, gw_ref, gb_ref, _ = _oracle_conv(case, x, w, b, dy)
+    _, gw_ref, gb_ref, _ = _oracle_conv(case, x, w, b, dy, 475)
     conv = capi.Conv2d(*case)
     xd, dyd = dev(T, x), dev(T, dy)
     capi.kernel_timing(1)
@@ -316,7 +353,6 @@ def test_conv2d_wgrad_any_size_vs_oracle(T, case, lib_option):
     T.cuda.synchronize()
     rep = capi.kernel_timing_report()
     capi.kernel_timing(0)
-    assert any(k.startswith("wgrad_sp_any<") for k in rep), list(rep)
     assert_close(host(gw), gw_ref, REL_TOL, "weight grad")
     assert_close(host(gb), gb_ref, REL_TOL, "bias grad")
     xs = T.empty(xd.numel() + 1, device="cuda")[1:].view_as(xd).copy_(xd)
@@ -338,6 +374,7 @@ def test_conv2d_wgrad_any_size_vs_oracle(T, case, lib_option):
     lib_option("WGRAD_SP_ANY", "0")
     gw3, gb3 = conv.backward_weight(xd, dyd, float(case[0]))
     assert_close(host(gw3), gw_ref, REL_TOL, "the replaced kernel's weight grad")
+    return rep
 
 
 @pytest.mark.parametrize("case", [SP_CASES[i] for i in (0, 2, 3, 5, 7)] + [(4, 16, 55, 55, 32, 3, 2, 0), (3, 64, 13, 13, 128, 3, 2, 0), (2, 32, 27, 27, 64, 3, 2, 0)],
@@ -379,10 +416,17 @@ ROWS_CASES = [
 def test_conv2d_row_kernel_vs_oracle(T, case, lib_option):
     """conv_rows.hip (round 5: LDS-staged 3x3 / stride-1 forward and data gradient of wide planes, conv2d.cpp:69-92 / 168-199) against the
     oracle, and against the implicit GEMM it replaces on these geometries (CNN_AMD_CONV_ROWS=0)"""
+    default, walk = _row_kernel(T, case, lib_option)
+    assert sum(n.startswith("conv_rows<") for n in default) == 2, default
+    assert sum(n.startswith("conv_rows<") for n in walk) == 4, walk
+
+
+def _row_kernel(T, case, lib_option):
+    """the comparisons of test_conv2d_row_kernel_vs_oracle -> the kernel names of the default launches and of the ROWS_BLOCKS=1 ones"""
     from cnn_amd import capi
 
     x, w, b, dy = _conv_inputs(case, 440)
-    y_ref, _, _, dx_ref = _oracle_conv(case, x, w, b, dy)
+    y_ref, _, _, dx_ref = _oracle_conv(case, x, w, b, dy, 440)
     conv = capi.Conv2d(*case)
     xd, wd, bd, dyd = dev(T, x), dev(T, w), dev(T, b), dev(T, dy)
     capi.kernel_timing(1)
@@ -391,7 +435,7 @@ def test_conv2d_row_kernel_vs_oracle(T, case, lib_option):
     T.cuda.synchronize()
     names = [k.split("|")[0] for k in capi.kernel_timing_report()]
     capi.kernel_timing(0)
-    assert sum(n.startswith("conv_rows<") for n in names) == 2, names
+    default = names
     assert_close(host(y), y_ref, REL_TOL, "row kernel forward")
     assert_close(host(dx), dx_ref, REL_TOL, "row kernel data gradient")
     # the unit walk: with one workgroup per output-channel tile for the whole launch every workgroup walks ALL units
@@ -410,7 +454,6 @@ def test_conv2d_row_kernel_vs_oracle(T, case, lib_option):
     T.cuda.synchronize()
     names = [k.split("|")[0] for k in capi.kernel_timing_report()]
     capi.kernel_timing(0)
-    assert sum(n.startswith("conv_rows<") for n in names) == 4, names
     assert_close(host(y), y_ref, REL_TOL, "row kernel forward, one workgroup walks every unit")
     assert_close(host(dx), dx_ref, REL_TOL, "row kernel data gradient, one workgroup walks every unit")
     assert_close(host(y2), y_ref, REL_TOL, "row kernel forward + ReLU, pre-activation")
@@ -428,6 +471,7 @@ def test_conv2d_row_kernel_vs_oracle(T, case, lib_option):
     lib_option("CONV_ROWS", "0")
     assert_close(host(conv.forward(xd, wd, bd)), y_ref, REL_TOL, "implicit GEMM forward")
     assert_close(host(conv.backward_data(dyd, wd)), dx_ref, REL_TOL, "implicit GEMM data gradient")
+    return default, names
 
 
 ANY_CASES = [
@@ -450,12 +494,19 @@ def test_conv2d_row_kernel_any_width_vs_oracle(T, case, lib_option):
     """conv_rows_any.hip (round 6: the runtime-width member of the row-kernel family -- 3x3 / stride-1 layers of ANY plane size up to 224
     columns, conv2d.cpp:41-42; forward conv2d.cpp:69-92, data gradient conv2d.cpp:168-199) against the oracle: default walk, one workgroup
     walking every unit, the ReLU / ReLU' epilogues, and against the kernels it replaces (ROWS_ANY=0)"""
+    for names in _row_kernel_any_width(T, case, lib_option):
+        assert sum(n.startswith("conv_rows_any<") for n in names) == (4 if case[1] >= 16 else 2), names
+
+
+def _row_kernel_any_width(T, case, lib_option):
+    """the comparisons of test_conv2d_row_kernel_any_width_vs_oracle -> the kernel names of the default walk and of the ROWS_BLOCKS=1 one"""
     from cnn_amd import capi
 
     x, w, b, dy = _conv_inputs(case, 455)
-    y_ref, _, _, dx_ref = _oracle_conv(case, x, w, b, dy)
+    y_ref, _, _, dx_ref = _oracle_conv(case, x, w, b, dy, 455)
     conv = capi.Conv2d(*case)
     xd, wd, bd, dyd = dev(T, x), dev(T, w), dev(T, b), dev(T, dy)
+    logs = []
     for blocks in (None, "1"):
         lib_option("ROWS_BLOCKS", blocks)
         capi.kernel_timing(1)
@@ -467,9 +518,8 @@ def test_conv2d_row_kernel_any_width_vs_oracle(T, case, lib_option):
         dxm = T.full_like(xd, 7.0)
         conv.backward_data_relu(dyd, wd, relu_in, dxm)
         T.cuda.synchronize()
-        names = [k.split("|")[0] for k in capi.kernel_timing_report()]
+        logs.append([k.split("|")[0] for k in capi.kernel_timing_report()])
         capi.kernel_timing(0)
-        assert sum(n.startswith("conv_rows_any<") for n in names) == (4 if case[1] >= 16 else 2), names
         assert_close(host(y), y_ref, REL_TOL, "any-width forward")
         assert_close(host(dx), dx_ref, REL_TOL, "any-width data gradient")
         assert_close(host(y2), y_ref, REL_TOL, "any-width forward + ReLU, pre-activation")
@@ -486,6 +536,7 @@ def test_conv2d_row_kernel_any_width_vs_oracle(T, case, lib_option):
     lib_option("ROWS_ANY", "0")
     assert_close(host(conv.forward(xd, wd, bd)), y_ref, REL_TOL, "the replaced kernel's forward")
     assert_close(host(conv.backward_data(dyd, wd)), dx_ref, REL_TOL, "the replaced kernel's data gradient")
+    return logs
 
 
 TALL_CASES = [
@@ -501,14 +552,22 @@ def test_conv2d_row_kernel_tall_units_vs_oracle(T, case, lib_option):
     """conv_rows.hip's TALL units (round 6: the batch-64 layers of the ResNet-shaped stack as 256 units instead of 448; conv2d.cpp:69-92 /
     168-199) against the oracle: forced here (ROWS_TALL=2: at these batch sizes the planner would not pick them), as one unit per workgroup
     and with one workgroup walking every unit, with the ReLU / ReLU' epilogues; bit-identical to the short units (same sums, same order)"""
+    for names in _row_kernel_tall_units(T, case, lib_option):
+        tall = [n for n in names if n.startswith("conv_rows<") and ",r14>" in n or ",r7>" in n]
+        assert len(tall) == 4, names
+
+
+def _row_kernel_tall_units(T, case, lib_option):
+    """the comparisons of test_conv2d_row_kernel_tall_units_vs_oracle -> the kernel names of the default walk and of the ROWS_BLOCKS=1 one"""
     from cnn_amd import capi
 
     x, w, b, dy = _conv_inputs(case, 445)
-    y_ref, _, _, dx_ref = _oracle_conv(case, x, w, b, dy)
+    y_ref, _, _, dx_ref = _oracle_conv(case, x, w, b, dy, 445)
     conv = capi.Conv2d(*case)
     xd, wd, bd, dyd = dev(T, x), dev(T, w), dev(T, b), dev(T, dy)
     y0, dx0 = conv.forward(xd, wd, bd), conv.backward_data(dyd, wd)
     lib_option("ROWS_TALL", "2")
+    logs = []
     for blocks in (None, "1"):
         lib_option("ROWS_BLOCKS", blocks)
         capi.kernel_timing(1)
@@ -520,10 +579,8 @@ def test_conv2d_row_kernel_tall_units_vs_oracle(T, case, lib_option):
         dxm = T.full_like(xd, 7.0)
         conv.backward_data_relu(dyd, wd, relu_in, dxm)
         T.cuda.synchronize()
-        names = [k.split("|")[0] for k in capi.kernel_timing_report()]
+        logs.append([k.split("|")[0] for k in capi.kernel_timing_report()])
         capi.kernel_timing(0)
-        tall = [n for n in names if n.startswith("conv_rows<") and ",r14>" in n or ",r7>" in n]
-        assert len(tall) == 4, names
         assert_close(host(y), y_ref, REL_TOL, "tall units forward")
         assert_close(host(dx), dx_ref, REL_TOL, "tall units data gradient")
         assert_close(host(y2), y_ref, REL_TOL, "tall units forward + ReLU, pre-activation")
@@ -531,6 +588,7 @@ def test_conv2d_row_kernel_tall_units_vs_oracle(T, case, lib_option):
         assert_close(host(dxm), np.where(host(relu_in) <= 0, np.float32(0), dx_ref), REL_TOL, "tall units data gradient + ReLU'")
         assert np.array_equal(host(y).view(np.uint32), host(y0).view(np.uint32))
         assert np.array_equal(host(dx).view(np.uint32), host(dx0).view(np.uint32))
+    return logs
 
 
 STEM_DGRAD_CASES = [
@@ -548,7 +606,7 @@ def test_conv2d_stem_data_gradient_packed_vs_oracle(T, case, lib_option):
     from cnn_amd import capi
 
     x, w, b, dy = _conv_inputs(case, 611)
-    _, _, _, dx_ref = _oracle_conv(case, x, w, b, dy)
+    _, _, _, dx_ref = _oracle_conv(case, x, w, b, dy, 611)
     conv = capi.Conv2d(*case)
     xd, wd, dyd = dev(T, x), dev(T, w), dev(T, dy)
     capi.kernel_timing(1)
@@ -592,14 +650,21 @@ def test_conv2d_stride2_row_kernel_vs_oracle(T, case, lib_option):
     default stride) against the oracle: default dispatch, then with one workgroup walking every unit of the launch (the unit loop's
     cross-unit prefetch and ragged last units in the middle of a walk), with the fused ReLU / ReLU' epilogues; and against the kernels it
     replaces on these geometries (CNN_AMD_CONV_S2=0)"""
+    for names in _stride2_row_kernel(T, case, lib_option):
+        assert sum(n.startswith("conv_s2<") for n in names) == 4, names
+
+
+def _stride2_row_kernel(T, case, lib_option):
+    """the comparisons of test_conv2d_stride2_row_kernel_vs_oracle -> the kernel names of the default grid and of the S2_BLOCKS=1 one"""
     from cnn_amd import capi
 
     x, w, b, dy = _conv_inputs(case, 540)
-    y_ref, _, _, dx_ref = _oracle_conv(case, x, w, b, dy)
+    y_ref, _, _, dx_ref = _oracle_conv(case, x, w, b, dy, 540)
     conv = capi.Conv2d(*case)
     xd, wd, bd, dyd = dev(T, x), dev(T, w), dev(T, b), dev(T, dy)
     relu_in = capi.relu_forward(xd - 0.5)  # the output of a ReLU layer in front (half of it blocked)
     lib_option("CONV_S2", "2")  # (every instance, also those the default dispatch leaves to the register-direct kernels)
+    logs = []
     for blocks in (None, "1"):
         lib_option("S2_BLOCKS", blocks)
         capi.kernel_timing(1)
@@ -612,9 +677,8 @@ def test_conv2d_stride2_row_kernel_vs_oracle(T, case, lib_option):
         dxm = T.full_like(xd, 7.0)
         conv.backward_data_relu(dyd, wd, relu_in, dxm)
         T.cuda.synchronize()
-        names = [k.split("|")[0] for k in capi.kernel_timing_report()]
+        logs.append([k.split("|")[0] for k in capi.kernel_timing_report()])
         capi.kernel_timing(0)
-        assert sum(n.startswith("conv_s2<") for n in names) == 4, names
         tag = "default grid" if blocks is None else "one workgroup walks every unit"
         assert_close(host(y), y_ref, REL_TOL, f"stride-2 row kernel forward, {tag}")
         assert_close(host(dx), dx_ref, REL_TOL, f"stride-2 row kernel data gradient, {tag}")
@@ -625,6 +689,7 @@ def test_conv2d_stride2_row_kernel_vs_oracle(T, case, lib_option):
     lib_option("CONV_S2", "0")
     assert_close(host(conv.forward(xd, wd, bd)), y_ref, REL_TOL, "replaced forward kernel")
     assert_close(host(conv.backward_data(dyd, wd)), dx_ref, REL_TOL, "replaced data-gradient kernel")
+    return logs
 
 
 @pytest.mark.parametrize("case", [(8, 64, 112, 112, 128, 3, 1, 0), (16, 128, 28, 28, 128, 3, 1, 1), (9, 48, 7, 7, 80, 3, 1, 1)],
@@ -1517,7 +1582,7 @@ def test_conv2d_forward_kernel_families(T, case, family, lib_option):
 
     lib_option("FWD_M16", "1" if family == "m16" else "0")
     x, w, b, dy = _conv_inputs(case, 740)
-    y_ref = _oracle_conv(case, x, w, b, dy)[0]
+    y_ref = _oracle_conv(case, x, w, b, dy, 740)[0]
     conv = capi.Conv2d(*case)
     xd, wd, bd = dev(T, x), dev(T, w), dev(T, b)
     y = conv.forward(xd, wd, bd)
@@ -1545,7 +1610,7 @@ def test_conv2d_dgrad_register_direct_opt_in_tiles(T, case, lib_option):
 
     lib_option("DGRAD_RD32", "1")
     x, w, b, dy = _conv_inputs(case, 730)
-    _, _, _, dx_ref = _oracle_conv(case, x, w, b, dy)
+    _, _, _, dx_ref = _oracle_conv(case, x, w, b, dy, 730)
     relu_below = np.maximum(x - 0.3, 0).astype(np.float32)
     conv = capi.Conv2d(*case)
     wd, dyd, rd = dev(T, w), dev(T, dy), dev(T, relu_below)
