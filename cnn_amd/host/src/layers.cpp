@@ -165,7 +165,11 @@ void Conv2D::ensure_workspace(int B, int H, int W) {
     cnn_conv2d_desc d{B, in_channels, H, W, out_channels, kernel_size, stride, padding, 0};
     const size_t need = cnn_conv2d_workspace_bytes(&d);
     if (need == 0) must(1, "cnn_conv2d_workspace_bytes");
-    workspace.reserve(need);
+    // A training pass sizes the buffer for its backward pass right away (backward_prelude asks for more than the forward kernels do):
+    // growing it there would free the first buffer, and a device free waits for every stream of the device -- the first train step
+    // of a net then blocked the host until the caller's stream had drained.
+    const size_t bwd = no_grad ? 0 : cnn_conv2d_backward_workspace_bytes(&d);
+    workspace.reserve(bwd > need ? bwd : need);
 }
 
 // cnn_conv2d_autotune for a geometry this layer sees for the first time -- with the CALLER's scratch (include/cnn_amd.h: "no allocation

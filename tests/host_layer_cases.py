@@ -87,8 +87,12 @@ def _rc(error):
     return f"rc={m.group(1)}" if m else "rc=3"
 
 
-def run_case(T, name):
-    """-> {"log": {key: launches}, "sha": {what: digest | "rc=<n>"}} of one case, on a fresh net and seeded inputs"""
+def run_case(T, name, driver=None):
+    """-> {"log": {key: launches}, "sha": {what: digest | "rc=<n>"}} of one case, on a fresh net and seeded inputs.
+    driver (the stream-order tests; None leaves the run and its record as they are): driver.before_steps(xd, ld) is called with the
+    device batch and labels in front of the call sequence, driver.before_op(i, op) / driver.after_op(i, op) around every call of it,
+    driver.after_steps() behind the flush that follows it, before anything is read back; kernel timing then stays off and the log
+    is empty"""
     from cnn_amd import capi, hostapi
 
     net_name, ops = CASES[name][:2]
@@ -104,9 +108,14 @@ def run_case(T, name):
     xd, ld = T.from_numpy(x).cuda(), T.from_numpy(labels).cuda()
     sha, last_B, device_loss = {}, B, False
     T.cuda.synchronize()
-    capi.kernel_timing(1)
+    if driver is None:
+        capi.kernel_timing(1)
     try:
+        if driver is not None:
+            driver.before_steps(xd, ld)
         for i, op in enumerate(ops):
+            if driver is not None:
+                driver.before_op(i, op)
             if op[0] == "step":
                 last_B = B + op[1] if len(op) > 1 else B
                 net.train_step(xd[:last_B], ld[:last_B], 1e-2)
@@ -129,7 +138,11 @@ def run_case(T, name):
                 C_, H_, W_ = layout[names.index(op[1])]["out"]
                 img, cam = net.grad_cam(op[1], (last_B, H_, W_))
                 sha[f"{i}:cam_image"], sha[f"{i}:cam"] = _sha(img), _sha(cam)
+            if driver is not None:
+                driver.after_op(i, op)
         net.flush()
+        if driver is not None:
+            driver.after_steps()
         sha["params"], sha["grads"] = _sha(net.get_params()), _sha(net.get_grads())
         if device_loss:
             sha["last_loss"] = _sha(np.float32(net.last_loss()))
@@ -143,9 +156,10 @@ def run_case(T, name):
         except KeyError as e:
             sha["input_delta"] = _rc(e)
         T.cuda.synchronize()
-        log = {k: cnt for k, (cnt, _) in capi.kernel_timing_report().items()}
+        log = {k: cnt for k, (cnt, _) in capi.kernel_timing_report().items()} if driver is None else {}
     finally:
-        capi.kernel_timing(0)
+        if driver is None:
+            capi.kernel_timing(0)
         if option:
             capi.set_option(option[0], old_option)
         for fn in SWITCHES.values():
