@@ -47,6 +47,16 @@ class AugmentOp(C.Structure):
 
 AUG_HFLIP, AUG_VFLIP, AUG_CROP, AUG_ROTATE = 1, 2, 3, 4  # CNN_AUG_*
 
+
+class ColourOp(C.Structure):
+    """mirror of cnn_colour_op"""
+
+    _fields_ = [("kind", C.c_int), ("a", C.c_float), ("b", C.c_float)]
+
+
+COL_BRIGHTNESS, COL_CONTRAST, COL_SATURATION, COL_HUE = 1, 2, 3, 4  # CNN_COL_*
+PHOTO_FLOATS = 20  # a sample's photo block: A[9], o[3], ex0, ey0, ew, eh, ev[3], reserved
+
 PAIR_NONE, PAIR_FLIP, PAIR_ROLL = 0, 1, 2  # CNN_PAIR_*
 MIX_MIXUP, MIX_CUTMIX = 1, 2  # CNN_MIX_*
 
@@ -169,6 +179,10 @@ SIGNATURES = {
     "cnn_batch_stager_create_u8_aug": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "cnn_batch_stager_matrices": (C.c_int, [_P, C.c_int, C.POINTER(C.POINTER(C.c_float))]),
     "cnn_batch_stager_set_fill": (C.c_int, [_P, C.c_float]),
+    "cnn_batch_stager_create_u8_photo": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "cnn_batch_stager_photo": (C.c_int, [_P, C.c_int, C.POINTER(C.POINTER(C.c_float))]),
+    "cnn_batch_stager_set_normalize": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int]),
+    "cnn_colour_matrix": (C.c_int, [C.POINTER(ColourOp), C.c_int, C.POINTER(C.c_float)]),
     "cnn_linear_forward": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "cnn_linear_backward": (C.c_int, [_P] * 6 + [C.c_int] * 3 + [C.c_float, _P]),
     "cnn_linear_backward_relu": (C.c_int, [_P] * 6 + [C.c_int] * 3 + [C.c_float, _P]),
@@ -1023,6 +1037,19 @@ def augment_matrix(ops, Hs, Ws, H, W):
     return m
 
 
+def colour_matrix(ops):
+    """cnn_colour_matrix (host only): ops, a sequence of ColourOp or (kind, a[, b]) tuples, applied in order with no clamp between them
+    -> (12,) float32: A row-major and o, the first twelve floats of a sample's photo block (BatchStager.photo(slot))"""
+    import numpy as np
+
+    arr = (ColourOp * max(len(ops), 1))()
+    for i, op in enumerate(ops):
+        arr[i] = op if isinstance(op, ColourOp) else ColourOp(int(op[0]), *[float(v) for v in op[1:]])
+    out = np.empty(12, dtype=np.float32)
+    check(load().cnn_colour_matrix(arr, len(ops), out.ctypes.data_as(C.POINTER(C.c_float))), "cnn_colour_matrix")
+    return out
+
+
 def augment_u8(src_u8, matrices, H, W, fill=0.0, out=None):
     """cnn_augment_u8: uint8 [B][Hs][Ws][3] and float32 [B][6] device tensors -> the float32 [B][3][H][W] batch, one launch"""
     import torch
@@ -1133,22 +1160,28 @@ def side_stream_join():
 class BatchStager:
     """cnn_batch_stager_*: `depth` pinned host slots + device buffers, uploads on a copy stream of its own, ordered by events"""
 
-    def __init__(self, batch_bytes=None, depth=2, u8_shape=None, source_shape=None, augment=False):
+    def __init__(self, batch_bytes=None, depth=2, u8_shape=None, source_shape=None, augment=False, photo=False):
         """u8_shape=(B, H, W): the slots hold interleaved BYTES [B][H][W][3] (cv::Mat CV_8UC3), submit() returns the fp32 planar batch
         the stager's conversion kernel writes (cnn_batch_stager_create_u8).  augment=True or source_shape=(Hs, Ws): the slots hold
         [B][Hs][Ws][3] bytes (Hs, Ws = H, W when source_shape is None) and per-sample maps, matrices(slot); submit() returns the
-        [B][3][H][W] batch cnn_augment_u8 writes through them (cnn_batch_stager_create_u8_aug)"""
+        [B][3][H][W] batch cnn_augment_u8 writes through them (cnn_batch_stager_create_u8_aug).  photo=True: an augmenting stager
+        whose slots also carry (B, 20) photometric parameters, photo(slot) -- colour matrix, erase box -- and whose kernel applies them
+        and set_normalize()'s mean / std behind the gather (cnn_batch_stager_create_u8_photo)"""
         self.lib = load()
         self.h = C.c_void_p()
         self.u8 = u8_shape is not None
-        self.aug = bool(augment) or source_shape is not None
+        self.is_photo = bool(photo)
+        self.aug = bool(augment) or source_shape is not None or self.is_photo
         if self.aug and not self.u8:
             raise CnnAmdError("BatchStager: augment / source_shape need u8_shape=(B, H, W)")
         if self.aug:
             B, H, W = (int(v) for v in u8_shape)
             Hs, Ws = (H, W) if source_shape is None else (int(v) for v in source_shape)
             self.B, self.bytes = B, B * Hs * Ws * 3
-            check(self.lib.cnn_batch_stager_create_u8_aug(C.byref(self.h), B, Hs, Ws, H, W, depth), "cnn_batch_stager_create_u8_aug")
+            if self.is_photo:
+                check(self.lib.cnn_batch_stager_create_u8_photo(C.byref(self.h), B, Hs, Ws, H, W, depth), "cnn_batch_stager_create_u8_photo")
+            else:
+                check(self.lib.cnn_batch_stager_create_u8_aug(C.byref(self.h), B, Hs, Ws, H, W, depth), "cnn_batch_stager_create_u8_aug")
         elif self.u8:
             B, H, W = (int(v) for v in u8_shape)
             self.bytes = B * H * W * 3
@@ -1168,6 +1201,22 @@ class BatchStager:
     def set_fill(self, fill):
         """the value of output pixels whose sample position lies outside the source (an augmenting stager; default 0)"""
         check(self.lib.cnn_batch_stager_set_fill(self.h, float(fill)), "cnn_batch_stager_set_fill")
+
+    def photo(self, slot):
+        """-> numpy (B, 20) float32 view of the slot's pinned photometric parameters (a photo stager; acquire() preset them to the
+        identity: A = I, o = 0, no box)"""
+        import numpy as np
+
+        p = C.POINTER(C.c_float)()
+        check(self.lib.cnn_batch_stager_photo(self.h, int(slot), C.byref(p)), "cnn_batch_stager_photo")
+        B = getattr(self, "B", 0)
+        return np.ctypeslib.as_array((C.c_float * (B * PHOTO_FLOATS)).from_address(C.addressof(p.contents))).reshape(B, PHOTO_FLOATS)
+
+    def set_normalize(self, mean, std, clamp=True):
+        """later submits write (clamp(u) - mean) / std per channel, clamp(u) = u limited to [0, 1] when clamp (a photo stager;
+        default: mean 0, std 1, clamp off)"""
+        m, s = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+        check(self.lib.cnn_batch_stager_set_normalize(self.h, m, s, int(bool(clamp))), "cnn_batch_stager_set_normalize")
 
     def acquire(self):
         """-> (numpy view of the pinned slot to fill -- float32, or uint8 for a u8 stager --, slot index); blocks until the slot is free"""

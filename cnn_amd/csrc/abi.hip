@@ -434,6 +434,11 @@ struct Stager {
     float fill = 0.f;
     float resize_map[6] = {1, 0, 0, 0, 1, 0};  // what acquire() presets: the plain resize of the source to W x H
     std::vector<float*> mat_host, mat_dev;
+    // photo staging (cnn_batch_stager_create_u8_photo): an augmenting stager whose matrix blocks are B * 26 floats, the B * 20 of the
+    // per-sample photometric parameters behind the B * 6 of the maps (one upload); ns / nt / clamp: the normalisation of later submits
+    bool photo = false;
+    float ns[3] = {1.f, 1.f, 1.f}, nt[3] = {0.f, 0.f, 0.f};
+    int clamp = 0;
     std::vector<hipEvent_t> uploaded, consumed;
     std::vector<char> in_use;  // consumed[i] has been recorded at least once
 };
@@ -522,12 +527,17 @@ int cnn_batch_stager_create_u8(void** stager, int B, int H, int W, int depth) {
     return CNN_AMD_OK;
 }
 
-int cnn_batch_stager_create_u8_aug(void** stager, int B, int Hs, int Ws, int H, int W, int depth) {
-    CNN_REQUIRE(stager && B > 0 && B <= 8192 && depth >= 2 && depth <= 16, "cnn_batch_stager_create_u8_aug: bad arguments (B 1..8192, depth 2..16)");
+namespace {
+// what a sample's photo block is preset to: A = I, o = 0, no box -- with s = 1, t = 0, clamp off the gather rule's bits unchanged
+const float kPhotoIdentity[20] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+int create_u8_aug(void** stager, int B, int Hs, int Ws, int H, int W, int depth, bool photo) {
     float map[6];
     if (int rc = cnn_augment_matrix(nullptr, 0, Hs, Ws, H, W, map)) return rc;  // (checks the four dimensions)
     Stager* st = new Stager();
     st->aug = true;
+    st->photo = photo;
+    const size_t per_sample = photo ? 26 : 6;
     st->bytes = (size_t)B * Hs * Ws * 3;
     st->depth = depth;
     st->B = B; st->H = H; st->W = W; st->Hs = Hs; st->Ws = Ws;
@@ -540,13 +550,50 @@ int cnn_batch_stager_create_u8_aug(void** stager, int B, int Hs, int Ws, int H, 
     CNN_HIP_CHECK(hipStreamCreateWithFlags(&st->copy, hipStreamNonBlocking));
     for (int i = 0; i < depth; ++i) {
         CNN_HIP_CHECK(hipHostMalloc(&st->host[i], st->bytes, hipHostMallocDefault));
-        CNN_HIP_CHECK(hipHostMalloc((void**)&st->mat_host[i], (size_t)B * 6 * sizeof(float), hipHostMallocDefault));
+        CNN_HIP_CHECK(hipHostMalloc((void**)&st->mat_host[i], (size_t)B * per_sample * sizeof(float), hipHostMallocDefault));
         CNN_HIP_CHECK(hipMalloc(&st->dev[i], st->bytes));
-        CNN_HIP_CHECK(hipMalloc((void**)&st->mat_dev[i], (size_t)B * 6 * sizeof(float)));
+        CNN_HIP_CHECK(hipMalloc((void**)&st->mat_dev[i], (size_t)B * per_sample * sizeof(float)));
         CNN_HIP_CHECK(hipMalloc(&st->dev_f32[i], (size_t)B * 3 * H * W * sizeof(float)));
         CNN_HIP_CHECK(hipEventCreateWithFlags(&st->uploaded[i], hipEventDisableTiming));
         CNN_HIP_CHECK(hipEventCreateWithFlags(&st->consumed[i], hipEventDisableTiming));
     }
+    return CNN_AMD_OK;
+}
+}  // namespace
+
+int cnn_batch_stager_create_u8_aug(void** stager, int B, int Hs, int Ws, int H, int W, int depth) {
+    CNN_REQUIRE(stager && B > 0 && B <= 8192 && depth >= 2 && depth <= 16, "cnn_batch_stager_create_u8_aug: bad arguments (B 1..8192, depth 2..16)");
+    return create_u8_aug(stager, B, Hs, Ws, H, W, depth, false);
+}
+
+int cnn_batch_stager_create_u8_photo(void** stager, int B, int Hs, int Ws, int H, int W, int depth) {
+    CNN_REQUIRE(stager && B > 0 && B <= 8192 && depth >= 2 && depth <= 16, "cnn_batch_stager_create_u8_photo: bad arguments (B 1..8192, depth 2..16)");
+    return create_u8_aug(stager, B, Hs, Ws, H, W, depth, true);
+}
+
+int cnn_batch_stager_photo(void* stager, int slot, float** pinned) {
+    Stager* st = static_cast<Stager*>(stager);
+    CNN_REQUIRE(st && pinned && slot >= 0 && slot < st->depth, "cnn_batch_stager_photo: bad arguments");
+    CNN_REQUIRE(st->photo, "cnn_batch_stager_photo: not a photo stager (cnn_batch_stager_create_u8_photo)");
+    *pinned = st->mat_host[slot] + 6 * (size_t)st->B;
+    return CNN_AMD_OK;
+}
+
+int cnn_batch_stager_set_normalize(void* stager, const float mean[3], const float std[3], int clamp) {
+    Stager* st = static_cast<Stager*>(stager);
+    CNN_REQUIRE(st && mean && std, "cnn_batch_stager_set_normalize: null pointer");
+    CNN_REQUIRE(st->photo, "cnn_batch_stager_set_normalize: not a photo stager (cnn_batch_stager_create_u8_photo)");
+    float ns[3], nt[3];
+    for (int c = 0; c < 3; ++c) {
+        CNN_REQUIRE(mean[c] - mean[c] == 0.f && std[c] - std[c] == 0.f && std[c] != 0.f,
+                    "cnn_batch_stager_set_normalize: channel %d: mean must be finite, std finite and non-zero", c);
+        ns[c] = (float)(1.0 / (double)std[c]);
+        nt[c] = (float)(-(double)mean[c] / (double)std[c] + 0.0);  // (+ 0.0: a mean of 0 leaves -0)
+        CNN_REQUIRE(ns[c] - ns[c] == 0.f && nt[c] - nt[c] == 0.f, "cnn_batch_stager_set_normalize: channel %d: 1/std or mean/std is not finite in fp32", c);
+    }
+    memcpy(st->ns, ns, sizeof(ns));
+    memcpy(st->nt, nt, sizeof(nt));
+    st->clamp = clamp ? 1 : 0;
     return CNN_AMD_OK;
 }
 
@@ -599,6 +646,8 @@ int cnn_batch_stager_acquire(void* stager, void** pinned_host, int* slot) {
     if (st->in_use[i]) CNN_HIP_CHECK(hipEventSynchronize(st->consumed[i]));
     if (st->aug)
         for (int b = 0; b < st->B; ++b) memcpy(st->mat_host[i] + 6 * (size_t)b, st->resize_map, sizeof(st->resize_map));
+    if (st->photo)
+        for (int b = 0; b < st->B; ++b) memcpy(st->mat_host[i] + 6 * (size_t)st->B + 20 * (size_t)b, kPhotoIdentity, sizeof(kPhotoIdentity));
     *pinned_host = st->host[i];
     *slot = i;
     return CNN_AMD_OK;
@@ -609,7 +658,12 @@ int cnn_batch_stager_submit(void* stager, int slot, void** device_ptr) {
     CNN_REQUIRE(st && device_ptr && slot >= 0 && slot < st->depth, "cnn_batch_stager_submit: bad arguments");
     if (st->in_use[slot]) CNN_HIP_CHECK(hipStreamWaitEvent(st->copy, st->consumed[slot], 0));
     CNN_HIP_CHECK(hipMemcpyAsync(st->dev[slot], st->host[slot], st->bytes, hipMemcpyHostToDevice, st->copy));
-    if (st->aug) {  // bytes + per-sample maps -> the fp32 planar batch, behind both copies on the same stream
+    if (st->photo) {  // the same with the photometric epilogue: maps and photo blocks are one upload
+        CNN_HIP_CHECK(hipMemcpyAsync(st->mat_dev[slot], st->mat_host[slot], (size_t)st->B * 26 * sizeof(float), hipMemcpyHostToDevice, st->copy));
+        if (int rc = augment_u8_photo((const unsigned char*)st->dev[slot], st->B, st->Hs, st->Ws, st->mat_dev[slot], st->fill, (float*)st->dev_f32[slot],
+                                      st->H, st->W, st->mat_dev[slot] + 6 * (size_t)st->B, st->ns, st->nt, st->clamp, st->copy))
+            return rc;
+    } else if (st->aug) {  // bytes + per-sample maps -> the fp32 planar batch, behind both copies on the same stream
         CNN_HIP_CHECK(hipMemcpyAsync(st->mat_dev[slot], st->mat_host[slot], (size_t)st->B * 6 * sizeof(float), hipMemcpyHostToDevice, st->copy));
         if (int rc = cnn_augment_u8((const unsigned char*)st->dev[slot], st->B, st->Hs, st->Ws, st->mat_dev[slot], st->fill, (float*)st->dev_f32[slot],
                                     st->H, st->W, st->copy))

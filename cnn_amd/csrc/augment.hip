@@ -15,6 +15,21 @@
 // A position inside the source's pixel area reads edge-replicated taps (what a resize needs), a position outside it gives `fill` (a
 // rotation's corners: the constant border).  With fx == 0 the rule yields t00 exactly, so the identity, flips, integer shifts and
 // quarter turns are bit-identical to the plain conversion of the permuted image.  There is no antialiasing: a large shrink ratio aliases.
+//
+// The photometric epilogue (the kPhoto instantiations, reached through a photo stager only: cnn_batch_stager_create_u8_photo; restated in
+// NumPy by tests/photo_ref.py, bit for bit as well).  Sample b has 20 floats p[b][0..19], the stager has s[3], t[3] and a clamp flag.  Per
+// output pixel, behind the rule above, every product and sum rounded separately:
+//     v0,v1,v2 = the gather rule's three channel values of this pixel (inside pixels only)
+//     u_c   = ((A[c][0]*v0 + A[c][1]*v1) + A[c][2]*v2) + o[c]        A = p[0..8] row-major, o = p[9..11]
+//     u_c   = clamp ? fminf(fmaxf(u_c, 0), 1) : u_c
+//     out_c = u_c * s[c] + t[c]                                      (normalisation: s = 1/std, t = -mean/std)
+//     out_c = inside ? out_c : fill                                  (fill is in OUTPUT units: the colour stage does not touch it)
+//     ex0,ey0,ew,eh = p[12..15] (whole numbers), ev[c] = p[16..18], p[19] reserved = 0
+//     out_c = (ex0 <= x && x < ex0+ew && ey0 <= y && y < ey0+eh) ? ev[c] : out_c     (fp32 comparisons; ev in output units)
+// ew == 0 or eh == 0 is no box.  With A = I, o = 0, clamp off, s = 1, t = 0 and no box the epilogue returns the gather rule's bits: the
+// table holds finite values >= 0, so 1*v + 0*w == v, v + 0 == v and v*1 + 0 == v.  The parameters are pinned memory the caller writes
+// and are not checked: a non-finite one gives unspecified PIXELS, never an access out of bounds -- the box only selects between two
+// values per pixel (a NaN bound compares false: no box), it never forms an address.
 #include <cmath>
 #include <mutex>
 
@@ -64,6 +79,18 @@ __device__ __forceinline__ float augment_blend(float t00, float t01, float t10, 
     return top + pv;
 }
 
+// the photometric epilogue of one channel: the colour row, the clamp and the normalisation
+__device__ __forceinline__ float photo_channel(float a0, float a1, float a2, float o, float v0, float v1, float v2, bool clamp, float s, float t) {
+#pragma clang fp contract(off)
+    const float p0 = a0 * v0, p1 = a1 * v1, p2 = a2 * v2;
+    const float s01 = p0 + p1;
+    const float s012 = s01 + p2;
+    float u = s012 + o;
+    u = clamp ? fminf(fmaxf(u, 0.f), 1.f) : u;
+    const float n = u * s;
+    return n + t;
+}
+
 // the bytes of two neighbours in a row in one load at any byte address (a wave's lanes are 12 source bytes apart at best, so a load
 // instruction touches many cache lines whatever its width: the number of loads, not their bytes, is what the four-tap gather pays for)
 __device__ __forceinline__ unsigned long long load_u64(const unsigned char* p) {
@@ -80,16 +107,29 @@ __device__ __forceinline__ unsigned long long load_u64(const unsigned char* p) {
 // load that would end behind the sample starts early enough to end with it (the pixel's bytes are then shifted down: a tap begins at
 // most 5 bytes into its load).  No branch between the loads (an outside pixel's taps are clamped to pixel 0 and not used): they are
 // all in flight together.  Offsets inside one sample fit an int (8192 * 8192 * 3), the sample bases are 64-bit.
-template <bool kQuad>
+// kPhoto: the photometric epilogue on the twelve values right before the store.  The sample's 20 floats are uniform loads like the matrix
+// (`photo` is [B][20]); the stager's six and the clamp flag arrive as kernel arguments.  A pixel in the erase box counts as not inside
+// for the loads (a quad wholly in the box takes the no-load route) and gets ev[c] by a per-element select, so a box edge may cut a quad.
+struct PhotoNorm {
+    float s[3], t[3];
+    int clamp;
+};
+template <bool kQuad, bool kPhoto>
 __global__ __launch_bounds__(kBlock) void augment_u8_kernel(const unsigned char* __restrict__ src, const float* __restrict__ mats,
                                                             const float* __restrict__ lut_g, float* __restrict__ dst, int Hs, int Ws, int H,
-                                                            int W, int W4, float fill) {
+                                                            int W, int W4, float fill, const float* __restrict__ photo, PhotoNorm norm) {
     __shared__ float lut[256];
     lut[threadIdx.x] = lut_g[threadIdx.x];
     __syncthreads();
     const size_t b = blockIdx.y;
     const float* m = mats + 6 * b;
     const float m0 = m[0], m1 = m[1], m2 = m[2], m3 = m[3], m4 = m[4], m5 = m[5];
+    float pp[20];
+    if (kPhoto) {
+#pragma unroll
+        for (int k = 0; k < 20; ++k) pp[k] = photo[20 * b + k];
+    }
+    const float ex1 = kPhoto ? pp[12] + pp[14] : 0.f, ey1 = kPhoto ? pp[13] + pp[15] : 0.f;
     const unsigned char* s = src + b * 3 * ((size_t)Hs * Ws);
     const size_t plane = (size_t)H * W;
     float* d = dst + b * 3 * plane;
@@ -99,11 +139,17 @@ __global__ __launch_bounds__(kBlock) void augment_u8_kernel(const unsigned char*
     for (int q = blockIdx.x * kBlock + threadIdx.x; q < quads; q += gridDim.x * kBlock) {
         const int y = q / W4, x = (q - y * W4) * 4;
         Taps t[4];
+        bool box[4] = {false, false, false, false};
         bool any = false, whole = true;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             t[i] = augment_taps(m0, m1, m2, m3, m4, m5, x + i, y, Hs, Ws);
             t[i].inside = t[i].inside && (kQuad || x + i < W);
+            if (kPhoto) {
+                const float xf = (float)(x + i), yf = (float)y;
+                box[i] = xf >= pp[12] && xf < ex1 && yf >= pp[13] && yf < ey1;
+                t[i].inside = t[i].inside && !box[i];
+            }
             any = any || t[i].inside;
             whole = whole && (!t[i].inside || (t[i].fx == 0.f && t[i].fy == 0.f));
         }
@@ -142,6 +188,18 @@ __global__ __launch_bounds__(kBlock) void augment_u8_kernel(const unsigned char*
                                                   t[i].fx, t[i].fy);
                     v[c][i] = t[i].inside ? r : fill;
                 }
+        }
+        if (kPhoto) {
+            const bool clamp = norm.clamp != 0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float v0 = v[0][i], v1 = v[1][i], v2 = v[2][i];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float r = photo_channel(pp[3 * c], pp[3 * c + 1], pp[3 * c + 2], pp[9 + c], v0, v1, v2, clamp, norm.s[c], norm.t[c]);
+                    v[c][i] = box[i] ? pp[16 + c] : (t[i].inside ? r : fill);
+                }
+            }
         }
         float* o = d + (size_t)y * W + x;
         if (kQuad) {
@@ -198,7 +256,62 @@ Affine compose(const Affine& a, const Affine& t) {
     return r;
 }
 
+// one launch per batch; `photo` ([B][20], device) selects the kPhoto instantiations.  The callers have checked the arguments.
+int launch_augment(const unsigned char* src, int B, int Hs, int Ws, const float* mats, float fill, float* dst, int H, int W, const float* photo,
+                   const PhotoNorm& norm, hipStream_t s) {
+    const float* lut = nullptr;
+    if (int rc = device_lut(&lut)) return rc;
+    const int W4 = (W + 3) / 4;
+    const int quads = H * W4;
+    const int need = (quads + kBlock - 1) / kBlock;
+    const dim3 grid((unsigned)(need < 4096 ? need : 4096), (unsigned)B);
+    const bool quad = W % 4 == 0 && aligned16(dst);
+    if (photo) {
+        if (quad)
+            CNN_KLAUNCH(s, "augment_u8_photo", (augment_u8_kernel<true, true><<<grid, kBlock, 0, s>>>(src, mats, lut, dst, Hs, Ws, H, W, W4, fill, photo, norm)),
+                        "B=%d src=%dx%d out=%dx%d quad", B, Hs, Ws, H, W);
+        else
+            CNN_KLAUNCH(s, "augment_u8_photo", (augment_u8_kernel<false, true><<<grid, kBlock, 0, s>>>(src, mats, lut, dst, Hs, Ws, H, W, W4, fill, photo, norm)),
+                        "B=%d src=%dx%d out=%dx%d px", B, Hs, Ws, H, W);
+    } else if (quad)
+        CNN_KLAUNCH(s, "augment_u8", (augment_u8_kernel<true, false><<<grid, kBlock, 0, s>>>(src, mats, lut, dst, Hs, Ws, H, W, W4, fill, nullptr, norm)),
+                    "B=%d src=%dx%d out=%dx%d quad", B, Hs, Ws, H, W);
+    else
+        CNN_KLAUNCH(s, "augment_u8", (augment_u8_kernel<false, false><<<grid, kBlock, 0, s>>>(src, mats, lut, dst, Hs, Ws, H, W, W4, fill, nullptr, norm)),
+                    "B=%d src=%dx%d out=%dx%d px", B, Hs, Ws, H, W);
+    return CNN_AMD_OK;
+}
+
+// 3 x 4 affine colour maps in double, v[r][0..2] * rgb + v[r][3]; compose(l, a) = l after a
+struct Colour {
+    double v[3][4];
+};
+Colour compose(const Colour& l, const Colour& a) {
+    Colour r;
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) r.v[i][j] = l.v[i][0] * a.v[0][j] + l.v[i][1] * a.v[1][j] + l.v[i][2] * a.v[2][j];
+        r.v[i][3] = l.v[i][0] * a.v[0][3] + l.v[i][1] * a.v[1][3] + l.v[i][2] * a.v[2][3] + l.v[i][3];
+    }
+    return r;
+}
+
 }  // namespace
+
+namespace cnn_amd {
+int augment_u8_photo(const unsigned char* src, int B, int Hs, int Ws, const float* mats_dev, float fill, float* dst, int H, int W,
+                     const float* photo_dev, const float s[3], const float t[3], int clamp, hipStream_t stream) {
+    CNN_REQUIRE(src && mats_dev && dst && photo_dev, "augment_u8_photo: null pointer");
+    CNN_REQUIRE(B > 0 && B <= kMaxDim && dims_ok(Hs, Ws, H, W), "augment_u8_photo: B=%d source %dx%d output %dx%d (each 1..%d)", B, Hs, Ws, H, W, kMaxDim);
+    CNN_REQUIRE(std::isfinite(fill), "augment_u8_photo: fill is not finite");
+    PhotoNorm norm;
+    for (int c = 0; c < 3; ++c) {
+        norm.s[c] = s[c];
+        norm.t[c] = t[c];
+    }
+    norm.clamp = clamp ? 1 : 0;
+    return launch_augment(src, B, Hs, Ws, mats_dev, fill, dst, H, W, photo_dev, norm, stream);
+}
+}  // namespace cnn_amd
 
 extern "C" {
 
@@ -206,20 +319,7 @@ int cnn_augment_u8(const unsigned char* src, int B, int Hs, int Ws, const float*
     CNN_REQUIRE(src && matrices_dev && dst, "cnn_augment_u8: null pointer");
     CNN_REQUIRE(B > 0 && B <= kMaxDim && dims_ok(Hs, Ws, H, W), "cnn_augment_u8: B=%d source %dx%d output %dx%d (each 1..%d)", B, Hs, Ws, H, W, kMaxDim);
     CNN_REQUIRE(std::isfinite(fill), "cnn_augment_u8: fill is not finite");
-    const float* lut = nullptr;
-    if (int rc = device_lut(&lut)) return rc;
-    hipStream_t s = as_stream(stream);
-    const int W4 = (W + 3) / 4;
-    const int quads = H * W4;
-    const int need = (quads + kBlock - 1) / kBlock;
-    const dim3 grid((unsigned)(need < 4096 ? need : 4096), (unsigned)B);
-    if (W % 4 == 0 && aligned16(dst))
-        CNN_KLAUNCH(s, "augment_u8", (augment_u8_kernel<true><<<grid, kBlock, 0, s>>>(src, matrices_dev, lut, dst, Hs, Ws, H, W, W4, fill)),
-                    "B=%d src=%dx%d out=%dx%d quad", B, Hs, Ws, H, W);
-    else
-        CNN_KLAUNCH(s, "augment_u8", (augment_u8_kernel<false><<<grid, kBlock, 0, s>>>(src, matrices_dev, lut, dst, Hs, Ws, H, W, W4, fill)),
-                    "B=%d src=%dx%d out=%dx%d px", B, Hs, Ws, H, W);
-    return CNN_AMD_OK;
+    return launch_augment(src, B, Hs, Ws, matrices_dev, fill, dst, H, W, nullptr, PhotoNorm(), as_stream(stream));
 }
 
 // Host only.  The ops transform a canvas that starts as the source, in order, the way ImageAugmentor::make_augment transforms its cv::Mat;
@@ -278,6 +378,74 @@ int cnn_augment_matrix(const cnn_augment_op* ops, int n_ops, int Hs, int Ws, int
     for (int i = 0; i < 6; ++i) {
         m[i] = (float)(a.v[i / 3][i % 3] + 0.0);  // (+ 0.0: a product such as 0 * -1 leaves -0)
         CNN_REQUIRE(std::isfinite(m[i]), "cnn_augment_matrix: the composed map is not finite");
+    }
+    return CNN_AMD_OK;
+}
+
+// Host only.  Each op is an affine map of the colour vector; they apply in order (op 0 first), with no clamp between them.  Composed in
+// double, rounded to fp32 once: out[0..8] = A row-major, out[9..11] = o (the first twelve floats of a sample's photo block).
+int cnn_colour_matrix(const cnn_colour_op* ops, int n_ops, float out[12]) {
+    CNN_REQUIRE(out != nullptr && n_ops >= 0 && (ops != nullptr || n_ops == 0), "cnn_colour_matrix: null pointer");
+    static const double kGray[3] = {0.299, 0.587, 0.114};
+    // RGB -> YIQ; the rows of I and Q sum to zero, so the grey axis is the Y axis
+    static const double kYiq[3][3] = {{0.299, 0.587, 0.114}, {0.5959, -0.2746, -0.3213}, {0.2115, -0.5227, 0.3112}};
+    Colour a = {{{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}}};
+    for (int i = 0; i < n_ops; ++i) {
+        const cnn_colour_op& op = ops[i];
+        const double f = op.a;
+        Colour l = {{{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}}};
+        CNN_REQUIRE(op.kind >= CNN_COL_BRIGHTNESS && op.kind <= CNN_COL_HUE, "cnn_colour_matrix: op %d: unknown kind %d", i, op.kind);
+        CNN_REQUIRE(std::isfinite(f), "cnn_colour_matrix: op %d: argument is not finite", i);
+        switch (op.kind) {
+        case CNN_COL_BRIGHTNESS:
+            for (int r = 0; r < 3; ++r) l.v[r][r] = f;
+            break;
+        case CNN_COL_CONTRAST: {
+            const double pivot = op.b;
+            CNN_REQUIRE(std::isfinite(pivot), "cnn_colour_matrix: op %d: pivot is not finite", i);
+            for (int r = 0; r < 3; ++r) {
+                l.v[r][r] = f;
+                l.v[r][3] = (1 - f) * pivot;
+            }
+            break;
+        }
+        case CNN_COL_SATURATION:
+            for (int r = 0; r < 3; ++r)
+                for (int c = 0; c < 3; ++c) l.v[r][c] = (r == c ? f : 0.0) + (1 - f) * kGray[c];
+            break;
+        default: {  // CNN_COL_HUE: I' = c*I - s*Q, Q' = s*I + c*Q, Y kept.  L = I + (c - 1) * P + s * K: the identity exactly at c = 1, s = 0
+            double c, s;
+            if (std::fmod(f, 90.0) == 0.0) {  // quarter turns: sine and cosine from a table (360 degrees is 0 degrees exactly)
+                static const double kCos[4] = {1, 0, -1, 0}, kSin[4] = {0, 1, 0, -1};
+                const int k = (int)std::fmod(std::fmod(f / 90.0, 4.0) + 4.0, 4.0);
+                c = kCos[k]; s = kSin[k];
+            } else {
+                const double rad = f * 3.14159265358979323846 / 180.0;
+                c = std::cos(rad); s = std::sin(rad);
+            }
+            const double (&t)[3][3] = kYiq;
+            const double det = t[0][0] * (t[1][1] * t[2][2] - t[1][2] * t[2][1]) - t[0][1] * (t[1][0] * t[2][2] - t[1][2] * t[2][0]) +
+                               t[0][2] * (t[1][0] * t[2][1] - t[1][1] * t[2][0]);
+            double inv[3][3];  // YIQ -> RGB: the inverse of the table, not the rounded textbook constants
+            for (int r = 0; r < 3; ++r)
+                for (int q = 0; q < 3; ++q) {
+                    const int r1 = (r + 1) % 3, r2 = (r + 2) % 3, q1 = (q + 1) % 3, q2 = (q + 2) % 3;
+                    inv[r][q] = (t[q1][r1] * t[q2][r2] - t[q1][r2] * t[q2][r1]) / det;
+                }
+            for (int r = 0; r < 3; ++r)
+                for (int q = 0; q < 3; ++q) {
+                    const double p = inv[r][1] * t[1][q] + inv[r][2] * t[2][q];   // the projection on the chroma plane
+                    const double k = inv[r][2] * t[1][q] - inv[r][1] * t[2][q];   // a quarter turn in it
+                    l.v[r][q] = (r == q ? 1.0 : 0.0) + ((c - 1) * p + s * k);
+                }
+            break;
+        }
+        }
+        a = compose(l, a);
+    }
+    for (int i = 0; i < 12; ++i) {
+        out[i] = (float)((i < 9 ? a.v[i / 3][i % 3] : a.v[i - 9][3]) + 0.0);  // (+ 0.0: a product such as 0 * -1 leaves -0)
+        CNN_REQUIRE(std::isfinite(out[i]), "cnn_colour_matrix: the composed map is not finite");
     }
     return CNN_AMD_OK;
 }

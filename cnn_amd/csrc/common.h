@@ -439,4 +439,9 @@ inline unsigned stream_grid(size_t work_items, int block) {
     return (unsigned)(need < 1 ? 1 : (need > cap ? cap : need));
 }
 
+// augment.hip: cnn_augment_u8 with the photometric epilogue (include/cnn_amd.h), for the photo stager's submit() in abi.hip -- no export
+// of its own.  photo_dev: [B][20] device floats; s, t, clamp: the stager's normalisation.  Same argument checks as cnn_augment_u8.
+int augment_u8_photo(const unsigned char* src, int B, int Hs, int Ws, const float* mats_dev, float fill, float* dst, int H, int W,
+                     const float* photo_dev, const float s[3], const float t[3], int clamp, hipStream_t stream);
+
 }  // namespace cnn_amd

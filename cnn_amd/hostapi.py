@@ -163,6 +163,56 @@ def augment_params(rng, B, Hs, Ws, H, W, hflip=0.5, vflip=0.2, crop=0.7, rotate=
     return out
 
 
+def photo_params(rng, B, H, W, brightness=0.4, contrast=0.4, saturation=0.4, hue=0.0, pivot=0.5, erase_prob=0.25, erase_area=(0.02, 1 / 3),
+                 erase_aspect=(0.3, 3.3), erase_value="const"):
+    """One batch's photometric parameters for an H x W output, sampled on the host with `rng` (a numpy.random.Generator).  Returns a
+    (B, 20) float32 array for BatchStager.photo(slot): A[9], o[3], ex0, ey0, ew, eh, ev[3], 0.
+
+    Colour follows torchvision's ColorJitter sampling: per sample the four ops in a shuffled order; brightness, contrast and saturation
+    factors uniform in [max(0, 1 - a), 1 + a]; hue uniform in [-hue, hue] as a fraction of the colour wheel (at most 0.5; 360 degrees
+    times it).  An amplitude of 0 leaves its op out.  Composition goes through capi.colour_matrix: contrast pivots on the fixed `pivot`
+    (not the image's mean grey), hue is the linear YIQ rotation (not the HSV shift), and nothing clamps between the ops.
+
+    Erasing follows timm's RandomErasing sampling: with probability erase_prob, up to 10 attempts of an area fraction uniform in
+    erase_area and an aspect ratio log-uniform in erase_aspect, h = round(sqrt(area * aspect)), w = round(sqrt(area / aspect)); the
+    first box with 1 <= w < W and 1 <= h < H is placed at a uniform position where it fits; no fitting attempt, no box.  The box's
+    value is in OUTPUT units (behind the normalisation): "const" is 0, "rand" draws one standard normal value per channel here on the
+    host.  Per-pixel noise (timm's mode="pixel") is out of scope: the kernel writes one value per channel and box."""
+    if erase_value not in ("const", "rand"):
+        raise capi.CnnAmdError('photo_params: erase_value is "const" or "rand"')
+    if not 0.0 <= hue <= 0.5:
+        raise capi.CnnAmdError("photo_params: hue is a fraction of the colour wheel, 0 .. 0.5")
+    amps = {capi.COL_BRIGHTNESS: brightness, capi.COL_CONTRAST: contrast, capi.COL_SATURATION: saturation, capi.COL_HUE: hue}
+    kinds = np.array(sorted(amps))
+    out = np.zeros((B, capi.PHOTO_FLOATS), dtype=np.float32)
+    log_aspect = (np.log(erase_aspect[0]), np.log(erase_aspect[1]))
+    for b in range(B):
+        ops = []
+        for kind in rng.permutation(kinds):
+            a = float(amps[int(kind)])
+            if a == 0.0:
+                continue
+            if kind == capi.COL_HUE:
+                ops.append((capi.COL_HUE, 360.0 * float(rng.uniform(-a, a))))
+            elif kind == capi.COL_CONTRAST:
+                ops.append((capi.COL_CONTRAST, float(rng.uniform(max(0.0, 1.0 - a), 1.0 + a)), float(pivot)))
+            else:
+                ops.append((int(kind), float(rng.uniform(max(0.0, 1.0 - a), 1.0 + a))))
+        out[b, :12] = capi.colour_matrix(ops)
+        if not float(rng.random()) < erase_prob:
+            continue
+        for _ in range(10):
+            target = float(rng.uniform(erase_area[0], erase_area[1])) * H * W
+            aspect = float(np.exp(rng.uniform(log_aspect[0], log_aspect[1])))
+            h, w = int(round(np.sqrt(target * aspect))), int(round(np.sqrt(target / aspect)))
+            if 1 <= w < W and 1 <= h < H:
+                out[b, 12:16] = (int(rng.integers(0, W - w + 1)), int(rng.integers(0, H - h + 1)), w, h)
+                if erase_value == "rand":
+                    out[b, 16:19] = rng.standard_normal(3)
+                break
+    return out
+
+
 class HostNet:
     """architectures::Sequential / AlexNet (cnn_amd/host) behind a handle: the C++ Layer API a reference user links against."""
 

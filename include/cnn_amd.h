@@ -789,8 +789,8 @@ int cnn_batch_stager_release(void* stager, int slot, void* stream);
 
 /* ---- geometric augmentation of uint8 batches on the device (an addition: ImageAugmentor, pipeline.cpp:40-77, runs OpenCV on the host).
  * Flip, crop, rotate and the resize to the network's size are ONE affine map per sample; one kernel gathers through it while it does the
- * stager's bytes -> fp32 planar conversion.  Decode, colour jitter and normalisation are not covered, and there is no antialiasing: a
- * large shrink ratio aliases.
+ * stager's bytes -> fp32 planar conversion.  Decode is not covered, and there is no antialiasing: a large shrink ratio aliases.  Colour
+ * jitter, normalisation and erasing: the photo stager below.
  * The rule.  Input: interleaved bytes [B][Hs][Ws][3]; output: planar fp32 [B][3][H][W].  Sample b has six floats m[b][0..5] that map
  * OUTPUT pixel indices to SOURCE pixel indices.  Per output pixel (x, y), all in fp32, every product and sum rounded separately:
  *     sx = (m0*x + m1*y) + m2            sy = (m3*x + m4*y) + m5
@@ -830,6 +830,50 @@ int cnn_augment_matrix(const cnn_augment_op* ops, int n_ops, int Hs, int Ws, int
 int cnn_batch_stager_create_u8_aug(void** stager, int B, int Hs, int Ws, int H, int W, int depth);
 int cnn_batch_stager_matrices(void* stager, int slot, float** pinned /* [B][6] */);
 int cnn_batch_stager_set_fill(void* stager, float fill);
+
+/* ---- the photometric half on the device: colour jitter, mean / std normalisation and random erasing in the same kernel, on the three
+ * channel values of an output pixel right before the store (no extra pass over memory).  Reached through a photo stager only.
+ * The rule.  Sample b has 20 floats p[b][0..19]; the stager has s[3], t[3] and a clamp flag.  Per output pixel (x, y), behind the gather
+ * rule above, all in fp32, every product and sum rounded separately:
+ *     v0,v1,v2 = the gather rule's three channel values of this pixel (inside pixels only)
+ *     u_c   = ((A[c][0]*v0 + A[c][1]*v1) + A[c][2]*v2) + o[c]        A = p[0..8] row-major, o = p[9..11]
+ *     u_c   = clamp ? fminf(fmaxf(u_c, 0), 1) : u_c
+ *     out_c = u_c * s[c] + t[c]                                      (normalisation: s = 1/std, t = -mean/std)
+ *     out_c = inside ? out_c : fill                                  (fill is in OUTPUT units: the colour stage does not touch it)
+ *     ex0,ey0,ew,eh = p[12..15] (whole numbers), ev[c] = p[16..18], p[19] reserved = 0
+ *     out_c = (ex0 <= x && x < ex0+ew && ey0 <= y && y < ey0+eh) ? ev[c] : out_c     (fp32 comparisons; ev in output units)
+ * ew == 0 or eh == 0 is no box; a box that runs past the output is clipped by the comparisons.  One box per sample, one value per
+ * channel: per-pixel noise is not covered.  With A = I, o = 0, clamp off, s = 1, t = 0 and no box the rule returns the gather rule's
+ * bits unchanged (the table holds finite values >= 0: 1*v + 0*w == v).  tests/photo_ref.py restates the rule in NumPy; the kernel equals
+ * it bit for bit.  The parameters are pinned memory the caller writes and cannot be checked: a non-finite one gives unspecified pixels,
+ * never an access out of bounds.
+ * cnn_batch_stager_create_u8_photo: an augmenting stager (cnn_batch_stager_matrices and _set_fill work on it) whose slots carry a pinned
+ * [B][20] block as well; acquire() presets it to the identity above, cnn_batch_stager_photo() hands it out to overwrite between
+ * acquire() and submit(), submit() uploads it with the matrices and runs the kernel on the stager's stream in front of the event wait()
+ * waits for.  cnn_batch_stager_set_normalize: s = 1/std and t = -mean/std of LATER submits, computed in double and rounded once; std
+ * finite and non-zero, mean finite; clamp != 0 turns the clamp to [0, 1] on.  Default: s = 1, t = 0, clamp off.  Both return
+ * CNN_AMD_E_BADARG on a stager of the other kinds. */
+int cnn_batch_stager_create_u8_photo(void** stager, int B, int Hs, int Ws, int H, int W, int depth);
+int cnn_batch_stager_photo(void* stager, int slot, float** pinned /* [B][20] */);
+int cnn_batch_stager_set_normalize(void* stager, const float mean[3], const float std[3], int clamp);
+/* cnn_colour_matrix composes A and o on the host (no GPU call): out[0..8] = A row-major, out[9..11] = o, the first twelve floats of a
+ * sample's block.  The ops apply in order to a colour x in [0, 1]^3, each an affine map, composed in double and rounded to fp32 once:
+ *   CNN_COL_BRIGHTNESS  a = f          x * f
+ *   CNN_COL_CONTRAST    a = f, b = pivot   f * x + (1 - f) * pivot.  The pivot is FIXED (0.5, or the dataset's mean grey): torchvision's
+ *                       ColorJitter uses the mean grey of each image, which would need a second pass over it.
+ *   CNN_COL_SATURATION  a = f          f * x + (1 - f) * gray(x), gray = 0.299 r + 0.587 g + 0.114 b
+ *   CNN_COL_HUE         a = degrees    a rotation about the grey axis in YIQ (I' = cos*I - sin*Q, Q' = sin*I + cos*Q): the LINEAR form of
+ *                       a hue shift, not torchvision's HSV one (they agree on saturated primaries' direction, not in value).
+ *                       Multiples of 90 degrees take sine and cosine from a table: 360 is 0 exactly.
+ * There is NO clamp between the ops, only the one clamp of the kernel behind the whole map: where torchvision clamps after every op, a
+ * value that leaves [0, 1] in between comes back differently here.  n_ops == 0 gives I and 0.  Rejected: unknown kinds, non-finite
+ * arguments, a composed map that is not finite. */
+enum { CNN_COL_BRIGHTNESS = 1, CNN_COL_CONTRAST = 2, CNN_COL_SATURATION = 3, CNN_COL_HUE = 4 };
+typedef struct cnn_colour_op {
+    int kind;
+    float a, b;
+} cnn_colour_op;
+int cnn_colour_matrix(const cnn_colour_op* ops, int n_ops, float out[12]);
 
 /* page-locked host memory (async H2D / D2H copies are only asynchronous from / to pinned buffers) */
 int cnn_host_alloc_pinned(void** ptr, size_t bytes);
