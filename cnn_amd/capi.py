@@ -183,6 +183,14 @@ SIGNATURES = {
     "cnn_batch_stager_photo": (C.c_int, [_P, C.c_int, C.POINTER(C.POINTER(C.c_float))]),
     "cnn_batch_stager_set_normalize": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int]),
     "cnn_colour_matrix": (C.c_int, [C.POINTER(ColourOp), C.c_int, C.POINTER(C.c_float)]),
+    "cnn_dataset_create_u8": (C.c_int, [C.POINTER(C.c_void_p), C.c_longlong, C.c_int, C.c_int]),
+    "cnn_dataset_write": (C.c_int, [_P, C.c_longlong, C.c_longlong, _P, _P]),
+    "cnn_dataset_read": (C.c_int, [_P, C.c_longlong, C.c_longlong, _P, _P]),
+    "cnn_dataset_info": (C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "cnn_dataset_destroy": (C.c_int, [_P]),
+    "cnn_batch_stager_create_u8_resident": (C.c_int, [C.POINTER(C.c_void_p), _P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "cnn_batch_stager_indices": (C.c_int, [_P, C.c_int, C.POINTER(C.POINTER(C.c_int))]),
+    "cnn_batch_stager_labels": (C.c_int, [_P, C.c_int, C.POINTER(C.POINTER(C.c_int))]),
     "cnn_linear_forward": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "cnn_linear_backward": (C.c_int, [_P] * 6 + [C.c_int] * 3 + [C.c_float, _P]),
     "cnn_linear_backward_relu": (C.c_int, [_P] * 6 + [C.c_int] * 3 + [C.c_float, _P]),
@@ -1157,24 +1165,87 @@ def side_stream_join():
     check(load().cnn_amd_side_stream_join(_stream()), "cnn_amd_side_stream_join")
 
 
+class ResidentDataset:
+    """cnn_dataset_*: N images of Hs x Ws x 3 bytes and N int32 labels in device memory (bytes 0 and labels -1 until written); the source
+    of BatchStager(u8_shape=..., resident=ds).  Close the stagers before the dataset."""
+
+    def __init__(self, N, Hs, Ws):
+        self.lib = load()
+        self.h = C.c_void_p()
+        check(self.lib.cnn_dataset_create_u8(C.byref(self.h), int(N), int(Hs), int(Ws)), "cnn_dataset_create_u8")
+        self.N, self.Hs, self.Ws = int(N), int(Hs), int(Ws)
+
+    def write(self, first, images_u8=None, labels=None):
+        """samples first .. first + count - 1: images_u8 uint8 (count, Hs, Ws, 3) and / or labels int32 (count,), host arrays; blocks.
+        Waits first for every gather the attached stagers have submitted"""
+        import numpy as np
+
+        if images_u8 is None and labels is None:
+            raise CnnAmdError("ResidentDataset.write: images_u8 and labels are both None")
+        count = None
+        if images_u8 is not None:
+            images_u8 = np.ascontiguousarray(images_u8, dtype=np.uint8)
+            if images_u8.ndim != 4 or images_u8.shape[1:] != (self.Hs, self.Ws, 3):
+                raise CnnAmdError(f"ResidentDataset.write: images must be uint8 (count, {self.Hs}, {self.Ws}, 3)")
+            count = images_u8.shape[0]
+        if labels is not None:
+            labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+            if count is not None and labels.size != count:
+                raise CnnAmdError("ResidentDataset.write: as many labels as images")
+            count = labels.size
+        check(self.lib.cnn_dataset_write(self.h, int(first), int(count), images_u8.ctypes.data_as(C.c_void_p) if images_u8 is not None else None,
+                                         labels.ctypes.data_as(C.c_void_p) if labels is not None else None), "cnn_dataset_write")
+
+    def read(self, first, count):
+        """-> (uint8 (count, Hs, Ws, 3), int32 (count,)) of samples first .. first + count - 1; blocks"""
+        import numpy as np
+
+        count = int(count)
+        images, labels = np.empty((max(count, 0), self.Hs, self.Ws, 3), np.uint8), np.empty(max(count, 0), np.int32)
+        check(self.lib.cnn_dataset_read(self.h, int(first), count, images.ctypes.data_as(C.c_void_p), labels.ctypes.data_as(C.c_void_p)),
+              "cnn_dataset_read")
+        return images, labels
+
+    def info(self):
+        """-> (N, Hs, Ws) as the library holds them"""
+        n, hs, ws = C.c_longlong(), C.c_int(), C.c_int()
+        check(self.lib.cnn_dataset_info(self.h, C.byref(n), C.byref(hs), C.byref(ws)), "cnn_dataset_info")
+        return int(n.value), int(hs.value), int(ws.value)
+
+    def close(self):
+        """cnn_dataset_destroy; raises while a stager is attached (and the dataset stays as it is)"""
+        if self.h:
+            check(self.lib.cnn_dataset_destroy(self.h), "cnn_dataset_destroy")
+            self.h = None
+
+
 class BatchStager:
     """cnn_batch_stager_*: `depth` pinned host slots + device buffers, uploads on a copy stream of its own, ordered by events"""
 
-    def __init__(self, batch_bytes=None, depth=2, u8_shape=None, source_shape=None, augment=False, photo=False):
+    def __init__(self, batch_bytes=None, depth=2, u8_shape=None, source_shape=None, augment=False, photo=False, resident=None):
         """u8_shape=(B, H, W): the slots hold interleaved BYTES [B][H][W][3] (cv::Mat CV_8UC3), submit() returns the fp32 planar batch
         the stager's conversion kernel writes (cnn_batch_stager_create_u8).  augment=True or source_shape=(Hs, Ws): the slots hold
         [B][Hs][Ws][3] bytes (Hs, Ws = H, W when source_shape is None) and per-sample maps, matrices(slot); submit() returns the
         [B][3][H][W] batch cnn_augment_u8 writes through them (cnn_batch_stager_create_u8_aug).  photo=True: an augmenting stager
         whose slots also carry (B, 20) photometric parameters, photo(slot) -- colour matrix, erase box -- and whose kernel applies them
-        and set_normalize()'s mean / std behind the gather (cnn_batch_stager_create_u8_photo)"""
+        and set_normalize()'s mean / std behind the gather (cnn_batch_stager_create_u8_photo).  resident=ds (a ResidentDataset): a
+        photo stager whose images are gathered out of ds by the slot's indices(slot); acquire() returns (None, slot), labels(slot) is
+        the device pointer of the gathered labels (cnn_batch_stager_create_u8_resident)"""
         self.lib = load()
         self.h = C.c_void_p()
         self.u8 = u8_shape is not None
-        self.is_photo = bool(photo)
+        self.resident = resident
+        self.is_photo = bool(photo) or resident is not None
         self.aug = bool(augment) or source_shape is not None or self.is_photo
         if self.aug and not self.u8:
             raise CnnAmdError("BatchStager: augment / source_shape need u8_shape=(B, H, W)")
-        if self.aug:
+        if resident is not None:
+            if source_shape is not None:
+                raise CnnAmdError("BatchStager: a resident stager's source shape is its dataset's")
+            B, H, W = (int(v) for v in u8_shape)
+            self.B, self.H, self.W, self.bytes = B, H, W, 0
+            check(self.lib.cnn_batch_stager_create_u8_resident(C.byref(self.h), resident.h, B, H, W, depth), "cnn_batch_stager_create_u8_resident")
+        elif self.aug:
             B, H, W = (int(v) for v in u8_shape)
             Hs, Ws = (H, W) if source_shape is None else (int(v) for v in source_shape)
             self.B, self.bytes = B, B * Hs * Ws * 3
@@ -1212,6 +1283,22 @@ class BatchStager:
         B = getattr(self, "B", 0)
         return np.ctypeslib.as_array((C.c_float * (B * PHOTO_FLOATS)).from_address(C.addressof(p.contents))).reshape(B, PHOTO_FLOATS)
 
+    def indices(self, slot):
+        """-> numpy (B,) int32 view of the slot's pinned sample indices (a resident stager; acquire() preset them to -1: no sample)"""
+        import numpy as np
+
+        p = C.POINTER(C.c_int)()
+        check(self.lib.cnn_batch_stager_indices(self.h, int(slot), C.byref(p)), "cnn_batch_stager_indices")
+        B = getattr(self, "B", 0)
+        return np.ctypeslib.as_array((C.c_int * B).from_address(C.addressof(p.contents)))
+
+    def labels(self, slot):
+        """-> device pointer (int) of the slot's int32 [B] labels (a resident stager): labels[idx], -1 where idx is -1; valid behind
+        wait(slot) and until release(slot)"""
+        p = C.POINTER(C.c_int)()
+        check(self.lib.cnn_batch_stager_labels(self.h, int(slot), C.byref(p)), "cnn_batch_stager_labels")
+        return C.cast(p, C.c_void_p).value
+
     def set_normalize(self, mean, std, clamp=True):
         """later submits write (clamp(u) - mean) / std per channel, clamp(u) = u limited to [0, 1] when clamp (a photo stager;
         default: mean 0, std 1, clamp off)"""
@@ -1224,6 +1311,8 @@ class BatchStager:
 
         host, slot = C.c_void_p(), C.c_int()
         check(self.lib.cnn_batch_stager_acquire(self.h, C.byref(host), C.byref(slot)), "cnn_batch_stager_acquire")
+        if self.resident is not None:  # (no pinned image block: the images are in the dataset)
+            return None, slot.value
         if self.u8:
             return np.ctypeslib.as_array((C.c_ubyte * self.bytes).from_address(host.value)), slot.value
         buf = (C.c_float * (self.bytes // 4)).from_address(host.value)

@@ -439,8 +439,24 @@ struct Stager {
     bool photo = false;
     float ns[3] = {1.f, 1.f, 1.f}, nt[3] = {0.f, 0.f, 0.f};
     int clamp = 0;
+    // resident staging (cnn_batch_stager_create_u8_resident): a photo stager whose source is `ds`; `host` / `dev` stay null, a slot's
+    // pinned block `idx_host` is B indices followed by the B * 26 floats (`mat_host` points behind the indices, so the photo stager's
+    // accessors and presets work on it as they are), `idx_dev` its device copy, `lab_dev` the labels the kernel gathers beside the batch
+    struct Dataset* ds = nullptr;
+    std::vector<int*> idx_host, idx_dev, lab_dev;
     std::vector<hipEvent_t> uploaded, consumed;
     std::vector<char> in_use;  // consumed[i] has been recorded at least once
+};
+
+// cnn_dataset_create_u8: N images of Hs x Ws x 3 bytes and N labels on `device`; `stagers` (under `mu`): the resident stagers attached
+struct Dataset {
+    long long N = 0;
+    int Hs = 0, Ws = 0, device = 0;
+    size_t sample_bytes = 0;
+    unsigned char* images = nullptr;
+    int* labels = nullptr;
+    std::mutex mu;
+    std::vector<Stager*> stagers;
 };
 
 // Tensor3D::read_from_opencv_mat (data_format.cpp:13-23) for a whole batch: interleaved bytes [B][H*W][3] -> planar fp32 [B][3][H*W].
@@ -614,10 +630,159 @@ int cnn_batch_stager_set_fill(void* stager, float fill) {
     return CNN_AMD_OK;
 }
 
+// ---- the device-resident dataset and its stager ----------------------------------------------------------------------------------
+int cnn_dataset_create_u8(void** dataset, long long N, int Hs, int Ws) {
+    CNN_REQUIRE(dataset != nullptr, "cnn_dataset_create_u8: null pointer");
+    CNN_REQUIRE(N >= 1 && N <= 2147483647LL && Hs >= 1 && Hs <= 8192 && Ws >= 1 && Ws <= 8192,
+                "cnn_dataset_create_u8: N=%lld (1..2^31-1) images of %dx%d (each 1..8192)", N, Hs, Ws);
+    int dev = 0;
+    CNN_HIP_CHECK(hipGetDevice(&dev));
+    Dataset* ds = new Dataset();
+    ds->N = N; ds->Hs = Hs; ds->Ws = Ws; ds->device = dev;
+    ds->sample_bytes = (size_t)Hs * Ws * 3;
+    const size_t bytes = (size_t)N * ds->sample_bytes;
+    hipError_t e = hipMalloc((void**)&ds->images, bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&ds->labels, (size_t)N * sizeof(int));
+    if (e == hipSuccess) e = hipMemset(ds->images, 0, bytes);
+    if (e == hipSuccess) e = hipMemset(ds->labels, 0xFF, (size_t)N * sizeof(int));  // every label -1
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        if (ds->images) (void)hipFree(ds->images);
+        if (ds->labels) (void)hipFree(ds->labels);
+        delete ds;
+        return fail(CNN_AMD_E_HIP + (int)e, "cnn_dataset_create_u8: %zu bytes of images and %lld labels: %s", bytes, N, hipGetErrorString(e));
+    }
+    *dataset = ds;
+    return CNN_AMD_OK;
+}
+
+namespace {
+int dataset_range(const char* who, Dataset* ds, long long first, long long count, const void* images, const void* labels) {
+    CNN_REQUIRE(ds != nullptr, "%s: null dataset", who);
+    CNN_REQUIRE(count > 0 && first >= 0 && first < ds->N && count <= ds->N - first, "%s: samples [%lld, %lld + %lld) outside [0, %lld)", who, first, first,
+                count, ds->N);
+    CNN_REQUIRE(images != nullptr || labels != nullptr, "%s: images and labels are both null", who);
+    return CNN_AMD_OK;
+}
+}  // namespace
+
+int cnn_dataset_write(void* dataset, long long first, long long count, const unsigned char* images, const int* labels) {
+    Dataset* ds = static_cast<Dataset*>(dataset);
+    if (int rc = dataset_range("cnn_dataset_write", ds, first, count, images, labels)) return rc;
+    std::lock_guard<std::mutex> lk(ds->mu);
+    for (Stager* st : ds->stagers) CNN_HIP_CHECK(hipStreamSynchronize(st->copy));  // every submitted gather has read its bytes
+    if (images) CNN_HIP_CHECK(hipMemcpy(ds->images + (size_t)first * ds->sample_bytes, images, (size_t)count * ds->sample_bytes, hipMemcpyHostToDevice));
+    if (labels) CNN_HIP_CHECK(hipMemcpy(ds->labels + first, labels, (size_t)count * sizeof(int), hipMemcpyHostToDevice));
+    CNN_HIP_CHECK(hipStreamSynchronize(nullptr));  // (a copy out of pageable memory may return once it is staged)
+    return CNN_AMD_OK;
+}
+
+int cnn_dataset_read(void* dataset, long long first, long long count, unsigned char* images, int* labels) {
+    Dataset* ds = static_cast<Dataset*>(dataset);
+    if (int rc = dataset_range("cnn_dataset_read", ds, first, count, images, labels)) return rc;
+    std::lock_guard<std::mutex> lk(ds->mu);
+    if (images) CNN_HIP_CHECK(hipMemcpy(images, ds->images + (size_t)first * ds->sample_bytes, (size_t)count * ds->sample_bytes, hipMemcpyDeviceToHost));
+    if (labels) CNN_HIP_CHECK(hipMemcpy(labels, ds->labels + first, (size_t)count * sizeof(int), hipMemcpyDeviceToHost));
+    return CNN_AMD_OK;
+}
+
+int cnn_dataset_info(void* dataset, long long* N, int* Hs, int* Ws) {
+    Dataset* ds = static_cast<Dataset*>(dataset);
+    CNN_REQUIRE(ds != nullptr && (N != nullptr || Hs != nullptr || Ws != nullptr), "cnn_dataset_info: null pointer");
+    if (N) *N = ds->N;
+    if (Hs) *Hs = ds->Hs;
+    if (Ws) *Ws = ds->Ws;
+    return CNN_AMD_OK;
+}
+
+int cnn_dataset_destroy(void* dataset) {
+    Dataset* ds = static_cast<Dataset*>(dataset);
+    CNN_REQUIRE(ds != nullptr, "cnn_dataset_destroy: null dataset");
+    {
+        std::lock_guard<std::mutex> lk(ds->mu);
+        CNN_REQUIRE(ds->stagers.empty(), "cnn_dataset_destroy: %zu stager(s) still attached (cnn_batch_stager_destroy them first)", ds->stagers.size());
+    }
+    (void)hipFree(ds->images);
+    (void)hipFree(ds->labels);
+    delete ds;
+    return CNN_AMD_OK;
+}
+
+int cnn_batch_stager_create_u8_resident(void** stager, void* dataset, int B, int H, int W, int depth) {
+    Dataset* ds = static_cast<Dataset*>(dataset);
+    CNN_REQUIRE(stager && ds && B > 0 && B <= 8192 && depth >= 2 && depth <= 16,
+                "cnn_batch_stager_create_u8_resident: bad arguments (a dataset, B 1..8192, depth 2..16)");
+    int dev = 0;
+    CNN_HIP_CHECK(hipGetDevice(&dev));
+    CNN_REQUIRE(dev == ds->device, "cnn_batch_stager_create_u8_resident: the dataset lives on device %d, the current device is %d", ds->device, dev);
+    float map[6];
+    if (int rc = cnn_augment_matrix(nullptr, 0, ds->Hs, ds->Ws, H, W, map)) return rc;  // (checks H and W)
+    Stager* st = new Stager();
+    st->aug = st->photo = true;
+    st->ds = ds;
+    st->depth = depth;
+    st->B = B; st->H = H; st->W = W; st->Hs = ds->Hs; st->Ws = ds->Ws;
+    memcpy(st->resize_map, map, sizeof(map));
+    st->host.assign(depth, nullptr); st->dev.assign(depth, nullptr); st->dev_f32.assign(depth, nullptr);
+    st->mat_host.assign(depth, nullptr); st->mat_dev.assign(depth, nullptr);
+    st->idx_host.assign(depth, nullptr); st->idx_dev.assign(depth, nullptr); st->lab_dev.assign(depth, nullptr);
+    st->uploaded.assign(depth, nullptr); st->consumed.assign(depth, nullptr);
+    st->in_use.assign(depth, 0);
+    *stager = st;
+    CNN_HIP_CHECK(hipStreamCreateWithFlags(&st->copy, hipStreamNonBlocking));
+    const size_t block = (size_t)B * (sizeof(int) + 26 * sizeof(float));
+    for (int i = 0; i < depth; ++i) {
+        CNN_HIP_CHECK(hipHostMalloc((void**)&st->idx_host[i], block, hipHostMallocDefault));
+        CNN_HIP_CHECK(hipMalloc((void**)&st->idx_dev[i], block));
+        st->mat_host[i] = reinterpret_cast<float*>(st->idx_host[i] + B);
+        st->mat_dev[i] = reinterpret_cast<float*>(st->idx_dev[i] + B);
+        CNN_HIP_CHECK(hipMalloc((void**)&st->lab_dev[i], (size_t)B * sizeof(int)));
+        CNN_HIP_CHECK(hipMalloc(&st->dev_f32[i], (size_t)B * 3 * H * W * sizeof(float)));
+        CNN_HIP_CHECK(hipEventCreateWithFlags(&st->uploaded[i], hipEventDisableTiming));
+        CNN_HIP_CHECK(hipEventCreateWithFlags(&st->consumed[i], hipEventDisableTiming));
+    }
+    std::lock_guard<std::mutex> lk(ds->mu);
+    ds->stagers.push_back(st);
+    return CNN_AMD_OK;
+}
+
+int cnn_batch_stager_indices(void* stager, int slot, int** pinned) {
+    Stager* st = static_cast<Stager*>(stager);
+    CNN_REQUIRE(st && pinned && slot >= 0 && slot < st->depth, "cnn_batch_stager_indices: bad arguments");
+    CNN_REQUIRE(st->ds, "cnn_batch_stager_indices: not a resident stager (cnn_batch_stager_create_u8_resident)");
+    *pinned = st->idx_host[slot];
+    return CNN_AMD_OK;
+}
+
+int cnn_batch_stager_labels(void* stager, int slot, const int** labels_dev) {
+    Stager* st = static_cast<Stager*>(stager);
+    CNN_REQUIRE(st && labels_dev && slot >= 0 && slot < st->depth, "cnn_batch_stager_labels: bad arguments");
+    CNN_REQUIRE(st->ds, "cnn_batch_stager_labels: not a resident stager (cnn_batch_stager_create_u8_resident)");
+    *labels_dev = st->lab_dev[slot];
+    return CNN_AMD_OK;
+}
+
 int cnn_batch_stager_destroy(void* stager) {
     Stager* st = static_cast<Stager*>(stager);
     if (!st) return CNN_AMD_OK;
     if (st->copy) (void)hipStreamSynchronize(st->copy);
+    if (st->ds) {  // detach: the dataset may be written without waiting for this stream, and destroyed
+        std::lock_guard<std::mutex> lk(st->ds->mu);
+        std::vector<Stager*>& v = st->ds->stagers;
+        for (size_t i = 0; i < v.size(); ++i)
+            if (v[i] == st) {
+                v.erase(v.begin() + (long)i);
+                break;
+            }
+        st->mat_host.clear();  // (they point into idx_host / idx_dev)
+        st->mat_dev.clear();
+    }
+    for (int* p : st->idx_host)
+        if (p) (void)hipHostFree(p);
+    for (int* p : st->idx_dev)
+        if (p) (void)hipFree(p);
+    for (int* p : st->lab_dev)
+        if (p) (void)hipFree(p);
     if (st->lut) (void)hipFree(st->lut);
     for (float* p : st->mat_host)
         if (p) (void)hipHostFree(p);
@@ -648,7 +813,9 @@ int cnn_batch_stager_acquire(void* stager, void** pinned_host, int* slot) {
         for (int b = 0; b < st->B; ++b) memcpy(st->mat_host[i] + 6 * (size_t)b, st->resize_map, sizeof(st->resize_map));
     if (st->photo)
         for (int b = 0; b < st->B; ++b) memcpy(st->mat_host[i] + 6 * (size_t)st->B + 20 * (size_t)b, kPhotoIdentity, sizeof(kPhotoIdentity));
-    *pinned_host = st->host[i];
+    if (st->ds)
+        for (int b = 0; b < st->B; ++b) st->idx_host[i][b] = -1;
+    *pinned_host = st->host[i];  // (null for a resident stager: its images are in the dataset)
     *slot = i;
     return CNN_AMD_OK;
 }
@@ -656,6 +823,23 @@ int cnn_batch_stager_acquire(void* stager, void** pinned_host, int* slot) {
 int cnn_batch_stager_submit(void* stager, int slot, void** device_ptr) {
     Stager* st = static_cast<Stager*>(stager);
     CNN_REQUIRE(st && device_ptr && slot >= 0 && slot < st->depth, "cnn_batch_stager_submit: bad arguments");
+    if (st->ds) {  // indices + maps + photo blocks: one upload; the gather out of the dataset's store: one launch
+        Dataset* ds = st->ds;
+        const int* idx = st->idx_host[slot];
+        for (int b = 0; b < st->B; ++b)  // pinned memory the caller wrote: checked before anything is enqueued
+            CNN_REQUIRE(idx[b] >= -1 && (long long)idx[b] < ds->N, "cnn_batch_stager_submit: index %d of sample %d is outside [-1, %lld)", idx[b], b, ds->N);
+        std::lock_guard<std::mutex> lk(ds->mu);  // (cnn_dataset_write drains this stream under the same lock)
+        if (st->in_use[slot]) CNN_HIP_CHECK(hipStreamWaitEvent(st->copy, st->consumed[slot], 0));
+        const size_t block = (size_t)st->B * (sizeof(int) + 26 * sizeof(float));
+        CNN_HIP_CHECK(hipMemcpyAsync(st->idx_dev[slot], st->idx_host[slot], block, hipMemcpyHostToDevice, st->copy));
+        if (int rc = augment_u8_resident(ds->images, ds->labels, ds->N, st->idx_dev[slot], st->lab_dev[slot], st->B, st->Hs, st->Ws, st->mat_dev[slot],
+                                         st->fill, (float*)st->dev_f32[slot], st->H, st->W, st->mat_dev[slot] + 6 * (size_t)st->B, st->ns, st->nt,
+                                         st->clamp, st->copy))
+            return rc;
+        CNN_HIP_CHECK(hipEventRecord(st->uploaded[slot], st->copy));
+        *device_ptr = st->dev_f32[slot];
+        return CNN_AMD_OK;
+    }
     if (st->in_use[slot]) CNN_HIP_CHECK(hipStreamWaitEvent(st->copy, st->consumed[slot], 0));
     CNN_HIP_CHECK(hipMemcpyAsync(st->dev[slot], st->host[slot], st->bytes, hipMemcpyHostToDevice, st->copy));
     if (st->photo) {  // the same with the photometric epilogue: maps and photo blocks are one upload

@@ -30,6 +30,11 @@
 // table holds finite values >= 0, so 1*v + 0*w == v, v + 0 == v and v*1 + 0 == v.  The parameters are pinned memory the caller writes
 // and are not checked: a non-finite one gives unspecified PIXELS, never an access out of bounds -- the box only selects between two
 // values per pixel (a NaN bound compares false: no box), it never forms an address.
+//
+// The resident stager's kernel (the kResident instantiations, reached through cnn_batch_stager_create_u8_resident only; restated by
+// tests/resident_ref.py): the same two rules with sample b's source taken from a dataset's store, idx = indices[b]:
+//     source = store + (size_t)idx * (Hs*Ws*3);   idx == -1: no pixel of the sample is inside, no byte of the store is read
+//     labels_out[b] = idx < 0 ? -1 : labels[idx]
 #include <cmath>
 #include <mutex>
 
@@ -110,14 +115,28 @@ __device__ __forceinline__ unsigned long long load_u64(const unsigned char* p) {
 // kPhoto: the photometric epilogue on the twelve values right before the store.  The sample's 20 floats are uniform loads like the matrix
 // (`photo` is [B][20]); the stager's six and the clamp flag arrive as kernel arguments.  A pixel in the erase box counts as not inside
 // for the loads (a quad wholly in the box takes the no-load route) and gets ev[c] by a per-element select, so a box edge may cut a quad.
+// kResident (the resident stager's kernel, augment_u8_resident): `src` is a dataset's image store and sample b's source is sample
+// idx = indices[b] of it, a uniform load like the matrix; the sample base is formed in 64 bits (the store may exceed 4 GiB) before any
+// offset inside the sample is added, and the pulled-back load above stays bounded by the SAMPLE (one that ran past sample idx would read
+// sample idx + 1, or leave the allocation behind the last one).  idx == -1: no pixel of the sample is inside, so every thread takes the
+// no-load route and no byte of the store is read; fill and the erase box apply as ever.  The stager has checked the indices on the host;
+// one that is not in [0, N) here is treated as -1 all the same, so that no index can form an address outside the store.  One lane of one
+// workgroup per sample writes labels_out[b] = idx < 0 ? -1 : labels[idx].
 struct PhotoNorm {
     float s[3], t[3];
     int clamp;
 };
-template <bool kQuad, bool kPhoto>
+struct ResidentArgs {
+    const int* indices;  // [B], device
+    const int* labels;   // [N], the dataset's
+    int* labels_out;     // [B]
+    long long N;
+};
+template <bool kQuad, bool kPhoto, bool kResident = false>
 __global__ __launch_bounds__(kBlock) void augment_u8_kernel(const unsigned char* __restrict__ src, const float* __restrict__ mats,
                                                             const float* __restrict__ lut_g, float* __restrict__ dst, int Hs, int Ws, int H,
-                                                            int W, int W4, float fill, const float* __restrict__ photo, PhotoNorm norm) {
+                                                            int W, int W4, float fill, const float* __restrict__ photo, PhotoNorm norm,
+                                                            ResidentArgs res) {
     __shared__ float lut[256];
     lut[threadIdx.x] = lut_g[threadIdx.x];
     __syncthreads();
@@ -130,11 +149,18 @@ __global__ __launch_bounds__(kBlock) void augment_u8_kernel(const unsigned char*
         for (int k = 0; k < 20; ++k) pp[k] = photo[20 * b + k];
     }
     const float ex1 = kPhoto ? pp[12] + pp[14] : 0.f, ey1 = kPhoto ? pp[13] + pp[15] : 0.f;
-    const unsigned char* s = src + b * 3 * ((size_t)Hs * Ws);
+    const int sample_bytes = Hs * Ws * 3;
+    long long idx = (long long)b;  // which sample of `src` this one reads
+    if (kResident) {
+        const int i = res.indices[b];
+        idx = (i >= 0 && (long long)i < res.N) ? (long long)i : -1;
+        if (blockIdx.x == 0 && threadIdx.x == 0) res.labels_out[b] = idx < 0 ? -1 : res.labels[idx];
+    }
+    const bool present = !kResident || idx >= 0;
+    const unsigned char* s = src + (size_t)(present ? idx : 0) * (size_t)sample_bytes;
     const size_t plane = (size_t)H * W;
     float* d = dst + b * 3 * plane;
     const int quads = H * W4;
-    const int sample_bytes = Hs * Ws * 3;
     const bool wide = sample_bytes >= 8;
     for (int q = blockIdx.x * kBlock + threadIdx.x; q < quads; q += gridDim.x * kBlock) {
         const int y = q / W4, x = (q - y * W4) * 4;
@@ -144,7 +170,7 @@ __global__ __launch_bounds__(kBlock) void augment_u8_kernel(const unsigned char*
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             t[i] = augment_taps(m0, m1, m2, m3, m4, m5, x + i, y, Hs, Ws);
-            t[i].inside = t[i].inside && (kQuad || x + i < W);
+            t[i].inside = t[i].inside && (kQuad || x + i < W) && present;
             if (kPhoto) {
                 const float xf = (float)(x + i), yf = (float)y;
                 box[i] = xf >= pp[12] && xf < ex1 && yf >= pp[13] && yf < ey1;
@@ -268,16 +294,34 @@ int launch_augment(const unsigned char* src, int B, int Hs, int Ws, const float*
     const bool quad = W % 4 == 0 && aligned16(dst);
     if (photo) {
         if (quad)
-            CNN_KLAUNCH(s, "augment_u8_photo", (augment_u8_kernel<true, true><<<grid, kBlock, 0, s>>>(src, mats, lut, dst, Hs, Ws, H, W, W4, fill, photo, norm)),
+            CNN_KLAUNCH(s, "augment_u8_photo", (augment_u8_kernel<true, true><<<grid, kBlock, 0, s>>>(src, mats, lut, dst, Hs, Ws, H, W, W4, fill, photo, norm, ResidentArgs())),
                         "B=%d src=%dx%d out=%dx%d quad", B, Hs, Ws, H, W);
         else
-            CNN_KLAUNCH(s, "augment_u8_photo", (augment_u8_kernel<false, true><<<grid, kBlock, 0, s>>>(src, mats, lut, dst, Hs, Ws, H, W, W4, fill, photo, norm)),
+            CNN_KLAUNCH(s, "augment_u8_photo", (augment_u8_kernel<false, true><<<grid, kBlock, 0, s>>>(src, mats, lut, dst, Hs, Ws, H, W, W4, fill, photo, norm, ResidentArgs())),
                         "B=%d src=%dx%d out=%dx%d px", B, Hs, Ws, H, W);
     } else if (quad)
-        CNN_KLAUNCH(s, "augment_u8", (augment_u8_kernel<true, false><<<grid, kBlock, 0, s>>>(src, mats, lut, dst, Hs, Ws, H, W, W4, fill, nullptr, norm)),
+        CNN_KLAUNCH(s, "augment_u8", (augment_u8_kernel<true, false><<<grid, kBlock, 0, s>>>(src, mats, lut, dst, Hs, Ws, H, W, W4, fill, nullptr, norm, ResidentArgs())),
                     "B=%d src=%dx%d out=%dx%d quad", B, Hs, Ws, H, W);
     else
-        CNN_KLAUNCH(s, "augment_u8", (augment_u8_kernel<false, false><<<grid, kBlock, 0, s>>>(src, mats, lut, dst, Hs, Ws, H, W, W4, fill, nullptr, norm)),
+        CNN_KLAUNCH(s, "augment_u8", (augment_u8_kernel<false, false><<<grid, kBlock, 0, s>>>(src, mats, lut, dst, Hs, Ws, H, W, W4, fill, nullptr, norm, ResidentArgs())),
+                    "B=%d src=%dx%d out=%dx%d px", B, Hs, Ws, H, W);
+    return CNN_AMD_OK;
+}
+
+// the resident stager's launch: the photo kernel with a dataset's store as its source; one launch per batch as well
+int launch_resident(const unsigned char* store, int B, int Hs, int Ws, const float* mats, float fill, float* dst, int H, int W, const float* photo,
+                    const PhotoNorm& norm, const ResidentArgs& res, hipStream_t s) {
+    const float* lut = nullptr;
+    if (int rc = device_lut(&lut)) return rc;
+    const int W4 = (W + 3) / 4;
+    const int quads = H * W4;
+    const int need = (quads + kBlock - 1) / kBlock;
+    const dim3 grid((unsigned)(need < 4096 ? need : 4096), (unsigned)B);
+    if (W % 4 == 0 && aligned16(dst))
+        CNN_KLAUNCH(s, "augment_u8_resident", (augment_u8_kernel<true, true, true><<<grid, kBlock, 0, s>>>(store, mats, lut, dst, Hs, Ws, H, W, W4, fill, photo, norm, res)),
+                    "B=%d src=%dx%d out=%dx%d quad", B, Hs, Ws, H, W);
+    else
+        CNN_KLAUNCH(s, "augment_u8_resident", (augment_u8_kernel<false, true, true><<<grid, kBlock, 0, s>>>(store, mats, lut, dst, Hs, Ws, H, W, W4, fill, photo, norm, res)),
                     "B=%d src=%dx%d out=%dx%d px", B, Hs, Ws, H, W);
     return CNN_AMD_OK;
 }
@@ -310,6 +354,28 @@ int augment_u8_photo(const unsigned char* src, int B, int Hs, int Ws, const floa
     }
     norm.clamp = clamp ? 1 : 0;
     return launch_augment(src, B, Hs, Ws, mats_dev, fill, dst, H, W, photo_dev, norm, stream);
+}
+
+// the same out of a dataset's store (abi.hip, the resident stager's submit): indices_dev [B] in [-1, N), checked by the caller on the host
+int augment_u8_resident(const unsigned char* store, const int* labels, long long N, const int* indices_dev, int* labels_out, int B, int Hs, int Ws,
+                        const float* mats_dev, float fill, float* dst, int H, int W, const float* photo_dev, const float s[3], const float t[3],
+                        int clamp, hipStream_t stream) {
+    CNN_REQUIRE(store && labels && indices_dev && labels_out && mats_dev && dst && photo_dev, "augment_u8_resident: null pointer");
+    CNN_REQUIRE(N > 0 && N <= 2147483647LL && B > 0 && B <= kMaxDim && dims_ok(Hs, Ws, H, W),
+                "augment_u8_resident: N=%lld B=%d source %dx%d output %dx%d (each 1..%d)", N, B, Hs, Ws, H, W, kMaxDim);
+    CNN_REQUIRE(std::isfinite(fill), "augment_u8_resident: fill is not finite");
+    PhotoNorm norm;
+    for (int c = 0; c < 3; ++c) {
+        norm.s[c] = s[c];
+        norm.t[c] = t[c];
+    }
+    norm.clamp = clamp ? 1 : 0;
+    ResidentArgs res;
+    res.indices = indices_dev;
+    res.labels = labels;
+    res.labels_out = labels_out;
+    res.N = N;
+    return launch_resident(store, B, Hs, Ws, mats_dev, fill, dst, H, W, photo_dev, norm, res, stream);
 }
 }  // namespace cnn_amd
 

@@ -443,5 +443,9 @@ inline unsigned stream_grid(size_t work_items, int block) {
 // of its own.  photo_dev: [B][20] device floats; s, t, clamp: the stager's normalisation.  Same argument checks as cnn_augment_u8.
 int augment_u8_photo(const unsigned char* src, int B, int Hs, int Ws, const float* mats_dev, float fill, float* dst, int H, int W,
                      const float* photo_dev, const float s[3], const float t[3], int clamp, hipStream_t stream);
+// ... and with a resident dataset's store as the source (cnn_batch_stager_create_u8_resident): sample b reads sample indices_dev[b]
+int augment_u8_resident(const unsigned char* store, const int* labels, long long N, const int* indices_dev, int* labels_out, int B, int Hs, int Ws,
+                        const float* mats_dev, float fill, float* dst, int H, int W, const float* photo_dev, const float s[3], const float t[3],
+                        int clamp, hipStream_t stream);
 
 }  // namespace cnn_amd

@@ -213,6 +213,27 @@ def photo_params(rng, B, H, W, brightness=0.4, contrast=0.4, saturation=0.4, hue
     return out
 
 
+def epoch_order(n, batch, seed, epoch, shuffle=True, drop_last=False, rank=0, world=1):
+    """The sample indices of one epoch over a resident dataset of n samples, for rank `rank` of `world`: an int32 [steps][batch] array
+    for BatchStager.indices(slot), row by row.  The permutation of range(n) is drawn from (seed, epoch) alone -- the same on every rank,
+    another one every epoch; shuffle=False is the ascending order.  Rank r takes elements r, r + world, ... of it.  Every rank gets the
+    same number of rows: without drop_last the tail is padded with -1 ("no sample": a fill image with label -1, which evaluation counts
+    as ignored and training must not see); with drop_last only the rows that every rank can fill are kept.  Pure NumPy, no device."""
+    n, batch, rank, world = int(n), int(batch), int(rank), int(world)
+    if n < 1 or batch < 1 or world < 1 or not 0 <= rank < world:
+        raise capi.CnnAmdError(f"epoch_order: n={n}, batch={batch} (each >= 1), rank={rank} of world={world}")
+    perm = np.random.default_rng([int(seed), int(epoch)]).permutation(n) if shuffle else np.arange(n)
+    mine = perm[rank::world].astype(np.int32)
+    if drop_last:
+        steps = (n // world) // batch  # (the smallest share)
+        return np.ascontiguousarray(mine[:steps * batch].reshape(steps, batch))
+    largest = (n + world - 1) // world  # (the largest share)
+    steps = (largest + batch - 1) // batch
+    out = np.full(steps * batch, -1, dtype=np.int32)
+    out[:mine.size] = mine
+    return out.reshape(steps, batch)
+
+
 class HostNet:
     """architectures::Sequential / AlexNet (cnn_amd/host) behind a handle: the C++ Layer API a reference user links against."""
 
@@ -557,6 +578,74 @@ class HostNet:
         self.eval_begin(top_k)
         for x_dev, labels_dev in batches:
             self.eval_step(x_dev, labels_dev)
+        return self.eval_result()
+
+    def train_step_ptrs(self, x_ptr, labels_ptr, B, H, W, lr):
+        """train_step on two raw device pointers (a resident capi.BatchStager's submit() and labels(slot))"""
+        self.lib.cnnh_net_train_step_device_loss(self.h, C.c_void_p(x_ptr), C.c_void_p(labels_ptr), int(B), int(H), int(W), float(lr))
+
+    def eval_step_ptrs(self, x_ptr, labels_ptr, B, H, W):
+        """eval_step on two raw device pointers"""
+        if not getattr(self, "_eval_begun", False):
+            raise capi.CnnAmdError("eval_step_ptrs before eval_begin")
+        self._eval_B = int(B)
+        self.lib.cnnh_net_eval_step_device(self.h, C.c_void_p(x_ptr), C.c_void_p(labels_ptr), int(B), int(H), int(W))
+
+    def _resident_loop(self, stager, order, params, step):
+        """one pass over the rows of `order` through a resident stager with one batch of look-ahead: batch i + 1 is submitted (its
+        gather runs on the stager's stream) before batch i is stepped on the current stream; step(x_ptr, labels_ptr, B, H, W)"""
+        B, H, W = stager.B, stager.H, stager.W
+
+        def submit(row):
+            _, slot = stager.acquire()
+            stager.indices(slot)[:] = row
+            if params is not None:
+                mats, blocks = params(row)
+                if mats is not None:
+                    stager.matrices(slot)[:] = mats
+                if blocks is not None:
+                    stager.photo(slot)[:] = blocks
+            return slot, stager.submit(slot)
+
+        ahead = submit(order[0]) if len(order) else None
+        for i in range(len(order)):
+            slot, x_ptr = ahead
+            ahead = submit(order[i + 1]) if i + 1 < len(order) else None
+            stager.wait(slot)
+            step(x_ptr, stager.labels(slot), B, H, W)
+            stager.release(slot)
+
+    @staticmethod
+    def _resident_order(stager, order, what):
+        order = np.ascontiguousarray(order, dtype=np.int32)
+        if getattr(stager, "resident", None) is None:
+            raise capi.CnnAmdError(f"{what}: the stager is not a resident one (capi.BatchStager(u8_shape=..., resident=ds))")
+        if order.ndim != 2 or order.shape[1] != stager.B:
+            raise capi.CnnAmdError(f"{what}: order must be int32 [steps][{stager.B}] (hostapi.epoch_order)")
+        n = stager.resident.N
+        if order.size and (int(order.min()) < -1 or int(order.max()) >= n):
+            raise capi.CnnAmdError(f"{what}: an index outside [-1, {n})")
+        return order
+
+    def train_epoch_resident(self, stager, order, lr, params=None):
+        """One epoch out of a resident dataset: per row of `order` (int32 [steps][B], hostapi.epoch_order(..., drop_last=True)) the
+        stager gathers the batch and its labels on the device and train_step runs on them;
+        params(row) -> (matrices (B, 6) or None, photo blocks (B, 20) or None) is written into the slot when given.  An order that
+        contains -1 is refused before anything is enqueued: the training loss head indexes its row by the label, and the -1 of a padded
+        row would be an access out of bounds, not an ignored sample.  A stager of depth 3 keeps the host ahead: with two slots the
+        acquire() for batch i + 1 waits for step i - 1 to finish, and step i is queued only behind that wait (correct, 4 % slower:
+        profiles/resident_dataset.md)."""
+        order = self._resident_order(stager, order, "train_epoch_resident")
+        if order.size and int(order.min()) < 0:
+            raise capi.CnnAmdError("train_epoch_resident: the order contains -1 (a padded row); train with epoch_order(..., drop_last=True)")
+        self._resident_loop(stager, order, params, lambda x, l, B, H, W: self.train_step_ptrs(x, l, B, H, W, lr))
+
+    def evaluate_resident(self, stager, order, top_k=1):
+        """evaluate() out of a resident dataset: eval_begin, one eval_step per row of `order`, eval_result.  The -1 of a padded last
+        row is right here: its sample is a fill image with label -1, which cnn_eval_accumulate counts as ignored and nowhere else."""
+        order = self._resident_order(stager, order, "evaluate_resident")
+        self.eval_begin(top_k)
+        self._resident_loop(stager, order, None, self.eval_step_ptrs)
         return self.eval_result()
 
     def input_delta(self, shape):

@@ -875,6 +875,45 @@ typedef struct cnn_colour_op {
 } cnn_colour_op;
 int cnn_colour_matrix(const cnn_colour_op* ops, int n_ops, float out[12]);
 
+/* ---- a device-resident uint8 dataset: decode once, upload once, gather every batch by index out of HBM (an addition: the reference's
+ * DataLoader decodes and resizes every image again every epoch, pipeline.cpp:112-140).  What crosses PCIe per batch is then B indices and
+ * B * 26 floats instead of B * Hs * Ws * 3 bytes.
+ * cnn_dataset_create_u8: N images of Hs x Ws x 3 interleaved bytes (N * Hs * Ws * 3 bytes, may exceed 4 GiB: every offset into the store
+ * is 64-bit) and N int32 labels on the CURRENT device; N in 1 .. 2^31-1, Hs and Ws in 1 .. 8192.  Every image byte starts as 0 and every
+ * label as -1: no uninitialised byte can reach a result.
+ * cnn_dataset_write / _read: samples [first, first + count) from / to PAGEABLE or pinned host memory; images [count][Hs][Ws][3] and
+ * labels [count], either may be NULL (that part is left alone), not both.  Blocking host calls: they return when the data is on the
+ * device / on the host.  write() first waits, on the host, until every gather that a stager attached to this dataset has already
+ * submitted has finished (it synchronises their copy streams): a submitted batch always holds the bytes that were there at submit(), a
+ * later submit always sees the write, and the caller has no rule to follow.  Rejected: count <= 0, a range that leaves [0, N), both
+ * pointers NULL.
+ * cnn_dataset_info: N, Hs, Ws (each pointer may be NULL, not all three).
+ * cnn_dataset_destroy: CNN_AMD_E_BADARG, and nothing changed, while a stager is attached (destroy the stagers first); NULL is refused. */
+int cnn_dataset_create_u8(void** dataset, long long N, int Hs, int Ws);
+int cnn_dataset_write(void* dataset, long long first, long long count, const unsigned char* images /* host [count][Hs][Ws][3], nullable */,
+                      const int* labels /* host [count], nullable */);
+int cnn_dataset_read(void* dataset, long long first, long long count, unsigned char* images /* nullable */, int* labels /* nullable */);
+int cnn_dataset_info(void* dataset, long long* N, int* Hs, int* Ws);
+int cnn_dataset_destroy(void* dataset);
+/* The fourth kind of u8 stager: a photo stager (cnn_batch_stager_matrices, _photo, _set_fill and _set_normalize work on it unchanged)
+ * whose source is the dataset.  A slot has NO pinned image block and no device byte block; it carries one pinned block of B int32 indices
+ * followed by the B * 26 floats, a device copy of that block, the fp32 [B][3][H][W] output and a device int32 [B] label buffer.
+ * The rule, added to the gather rule and the photometric rule above with nothing else changed: sample b reads idx = indices[b]; its
+ * source image is sample idx of the store; with idx == -1 no pixel of the sample is inside and no byte of the store is read (every pixel
+ * is `fill`, an erase box still applies); labels_out[b] = idx < 0 ? -1 : labels[idx].  tests/resident_ref.py restates it.
+ *   acquire()  returns *pinned_host = NULL; presets the indices to -1, the matrices to the plain resize map, the photo blocks to the identity
+ *   cnn_batch_stager_indices()  the slot's pinned [B] indices, to overwrite between acquire() and submit()
+ *   submit()   checks the B indices on the host: one outside [-1, N) returns CNN_AMD_E_BADARG with nothing enqueued, and the slot stays
+ *              acquired and usable.  Otherwise ONE upload of the block and ONE launch (augment_u8_resident) on the stager's stream in front
+ *              of the event wait() waits for; returns the fp32 batch
+ *   cnn_batch_stager_labels()   the slot's device label buffer: valid behind the same wait() and until release()
+ * cnn_batch_stager_create_u8_resident: B in 1 .. 8192, H and W in 1 .. 8192, depth 2 .. 16; the dataset's device must be the current
+ * one; the dataset outlives the stager (cnn_dataset_destroy refuses while it is attached).  _indices and _labels return
+ * CNN_AMD_E_BADARG on a stager of the other three kinds. */
+int cnn_batch_stager_create_u8_resident(void** stager, void* dataset, int B, int H, int W, int depth);
+int cnn_batch_stager_indices(void* stager, int slot, int** pinned /* [B] */);
+int cnn_batch_stager_labels(void* stager, int slot, const int** labels_dev /* [B] */);
+
 /* page-locked host memory (async H2D / D2H copies are only asynchronous from / to pinned buffers) */
 int cnn_host_alloc_pinned(void** ptr, size_t bytes);
 int cnn_host_free_pinned(void* ptr);
