@@ -104,17 +104,24 @@ def _sha(t):
 
 
 class _Layer:
-    """seeded inputs of one desc on the device, and fresh (poisoned) output tensors per call"""
+    """seeded inputs of one desc on the device, and fresh (poisoned) output tensors per call.  inputs = (x, w, b, dy, relu_below) as host
+    arrays replaces the seeded ones, divisor the weight gradient's (default: the batch size) -- tests/test_gpu_exact_sums.py"""
 
-    def __init__(self, T, case, seed):
+    def __init__(self, T, case, seed, inputs=None, divisor=None):
         from cnn_amd import capi
 
         B, Ci, H, W, Co, k, s, pad = case[:8]
         self.T, self.case = T, case
+        self.divisor = float(B if divisor is None else divisor)
         self.conv = capi.Conv2d(B, Ci, H, W, Co, k, s, pad)
         self.conv.desc.flags = case[8] if len(case) > 8 else 0
         Ho, Wo = self.conv.Ho, self.conv.Wo
         dev = lambda a: T.from_numpy(np.ascontiguousarray(a)).cuda()
+        if inputs is not None:
+            self.x, self.w, self.b, self.dy, self.relu_below = (dev(a) for a in inputs)
+            assert self.x.shape == (B, Ci, H, W) and self.w.shape == (Co, Ci, k, k) and self.b.shape == (Co,)
+            assert self.dy.shape == (B, Co, Ho, Wo) and self.relu_below.shape == self.x.shape
+            return
         self.x = dev(uniform01(seed, (B, Ci, H, W)))
         self.w = dev(normal_scaled(seed + 1, (Co, Ci, k, k)))
         self.b = dev(normal_scaled(seed + 2, (Co,)))
@@ -130,6 +137,14 @@ class _Layer:
 
 def _logged(T, fn):
     """runs fn() -> {name: tensor} | int error code with the launch log on: {"log": {key: launches}, "sha": {...}} | {"log", "rc"}"""
+    out, log = _logged_outputs(T, fn)
+    if isinstance(out, int):
+        return {"log": log, "rc": out}
+    return {"log": log, "sha": {name: _sha(t) for name, t in sorted(out.items())}}
+
+
+def _logged_outputs(T, fn):
+    """... -> ({name: tensor} | int error code, {key: launches})"""
     from cnn_amd import capi
 
     T.cuda.synchronize()
@@ -143,9 +158,7 @@ def _logged(T, fn):
         log = {k: cnt for k, (cnt, _) in capi.kernel_timing_report().items()}
     finally:
         capi.kernel_timing(0)
-    if isinstance(out, int):
-        return {"log": log, "rc": out}
-    return {"log": log, "sha": {name: _sha(t) for name, t in sorted(out.items())}}
+    return out, log
 
 
 def _raw(L, mode, ws, ws_bytes):
@@ -173,7 +186,7 @@ def _calls(L, offset_ws):
         return {"y": y, "y_relu": yr}
 
     def backward_weight():
-        gw, gb = conv.backward_weight(L.x, L.dy, float(L.case[0]))
+        gw, gb = conv.backward_weight(L.x, L.dy, L.divisor)
         return {"gw": gw, "gb": gb}
 
     calls = {
