@@ -94,6 +94,20 @@ def conv_truth(case, x, w, b, dy, memo=None):
     (the way tests/test_gpu_parity._oracle_conv does)"""
     if memo is not None and memo in _TRUTH_MEMO:
         return _TRUTH_MEMO[memo]
+    y, S_gw, S_gb, dx = conv_f64(case, x, w, b, dy)
+    assert max(np.abs(S_gw).max(), np.abs(S_gb).max()) < LIMIT
+    out = (_f32(y), S_gw, S_gb, _f32(dx))
+    if memo is not None:
+        for a in out:
+            a.flags.writeable = False
+        _TRUTH_MEMO[memo] = out
+    return out
+
+
+def conv_f64(case, x, w, b, dy):
+    """the arithmetic of conv_truth in float64 on any operands: y, the undivided S_gw and S_gb, dx (all float64).  On continuous operands
+    it is a high-precision reference of the same operation, for any filter size -- the C oracle transcribes the reference's walk over
+    window centres (r = (k - 1) / 2 on either side) and is the operation only for odd k"""
     B, Ci, H, W, Co, k, s, pad, Ho, Wo = geometry(case)
     xp = np.pad(x.astype(np.float64), ((0, 0), (0, 0), (pad, pad), (pad, pad)))
     win = np.lib.stride_tricks.sliding_window_view(xp, (k, k), axis=(2, 3))[:, :, ::s, ::s]          # [B][Ci][Ho][Wo][k][k]
@@ -110,13 +124,7 @@ def conv_truth(case, x, w, b, dy, memo=None):
         for j in range(k):
             dxp[:, :, i : i + s * Ho : s, j : j + s * Wo : s] += dcols[..., i, j].transpose(0, 3, 1, 2)
     dx = dxp[:, :, pad : pad + H, pad : pad + W]
-    assert max(np.abs(S_gw).max(), np.abs(S_gb).max()) < LIMIT
-    out = (_f32(np.ascontiguousarray(y)), S_gw, S_gb, _f32(np.ascontiguousarray(dx)))
-    if memo is not None:
-        for a in out:
-            a.flags.writeable = False
-        _TRUTH_MEMO[memo] = out
-    return out
+    return np.ascontiguousarray(y), S_gw, S_gb, np.ascontiguousarray(dx)
 
 
 def lattice_conv(case, seed, amp=8, bias_amp=64):

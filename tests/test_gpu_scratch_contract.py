@@ -19,7 +19,9 @@ two more that HAND_PICKED does not reach (each asserts from its own launch log t
     smallest batch of that plane at which reduce_slabs takes its two-stage form (slab_reduce/stage1 into the rows behind the slabs);
   * (2, 128, 30, 30, 512, 3, 1, 1) with IGEMM_CFG=232: no rule-based plan splits K, the tuner pins such tiles; 5 pixel tiles x 4 channel
     blocks x 8 channel ranges is the smallest forward this tile accepts (20 workgroups < CUs, 160 within a round, 16 chunks >= 2 x 8):
-    8 partial tensors behind the filter image, in the workspace and in the prepared buffer (split_reduce/fwd).
+    8 partial tensors behind the filter image, in the workspace and in the prepared buffer (split_reduce/fwd);
+  * (1, 12, 30, 30, 40, 3, 1, 1) with IGEMM_CFG=202, 226 and 22: three tiles only the tuner pins (tests/test_gpu_igemm_tiles.py holds all
+    of them to exact bits): ragged 16-byte row units, whole-image staging with masked taps, the single-buffered kernel.
 
 A HIP error (a status >= CNN_AMD_E_HIP, or a failed synchronisation) is not a refusal: the test then ends the whole session with
 pytest.exit(returncode=3), because nothing more is to be started on a device that has faulted -- the tests behind it do not run."""
@@ -42,12 +44,23 @@ pytestmark = pytest.mark.gpu
 STAGE1_CASE = (5, 64, 28, 28, 128, 3, 1, 1)
 SPLITK_CASE = (2, 128, 30, 30, 512, 3, 1, 1)
 SPLITK_OPTIONS = (("IGEMM_CFG", "232"), ("DGRAD_RD", "0"), ("CONV_ROWS", "0"))
+# three tiles the tuner can pin and no rule picks on this plane (tests/igemm_tiles.py), forced on a 900-pixel plane with a 4-channel last
+# chunk: 202 stages padded rows in 16-byte units with a ragged tail, 226 whole images with masked taps, 22 is single-buffered
+TILE_CASE = (1, 12, 30, 30, 40, 3, 1, 1)
+TILE_OPTIONS = {cfg: (("IGEMM_CFG", str(cfg)), ("CONV_ROWS", "0"), ("FWD_RD", "0"), ("DGRAD_RD", "0")) for cfg in (202, 226, 22)}
+TILE_KERNELS = {202: "igemm_dma_kernel<32,2,2,1,4,4>", 226: "igemm_dma_kernel<32,2,1,1,4,4,img+mask>", 22: "igemm_kernel<32,2,1,2,2,16>"}
+# (appended at the end: the seeds of the entries in front are derived from their index)
 PARAMS = ([(c, ()) for c in R.HAND_PICKED] + [(STAGE1_CASE, ()), (SPLITK_CASE, SPLITK_OPTIONS)] +
-          [(c, (opt,)) for opt in R.OPTIONS for c in R.OPTION_CASES])
-# kernels the two added descs exist for: {call: a name its launch log must hold}
+          [(c, (opt,)) for opt in R.OPTIONS for c in R.OPTION_CASES] + [(TILE_CASE, TILE_OPTIONS[cfg]) for cfg in (202, 226, 22)])
+# kernels the added descs exist for: {call: a name its launch log must hold}
 MUST_LAUNCH = {(STAGE1_CASE, ()): {"backward_weight": "slab_reduce/stage1", "backward": "slab_reduce/stage1", "backward_prepared": "slab_reduce/stage1"},
                (SPLITK_CASE, SPLITK_OPTIONS): {"forward": "split_reduce/fwd", "forward_relu": "split_reduce/fwd+relu",
                                                "forward_prepared": "split_reduce/fwd+relu"}}
+for _cfg, _kernel in TILE_KERNELS.items():
+    MUST_LAUNCH[(TILE_CASE, TILE_OPTIONS[_cfg])] = {
+        "forward": _kernel + "/fwd", "forward_relu": _kernel + "/fwd+relu", "forward_prepared": _kernel + "/fwd+relu",
+        "backward_data": _kernel + "/dgrad", "backward_data_relu": _kernel + "/dgrad+relu",
+        "backward_data_prepared": _kernel + "/dgrad", "backward_data_relu_prepared": _kernel + "/dgrad+relu"}
 
 
 def _id(p):
