@@ -189,6 +189,12 @@ SIGNATURES = {
     "cnn_dataset_info": (C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "cnn_dataset_destroy": (C.c_int, [_P]),
     "cnn_batch_stager_create_u8_resident": (C.c_int, [C.POINTER(C.c_void_p), _P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "cnn_dataset_max_levels": (C.c_int, [C.c_int, C.c_int]),
+    "cnn_augment_level": (C.c_int, [C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
+    "cnn_dataset_create_u8_levels": (C.c_int, [C.POINTER(C.c_void_p), C.c_longlong, C.c_int, C.c_int, C.c_int]),
+    "cnn_dataset_read_level": (C.c_int, [_P, C.c_int, C.c_longlong, C.c_longlong, _P]),
+    "cnn_dataset_level_info": (C.c_int, [_P, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "cnn_batch_stager_levels": (C.c_int, [_P, C.c_int, C.POINTER(C.POINTER(C.c_int))]),
     "cnn_batch_stager_indices": (C.c_int, [_P, C.c_int, C.POINTER(C.POINTER(C.c_int))]),
     "cnn_batch_stager_labels": (C.c_int, [_P, C.c_int, C.POINTER(C.POINTER(C.c_int))]),
     "cnn_linear_forward": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
@@ -1165,15 +1171,53 @@ def side_stream_join():
     check(load().cnn_amd_side_stream_join(_stream()), "cnn_amd_side_stream_join")
 
 
+def dataset_max_levels(Hs, Ws):
+    """cnn_dataset_max_levels: how many half-size levels an Hs x Ws image has until both dimensions are 1 (host only)"""
+    n = load().cnn_dataset_max_levels(int(Hs), int(Ws))
+    if n <= 0:
+        raise CnnAmdError(f"cnn_dataset_max_levels: {load().cnn_amd_last_error().decode()}")
+    return n
+
+
+def augment_level(m, levels):
+    """cnn_augment_level: -> (level, float32 (6,) map on that level) a levelled resident stager's submit() picks for the map m of a
+    dataset with `levels` levels (host only)"""
+    import numpy as np
+
+    src = np.ascontiguousarray(m, dtype=np.float32).reshape(6)
+    out, level = np.empty(6, np.float32), C.c_int()
+    check(load().cnn_augment_level(src.ctypes.data_as(C.POINTER(C.c_float)), int(levels), C.byref(level), out.ctypes.data_as(C.POINTER(C.c_float))),
+          "cnn_augment_level")
+    return int(level.value), out
+
+
 class ResidentDataset:
     """cnn_dataset_*: N images of Hs x Ws x 3 bytes and N int32 labels in device memory (bytes 0 and labels -1 until written); the source
-    of BatchStager(u8_shape=..., resident=ds).  Close the stagers before the dataset."""
+    of BatchStager(u8_shape=..., resident=ds).  levels > 1: each image keeps levels - 1 prefiltered half-size copies, rebuilt by write(),
+    and an attached stager gathers every sample from the level whose residual shrink is below 2 (cnn_dataset_create_u8_levels).  Close
+    the stagers before the dataset."""
 
-    def __init__(self, N, Hs, Ws):
+    def __init__(self, N, Hs, Ws, levels=1):
         self.lib = load()
         self.h = C.c_void_p()
-        check(self.lib.cnn_dataset_create_u8(C.byref(self.h), int(N), int(Hs), int(Ws)), "cnn_dataset_create_u8")
-        self.N, self.Hs, self.Ws = int(N), int(Hs), int(Ws)
+        check(self.lib.cnn_dataset_create_u8_levels(C.byref(self.h), int(N), int(Hs), int(Ws), int(levels)), "cnn_dataset_create_u8_levels")
+        self.N, self.Hs, self.Ws, self.levels = int(N), int(Hs), int(Ws), int(levels)
+
+    def level_shape(self, level):
+        """-> (H_l, W_l) of level `level` as the library holds them"""
+        n, h, w = C.c_int(), C.c_int(), C.c_int()
+        check(self.lib.cnn_dataset_level_info(self.h, C.byref(n), int(level), C.byref(h), C.byref(w)), "cnn_dataset_level_info")
+        return int(h.value), int(w.value)
+
+    def read_level(self, level, first, count):
+        """-> uint8 (count, H_l, W_l, 3) of samples first .. first + count - 1 at level `level`; blocks"""
+        import numpy as np
+
+        h, w = self.level_shape(level)
+        count = int(count)
+        images = np.empty((max(count, 0), h, w, 3), np.uint8)
+        check(self.lib.cnn_dataset_read_level(self.h, int(level), int(first), count, images.ctypes.data_as(C.c_void_p)), "cnn_dataset_read_level")
+        return images
 
     def write(self, first, images_u8=None, labels=None):
         """samples first .. first + count - 1: images_u8 uint8 (count, Hs, Ws, 3) and / or labels int32 (count,), host arrays; blocks.
@@ -1291,6 +1335,15 @@ class BatchStager:
         check(self.lib.cnn_batch_stager_indices(self.h, int(slot), C.byref(p)), "cnn_batch_stager_indices")
         B = getattr(self, "B", 0)
         return np.ctypeslib.as_array((C.c_int * B).from_address(C.addressof(p.contents)))
+
+    def levels(self, slot):
+        """-> numpy (B,) int32 copy of the levels the slot's last submit() chose (a resident stager on a dataset with levels > 1)"""
+        import numpy as np
+
+        p = C.POINTER(C.c_int)()
+        check(self.lib.cnn_batch_stager_levels(self.h, int(slot), C.byref(p)), "cnn_batch_stager_levels")
+        B = getattr(self, "B", 0)
+        return np.ctypeslib.as_array((C.c_int * B).from_address(C.addressof(p.contents))).copy()
 
     def labels(self, slot):
         """-> device pointer (int) of the slot's int32 [B] labels (a resident stager): labels[idx], -1 where idx is -1; valid behind

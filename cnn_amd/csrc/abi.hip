@@ -444,17 +444,28 @@ struct Stager {
     // accessors and presets work on it as they are), `idx_dev` its device copy, `lab_dev` the labels the kernel gathers beside the batch
     struct Dataset* ds = nullptr;
     std::vector<int*> idx_host, idx_dev, lab_dev;
+    // ... on a dataset with `levels` > 1 the block carries, behind the B * 26 floats, B int32 levels and the B * 6 floats of the level
+    // maps: what submit() computes from the caller's maps (cnn_augment_level) and the kernel reads in their place.  One upload still
+    int levels = 1;
+    std::vector<int*> lvl_host, lvl_dev;
+    std::vector<float*> lmat_host, lmat_dev;
     std::vector<hipEvent_t> uploaded, consumed;
     std::vector<char> in_use;  // consumed[i] has been recorded at least once
 };
 
-// cnn_dataset_create_u8: N images of Hs x Ws x 3 bytes and N labels on `device`; `stagers` (under `mu`): the resident stagers attached
+// cnn_dataset_create_u8: N images of Hs x Ws x 3 bytes and N labels on `device`; `stagers` (under `mu`): the resident stagers attached.
+// cnn_dataset_create_u8_levels: `level` has one row per level (level[0].base == 0: the level-0 region keeps the one-level layout, the
+// higher levels follow it in the same allocation); with more than one level `table` is its device copy and `stream` the stream the
+// rebuild kernels of write() run on -- both stay null for a one-level dataset, which is what it always was
 struct Dataset {
     long long N = 0;
     int Hs = 0, Ws = 0, device = 0;
     size_t sample_bytes = 0;
     unsigned char* images = nullptr;
     int* labels = nullptr;
+    std::vector<DatasetLevel> level;
+    DatasetLevel* table = nullptr;
+    hipStream_t stream = nullptr;
     std::mutex mu;
     std::vector<Stager*> stagers;
 };
@@ -631,29 +642,55 @@ int cnn_batch_stager_set_fill(void* stager, float fill) {
 }
 
 // ---- the device-resident dataset and its stager ----------------------------------------------------------------------------------
-int cnn_dataset_create_u8(void** dataset, long long N, int Hs, int Ws) {
-    CNN_REQUIRE(dataset != nullptr, "cnn_dataset_create_u8: null pointer");
+namespace {
+int dataset_create(const char* who, void** dataset, long long N, int Hs, int Ws, int levels) {
+    CNN_REQUIRE(dataset != nullptr, "%s: null pointer", who);
     CNN_REQUIRE(N >= 1 && N <= 2147483647LL && Hs >= 1 && Hs <= 8192 && Ws >= 1 && Ws <= 8192,
-                "cnn_dataset_create_u8: N=%lld (1..2^31-1) images of %dx%d (each 1..8192)", N, Hs, Ws);
+                "%s: N=%lld (1..2^31-1) images of %dx%d (each 1..8192)", who, N, Hs, Ws);
+    CNN_REQUIRE(levels >= 1 && levels <= cnn_dataset_max_levels(Hs, Ws), "%s: levels=%d (1..%d for %dx%d)", who, levels,
+                cnn_dataset_max_levels(Hs, Ws), Hs, Ws);
     int dev = 0;
     CNN_HIP_CHECK(hipGetDevice(&dev));
     Dataset* ds = new Dataset();
     ds->N = N; ds->Hs = Hs; ds->Ws = Ws; ds->device = dev;
     ds->sample_bytes = (size_t)Hs * Ws * 3;
-    const size_t bytes = (size_t)N * ds->sample_bytes;
+    size_t bytes = 0;  // level 0 first, as ever; every offset in 64 bits
+    for (int l = 0, h = Hs, w = Ws; l < levels; ++l, h = (h + 1) / 2, w = (w + 1) / 2) {
+        DatasetLevel lv;
+        lv.base = (long long)bytes;
+        lv.H = h; lv.W = w;
+        lv.sample_bytes = h * w * 3;
+        lv.reserved = 0;
+        ds->level.push_back(lv);
+        bytes += (size_t)N * (size_t)lv.sample_bytes;
+    }
     hipError_t e = hipMalloc((void**)&ds->images, bytes);
     if (e == hipSuccess) e = hipMalloc((void**)&ds->labels, (size_t)N * sizeof(int));
-    if (e == hipSuccess) e = hipMemset(ds->images, 0, bytes);
+    if (e == hipSuccess) e = hipMemset(ds->images, 0, bytes);  // (the all-zero image's levels are all zero)
     if (e == hipSuccess) e = hipMemset(ds->labels, 0xFF, (size_t)N * sizeof(int));  // every label -1
+    if (e == hipSuccess && levels > 1) {
+        e = hipMalloc((void**)&ds->table, (size_t)levels * sizeof(DatasetLevel));
+        if (e == hipSuccess) e = hipMemcpy(ds->table, ds->level.data(), (size_t)levels * sizeof(DatasetLevel), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(&ds->stream, hipStreamNonBlocking);
+    }
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
         if (ds->images) (void)hipFree(ds->images);
         if (ds->labels) (void)hipFree(ds->labels);
+        if (ds->table) (void)hipFree(ds->table);
+        if (ds->stream) (void)hipStreamDestroy(ds->stream);
         delete ds;
-        return fail(CNN_AMD_E_HIP + (int)e, "cnn_dataset_create_u8: %zu bytes of images and %lld labels: %s", bytes, N, hipGetErrorString(e));
+        return fail(CNN_AMD_E_HIP + (int)e, "%s: %zu bytes of images and %lld labels: %s", who, bytes, N, hipGetErrorString(e));
     }
     *dataset = ds;
     return CNN_AMD_OK;
+}
+}  // namespace
+
+int cnn_dataset_create_u8(void** dataset, long long N, int Hs, int Ws) { return dataset_create("cnn_dataset_create_u8", dataset, N, Hs, Ws, 1); }
+
+int cnn_dataset_create_u8_levels(void** dataset, long long N, int Hs, int Ws, int levels) {
+    return dataset_create("cnn_dataset_create_u8_levels", dataset, N, Hs, Ws, levels);
 }
 
 namespace {
@@ -674,6 +711,13 @@ int cnn_dataset_write(void* dataset, long long first, long long count, const uns
     if (images) CNN_HIP_CHECK(hipMemcpy(ds->images + (size_t)first * ds->sample_bytes, images, (size_t)count * ds->sample_bytes, hipMemcpyHostToDevice));
     if (labels) CNN_HIP_CHECK(hipMemcpy(ds->labels + first, labels, (size_t)count * sizeof(int), hipMemcpyHostToDevice));
     CNN_HIP_CHECK(hipStreamSynchronize(nullptr));  // (a copy out of pageable memory may return once it is staged)
+    if (images && ds->level.size() > 1) {  // the half-size levels of exactly these samples, one launch per level, behind the copy above
+        for (size_t l = 1; l < ds->level.size(); ++l)
+            if (int rc = dataset_halve_u8(ds->images + ds->level[l - 1].base, ds->images + ds->level[l].base, first, count, ds->level[l - 1].H,
+                                          ds->level[l - 1].W, ds->stream))
+                return rc;
+        CNN_HIP_CHECK(hipStreamSynchronize(ds->stream));
+    }
     return CNN_AMD_OK;
 }
 
@@ -683,6 +727,27 @@ int cnn_dataset_read(void* dataset, long long first, long long count, unsigned c
     std::lock_guard<std::mutex> lk(ds->mu);
     if (images) CNN_HIP_CHECK(hipMemcpy(images, ds->images + (size_t)first * ds->sample_bytes, (size_t)count * ds->sample_bytes, hipMemcpyDeviceToHost));
     if (labels) CNN_HIP_CHECK(hipMemcpy(labels, ds->labels + first, (size_t)count * sizeof(int), hipMemcpyDeviceToHost));
+    return CNN_AMD_OK;
+}
+
+int cnn_dataset_read_level(void* dataset, int level, long long first, long long count, unsigned char* images) {
+    Dataset* ds = static_cast<Dataset*>(dataset);
+    if (int rc = dataset_range("cnn_dataset_read_level", ds, first, count, images, nullptr)) return rc;
+    CNN_REQUIRE(level >= 0 && level < (int)ds->level.size(), "cnn_dataset_read_level: level %d outside [0, %d)", level, (int)ds->level.size());
+    const DatasetLevel& lv = ds->level[(size_t)level];
+    std::lock_guard<std::mutex> lk(ds->mu);
+    CNN_HIP_CHECK(hipMemcpy(images, ds->images + lv.base + (size_t)first * (size_t)lv.sample_bytes, (size_t)count * (size_t)lv.sample_bytes,
+                            hipMemcpyDeviceToHost));
+    return CNN_AMD_OK;
+}
+
+int cnn_dataset_level_info(void* dataset, int* levels, int level, int* H_l, int* W_l) {
+    Dataset* ds = static_cast<Dataset*>(dataset);
+    CNN_REQUIRE(ds != nullptr && (levels != nullptr || H_l != nullptr || W_l != nullptr), "cnn_dataset_level_info: null pointer");
+    CNN_REQUIRE(level >= 0 && level < (int)ds->level.size(), "cnn_dataset_level_info: level %d outside [0, %d)", level, (int)ds->level.size());
+    if (levels) *levels = (int)ds->level.size();
+    if (H_l) *H_l = ds->level[(size_t)level].H;
+    if (W_l) *W_l = ds->level[(size_t)level].W;
     return CNN_AMD_OK;
 }
 
@@ -704,9 +769,19 @@ int cnn_dataset_destroy(void* dataset) {
     }
     (void)hipFree(ds->images);
     (void)hipFree(ds->labels);
+    if (ds->table) (void)hipFree(ds->table);
+    if (ds->stream) (void)hipStreamDestroy(ds->stream);
     delete ds;
     return CNN_AMD_OK;
 }
+
+namespace {
+// a resident slot's one pinned block (and its device copy): B indices and B * 26 floats; on a dataset with levels B levels and B * 6 more
+size_t resident_block_bytes(const Stager* st) {
+    const size_t per_sample = sizeof(int) + 26 * sizeof(float) + (st->levels > 1 ? sizeof(int) + 6 * sizeof(float) : 0);
+    return (size_t)st->B * per_sample;
+}
+}  // namespace
 
 int cnn_batch_stager_create_u8_resident(void** stager, void* dataset, int B, int H, int W, int depth) {
     Dataset* ds = static_cast<Dataset*>(dataset);
@@ -726,16 +801,26 @@ int cnn_batch_stager_create_u8_resident(void** stager, void* dataset, int B, int
     st->host.assign(depth, nullptr); st->dev.assign(depth, nullptr); st->dev_f32.assign(depth, nullptr);
     st->mat_host.assign(depth, nullptr); st->mat_dev.assign(depth, nullptr);
     st->idx_host.assign(depth, nullptr); st->idx_dev.assign(depth, nullptr); st->lab_dev.assign(depth, nullptr);
+    st->levels = (int)ds->level.size();
+    st->lvl_host.assign(depth, nullptr); st->lvl_dev.assign(depth, nullptr);
+    st->lmat_host.assign(depth, nullptr); st->lmat_dev.assign(depth, nullptr);
     st->uploaded.assign(depth, nullptr); st->consumed.assign(depth, nullptr);
     st->in_use.assign(depth, 0);
     *stager = st;
     CNN_HIP_CHECK(hipStreamCreateWithFlags(&st->copy, hipStreamNonBlocking));
-    const size_t block = (size_t)B * (sizeof(int) + 26 * sizeof(float));
+    const size_t block = resident_block_bytes(st);
     for (int i = 0; i < depth; ++i) {
         CNN_HIP_CHECK(hipHostMalloc((void**)&st->idx_host[i], block, hipHostMallocDefault));
         CNN_HIP_CHECK(hipMalloc((void**)&st->idx_dev[i], block));
         st->mat_host[i] = reinterpret_cast<float*>(st->idx_host[i] + B);
         st->mat_dev[i] = reinterpret_cast<float*>(st->idx_dev[i] + B);
+        if (st->levels > 1) {  // behind the 26 floats per sample: the levels, then the level maps
+            st->lvl_host[i] = reinterpret_cast<int*>(st->mat_host[i] + 26 * (size_t)B);
+            st->lvl_dev[i] = reinterpret_cast<int*>(st->mat_dev[i] + 26 * (size_t)B);
+            st->lmat_host[i] = reinterpret_cast<float*>(st->lvl_host[i] + B);
+            st->lmat_dev[i] = reinterpret_cast<float*>(st->lvl_dev[i] + B);
+            memset(st->lvl_host[i], 0, (size_t)B * (sizeof(int) + 6 * sizeof(float)));
+        }
         CNN_HIP_CHECK(hipMalloc((void**)&st->lab_dev[i], (size_t)B * sizeof(int)));
         CNN_HIP_CHECK(hipMalloc(&st->dev_f32[i], (size_t)B * 3 * H * W * sizeof(float)));
         CNN_HIP_CHECK(hipEventCreateWithFlags(&st->uploaded[i], hipEventDisableTiming));
@@ -751,6 +836,15 @@ int cnn_batch_stager_indices(void* stager, int slot, int** pinned) {
     CNN_REQUIRE(st && pinned && slot >= 0 && slot < st->depth, "cnn_batch_stager_indices: bad arguments");
     CNN_REQUIRE(st->ds, "cnn_batch_stager_indices: not a resident stager (cnn_batch_stager_create_u8_resident)");
     *pinned = st->idx_host[slot];
+    return CNN_AMD_OK;
+}
+
+int cnn_batch_stager_levels(void* stager, int slot, const int** pinned) {
+    Stager* st = static_cast<Stager*>(stager);
+    CNN_REQUIRE(st && pinned && slot >= 0 && slot < st->depth, "cnn_batch_stager_levels: bad arguments");
+    CNN_REQUIRE(st->ds, "cnn_batch_stager_levels: not a resident stager (cnn_batch_stager_create_u8_resident)");
+    CNN_REQUIRE(st->levels > 1, "cnn_batch_stager_levels: the stager's dataset has one level (cnn_dataset_create_u8_levels)");
+    *pinned = st->lvl_host[slot];
     return CNN_AMD_OK;
 }
 
@@ -828,13 +922,22 @@ int cnn_batch_stager_submit(void* stager, int slot, void** device_ptr) {
         const int* idx = st->idx_host[slot];
         for (int b = 0; b < st->B; ++b)  // pinned memory the caller wrote: checked before anything is enqueued
             CNN_REQUIRE(idx[b] >= -1 && (long long)idx[b] < ds->N, "cnn_batch_stager_submit: index %d of sample %d is outside [-1, %lld)", idx[b], b, ds->N);
+        if (st->levels > 1)  // each sample's level and its map on that level, beside the caller's maps (those stay as they are)
+            for (int b = 0; b < st->B; ++b)
+                if (int rc = cnn_augment_level(st->mat_host[slot] + 6 * (size_t)b, st->levels, st->lvl_host[slot] + b, st->lmat_host[slot] + 6 * (size_t)b))
+                    return rc;
         std::lock_guard<std::mutex> lk(ds->mu);  // (cnn_dataset_write drains this stream under the same lock)
         if (st->in_use[slot]) CNN_HIP_CHECK(hipStreamWaitEvent(st->copy, st->consumed[slot], 0));
-        const size_t block = (size_t)st->B * (sizeof(int) + 26 * sizeof(float));
+        const size_t block = resident_block_bytes(st);
         CNN_HIP_CHECK(hipMemcpyAsync(st->idx_dev[slot], st->idx_host[slot], block, hipMemcpyHostToDevice, st->copy));
-        if (int rc = augment_u8_resident(ds->images, ds->labels, ds->N, st->idx_dev[slot], st->lab_dev[slot], st->B, st->Hs, st->Ws, st->mat_dev[slot],
-                                         st->fill, (float*)st->dev_f32[slot], st->H, st->W, st->mat_dev[slot] + 6 * (size_t)st->B, st->ns, st->nt,
-                                         st->clamp, st->copy))
+        if (st->levels > 1) {
+            if (int rc = augment_u8_resident_levels(ds->images, ds->labels, ds->N, st->idx_dev[slot], st->lab_dev[slot], st->B, st->Hs, st->Ws,
+                                                    st->lmat_dev[slot], st->lvl_dev[slot], ds->table, st->levels, st->fill, (float*)st->dev_f32[slot],
+                                                    st->H, st->W, st->mat_dev[slot] + 6 * (size_t)st->B, st->ns, st->nt, st->clamp, st->copy))
+                return rc;
+        } else if (int rc = augment_u8_resident(ds->images, ds->labels, ds->N, st->idx_dev[slot], st->lab_dev[slot], st->B, st->Hs, st->Ws,
+                                                st->mat_dev[slot], st->fill, (float*)st->dev_f32[slot], st->H, st->W,
+                                                st->mat_dev[slot] + 6 * (size_t)st->B, st->ns, st->nt, st->clamp, st->copy))
             return rc;
         CNN_HIP_CHECK(hipEventRecord(st->uploaded[slot], st->copy));
         *device_ptr = st->dev_f32[slot];

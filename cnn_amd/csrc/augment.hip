@@ -14,7 +14,8 @@
 //     out = inside ? out : fill
 // A position inside the source's pixel area reads edge-replicated taps (what a resize needs), a position outside it gives `fill` (a
 // rotation's corners: the constant border).  With fx == 0 the rule yields t00 exactly, so the identity, flips, integer shifts and
-// quarter turns are bit-identical to the plain conversion of the permuted image.  There is no antialiasing: a large shrink ratio aliases.
+// quarter turns are bit-identical to the plain conversion of the permuted image.  Two taps per axis whatever the scale: a shrink ratio of
+// 2 or more aliases, except out of a dataset with half-size levels (below).
 //
 // The photometric epilogue (the kPhoto instantiations, reached through a photo stager only: cnn_batch_stager_create_u8_photo; restated in
 // NumPy by tests/photo_ref.py, bit for bit as well).  Sample b has 20 floats p[b][0..19], the stager has s[3], t[3] and a clamp flag.  Per
@@ -35,7 +36,14 @@
 // tests/resident_ref.py): the same two rules with sample b's source taken from a dataset's store, idx = indices[b]:
 //     source = store + (size_t)idx * (Hs*Ws*3);   idx == -1: no pixel of the sample is inside, no byte of the store is read
 //     labels_out[b] = idx < 0 ? -1 : labels[idx]
+//
+// Half-size levels (the kLevels instantiations, reached through a resident stager on a dataset with more than one level only; restated by
+// tests/mip_ref.py; the contract is in include/cnn_amd.h).  Level l > 0 of an image is the edge-replicated 2 x 2 box of level l - 1,
+// rounded half up, in integers (dataset_halve_u8 below, at write time).  The host picks a level per sample from the map's scale and
+// rewrites the map for that level (cnn_augment_level); the kernel applies the rules above to image idx of level l with Hs, Ws := H_l, W_l:
+//     source = store + base[l] + (size_t)idx * (H_l*W_l*3)
 #include <cmath>
+#include <cstring>
 #include <mutex>
 
 #include "common.h"
@@ -46,6 +54,7 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kMaxDim = 8192;  // fp32 holds every pixel index (and index + 0.5) below this exactly
+constexpr int kMaxLevels = 14;  // 8192 halves to 1 in 13 steps
 
 // where output pixel (x, y) samples the source: the byte offsets of the four taps inside the sample's image and the two weights
 struct Taps {
@@ -131,10 +140,21 @@ struct ResidentArgs {
     const int* labels;   // [N], the dataset's
     int* labels_out;     // [B]
     long long N;
+    // kLevels only: the sample's level, and the dataset's table of levels (device memory: a by-value array indexed by a runtime level
+    // would live in scratch)
+    const int* levels;        // [B], device
+    const DatasetLevel* table;  // [L]
+    int L;
 };
-template <bool kQuad, bool kPhoto, bool kResident = false>
+// kLevels (augment_u8_resident_levels): `mats` holds the LEVEL maps and sample b reads image idx of level l = levels[b], two more uniform
+// loads: the level, and that level's row of the dataset's table -- Hs, Ws, the sample's byte count and the level's base.  sample_bytes,
+// `wide` and the pulled-back load's bound are then the LEVEL's sample's (a load that ran past a level-l sample would read its neighbour,
+// or leave the allocation behind the last sample of the last level; a level of one or two pixels takes the byte-load route).  A level
+// that is not in [0, L) is treated as 0; the taps are clamped to the level's own size whatever the map says, so no value can form an
+// address outside the store.
+template <bool kQuad, bool kPhoto, bool kResident = false, bool kLevels = false>
 __global__ __launch_bounds__(kBlock) void augment_u8_kernel(const unsigned char* __restrict__ src, const float* __restrict__ mats,
-                                                            const float* __restrict__ lut_g, float* __restrict__ dst, int Hs, int Ws, int H,
+                                                            const float* __restrict__ lut_g, float* __restrict__ dst, int Hs0, int Ws0, int H,
                                                             int W, int W4, float fill, const float* __restrict__ photo, PhotoNorm norm,
                                                             ResidentArgs res) {
     __shared__ float lut[256];
@@ -143,13 +163,21 @@ __global__ __launch_bounds__(kBlock) void augment_u8_kernel(const unsigned char*
     const size_t b = blockIdx.y;
     const float* m = mats + 6 * b;
     const float m0 = m[0], m1 = m[1], m2 = m[2], m3 = m[3], m4 = m[4], m5 = m[5];
+    int Hs = Hs0, Ws = Ws0, sample_bytes = Hs0 * Ws0 * 3;
+    if (kLevels) {
+        const int l = res.levels[b];
+        const DatasetLevel lv = res.table[(l >= 0 && l < res.L) ? l : 0];
+        Hs = lv.H;
+        Ws = lv.W;
+        sample_bytes = lv.sample_bytes;
+        src += lv.base;
+    }
     float pp[20];
     if (kPhoto) {
 #pragma unroll
         for (int k = 0; k < 20; ++k) pp[k] = photo[20 * b + k];
     }
     const float ex1 = kPhoto ? pp[12] + pp[14] : 0.f, ey1 = kPhoto ? pp[13] + pp[15] : 0.f;
-    const int sample_bytes = Hs * Ws * 3;
     long long idx = (long long)b;  // which sample of `src` this one reads
     if (kResident) {
         const int i = res.indices[b];
@@ -242,6 +270,32 @@ __global__ __launch_bounds__(kBlock) void augment_u8_kernel(const unsigned char*
     }
 }
 
+// One half-size level of samples [first, first + count) of a dataset from the level before it: bytes in, bytes out, integers only.
+//     y0 = 2y, y1 = min(2y + 1, Hp - 1), x0 = 2x, x1 = min(2x + 1, Wp - 1)
+//     v  = (p[y0][x0] + p[y0][x1] + p[y1][x0] + p[y1][x1] + 2) >> 2
+// A thread owns one output pixel (three channels) and strides over the pixels of a sample (blockIdx.x) and over the samples
+// (blockIdx.y), so `count` is not limited by a grid dimension.  Offsets inside one sample fit an int (8192 * 8192 * 3); the sample bases
+// are formed in 64 bits first.
+__global__ __launch_bounds__(kBlock) void dataset_halve_u8_kernel(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst,
+                                                                   long long first, long long count, int Hp, int Wp, int H, int W) {
+    const int pixels = H * W;
+    const size_t src_bytes = (size_t)Hp * Wp * 3, dst_bytes = (size_t)pixels * 3;
+    for (long long n = blockIdx.y; n < count; n += gridDim.y) {
+        const unsigned char* s = src + (size_t)(first + n) * src_bytes;
+        unsigned char* d = dst + (size_t)(first + n) * dst_bytes;
+        for (int p = blockIdx.x * kBlock + threadIdx.x; p < pixels; p += gridDim.x * kBlock) {
+            const int y = p / W, x = p - y * W;
+            const int y0 = 2 * y, y1 = min(2 * y + 1, Hp - 1), x0 = 2 * x, x1 = min(2 * x + 1, Wp - 1);
+            const int o00 = (y0 * Wp + x0) * 3, o01 = (y0 * Wp + x1) * 3, o10 = (y1 * Wp + x0) * 3, o11 = (y1 * Wp + x1) * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const unsigned v = (unsigned)s[o00 + c] + s[o01 + c] + s[o10 + c] + s[o11 + c] + 2u;
+                d[3 * p + c] = (unsigned char)(v >> 2);
+            }
+        }
+    }
+}
+
 // lut[v] = v * 1.f / 255 (data_format.cpp:19-21, the reference's own expression, evaluated on the host): one device copy per device,
 // made at first use and kept for the life of the process
 int device_lut(const float** out) {
@@ -317,6 +371,17 @@ int launch_resident(const unsigned char* store, int B, int Hs, int Ws, const flo
     const int quads = H * W4;
     const int need = (quads + kBlock - 1) / kBlock;
     const dim3 grid((unsigned)(need < 4096 ? need : 4096), (unsigned)B);
+    if (res.levels) {  // a dataset with more than one level: the same launch of the kLevels instantiations
+        if (W % 4 == 0 && aligned16(dst))
+            CNN_KLAUNCH(s, "augment_u8_resident_levels",
+                        (augment_u8_kernel<true, true, true, true><<<grid, kBlock, 0, s>>>(store, mats, lut, dst, Hs, Ws, H, W, W4, fill, photo, norm, res)),
+                        "B=%d src=%dx%d L=%d out=%dx%d quad", B, Hs, Ws, res.L, H, W);
+        else
+            CNN_KLAUNCH(s, "augment_u8_resident_levels",
+                        (augment_u8_kernel<false, true, true, true><<<grid, kBlock, 0, s>>>(store, mats, lut, dst, Hs, Ws, H, W, W4, fill, photo, norm, res)),
+                        "B=%d src=%dx%d L=%d out=%dx%d px", B, Hs, Ws, res.L, H, W);
+        return CNN_AMD_OK;
+    }
     if (W % 4 == 0 && aligned16(dst))
         CNN_KLAUNCH(s, "augment_u8_resident", (augment_u8_kernel<true, true, true><<<grid, kBlock, 0, s>>>(store, mats, lut, dst, Hs, Ws, H, W, W4, fill, photo, norm, res)),
                     "B=%d src=%dx%d out=%dx%d quad", B, Hs, Ws, H, W);
@@ -370,12 +435,50 @@ int augment_u8_resident(const unsigned char* store, const int* labels, long long
         norm.t[c] = t[c];
     }
     norm.clamp = clamp ? 1 : 0;
-    ResidentArgs res;
+    ResidentArgs res = ResidentArgs();
     res.indices = indices_dev;
     res.labels = labels;
     res.labels_out = labels_out;
     res.N = N;
     return launch_resident(store, B, Hs, Ws, mats_dev, fill, dst, H, W, photo_dev, norm, res, stream);
+}
+
+int augment_u8_resident_levels(const unsigned char* store, const int* labels, long long N, const int* indices_dev, int* labels_out, int B, int Hs,
+                               int Ws, const float* mats_dev, const int* levels_dev, const DatasetLevel* table_dev, int L, float fill, float* dst, int H,
+                               int W, const float* photo_dev, const float s[3], const float t[3], int clamp, hipStream_t stream) {
+    CNN_REQUIRE(store && labels && indices_dev && labels_out && mats_dev && dst && photo_dev && levels_dev && table_dev,
+                "augment_u8_resident_levels: null pointer");
+    CNN_REQUIRE(N > 0 && N <= 2147483647LL && B > 0 && B <= kMaxDim && dims_ok(Hs, Ws, H, W) && L > 1 && L <= kMaxLevels,
+                "augment_u8_resident_levels: N=%lld B=%d source %dx%d output %dx%d (each 1..%d) levels=%d (2..%d)", N, B, Hs, Ws, H, W, kMaxDim, L,
+                kMaxLevels);
+    CNN_REQUIRE(std::isfinite(fill), "augment_u8_resident_levels: fill is not finite");
+    PhotoNorm norm;
+    for (int c = 0; c < 3; ++c) {
+        norm.s[c] = s[c];
+        norm.t[c] = t[c];
+    }
+    norm.clamp = clamp ? 1 : 0;
+    ResidentArgs res = ResidentArgs();
+    res.indices = indices_dev;
+    res.labels = labels;
+    res.labels_out = labels_out;
+    res.N = N;
+    res.levels = levels_dev;
+    res.table = table_dev;
+    res.L = L;
+    return launch_resident(store, B, Hs, Ws, mats_dev, fill, dst, H, W, photo_dev, norm, res, stream);
+}
+
+int dataset_halve_u8(const unsigned char* src, unsigned char* dst, long long first, long long count, int Hp, int Wp, hipStream_t stream) {
+    CNN_REQUIRE(src && dst, "dataset_halve_u8: null pointer");
+    CNN_REQUIRE(first >= 0 && count > 0 && Hp > 0 && Wp > 0 && Hp <= kMaxDim && Wp <= kMaxDim && (Hp > 1 || Wp > 1),
+                "dataset_halve_u8: samples [%lld, +%lld) of %dx%d", first, count, Hp, Wp);
+    const int H = (Hp + 1) / 2, W = (Wp + 1) / 2;
+    const int need = (H * W + kBlock - 1) / kBlock;
+    const dim3 grid((unsigned)(need < 4096 ? need : 4096), (unsigned)(count < 4096 ? count : 4096));
+    CNN_KLAUNCH(stream, "dataset_halve_u8", (dataset_halve_u8_kernel<<<grid, kBlock, 0, stream>>>(src, dst, first, count, Hp, Wp, H, W)),
+                "n=%lld src=%dx%d out=%dx%d", count, Hp, Wp, H, W);
+    return CNN_AMD_OK;
 }
 }  // namespace cnn_amd
 
@@ -445,6 +548,44 @@ int cnn_augment_matrix(const cnn_augment_op* ops, int n_ops, int Hs, int Ws, int
         m[i] = (float)(a.v[i / 3][i % 3] + 0.0);  // (+ 0.0: a product such as 0 * -1 leaves -0)
         CNN_REQUIRE(std::isfinite(m[i]), "cnn_augment_matrix: the composed map is not finite");
     }
+    return CNN_AMD_OK;
+}
+
+// Host only.  How many levels a chain of half-size images has until both dimensions are 1; 0 (and a message) for sizes outside 1..8192.
+int cnn_dataset_max_levels(int Hs, int Ws) {
+    if (!(Hs > 0 && Ws > 0 && Hs <= kMaxDim && Ws <= kMaxDim)) {
+        (void)fail(CNN_AMD_E_BADARG, "cnn_dataset_max_levels: %dx%d (each 1..%d)", Hs, Ws, kMaxDim);
+        return 0;
+    }
+    int n = 1;
+    for (int h = Hs, w = Ws; h > 1 || w > 1; h = (h + 1) / 2, w = (w + 1) / 2) ++n;
+    return n;
+}
+
+// Host only.  The level a sample gathers from and its map on that level (include/cnn_amd.h has the rule; tests/mip_ref.py restates it).
+// All in double; every product, sum and quotient rounded separately; the two offsets rounded to fp32 once.
+int cnn_augment_level(const float m[6], int levels, int* level, float m_level[6]) {
+#pragma clang fp contract(off)
+    CNN_REQUIRE(m != nullptr && level != nullptr && m_level != nullptr, "cnn_augment_level: null pointer");
+    CNN_REQUIRE(levels >= 1 && levels <= kMaxLevels, "cnn_augment_level: levels=%d (1..%d)", levels, kMaxLevels);
+    const double m0 = m[0], m1 = m[1], m2 = m[2], m3 = m[3], m4 = m[4], m5 = m[5];
+    const double rx = std::sqrt(m0 * m0 + m3 * m3), ry = std::sqrt(m1 * m1 + m4 * m4);
+    const double r = rx > ry ? rx : ry;  // source pixels per output pixel
+    int l = 0;
+    if (std::isfinite(rx) && std::isfinite(ry))
+        while (l + 1 < levels && r >= (double)(1 << (l + 1))) ++l;
+    *level = l;
+    if (l == 0) {
+        memmove(m_level, m, 6 * sizeof(float));  // bit for bit
+        return CNN_AMD_OK;
+    }
+    const double k = (double)(1 << l);
+    m_level[0] = (float)(m0 / k);
+    m_level[1] = (float)(m1 / k);
+    m_level[2] = (float)((m2 + 0.5) / k - 0.5);
+    m_level[3] = (float)(m3 / k);
+    m_level[4] = (float)(m4 / k);
+    m_level[5] = (float)((m5 + 0.5) / k - 0.5);
     return CNN_AMD_OK;
 }
 

@@ -447,5 +447,20 @@ int augment_u8_photo(const unsigned char* src, int B, int Hs, int Ws, const floa
 int augment_u8_resident(const unsigned char* store, const int* labels, long long N, const int* indices_dev, int* labels_out, int B, int Hs, int Ws,
                         const float* mats_dev, float fill, float* dst, int H, int W, const float* photo_dev, const float s[3], const float t[3],
                         int clamp, hipStream_t stream);
+// One level of a dataset with half-size levels (cnn_dataset_create_u8_levels): where its [N][H][W][3] region begins in the store, its
+// size and the bytes of one sample (H * W * 3).  The dataset keeps a host and a device copy of the table.
+struct DatasetLevel {
+    long long base;
+    int H, W;
+    int sample_bytes;
+    int reserved;
+};
+// ... the same out of level levels_dev[b] of a dataset with `L` > 1 levels (augment_u8_resident_levels): mats_dev holds the LEVEL maps
+// (cnn_augment_level), table_dev the dataset's L levels; Hs, Ws are level 0's
+int augment_u8_resident_levels(const unsigned char* store, const int* labels, long long N, const int* indices_dev, int* labels_out, int B, int Hs,
+                               int Ws, const float* mats_dev, const int* levels_dev, const DatasetLevel* table_dev, int L, float fill, float* dst, int H,
+                               int W, const float* photo_dev, const float s[3], const float t[3], int clamp, hipStream_t stream);
+// level l of samples [first, first + count) from level l - 1 (dataset_halve_u8): src [N][Hp][Wp][3], dst [N][(Hp+1)/2][(Wp+1)/2][3]
+int dataset_halve_u8(const unsigned char* src, unsigned char* dst, long long first, long long count, int Hp, int Wp, hipStream_t stream);
 
 }  // namespace cnn_amd

@@ -22,9 +22,14 @@ namespace architectures {
 
 // N images of Hs x Ws x 3 interleaved bytes (cv::Mat CV_8UC3 as it lies) and N labels in device memory, on the device that is current
 // at construction.  Every byte starts as 0 and every label as -1.  Not copyable; destroy the loaders on it first.
+// levels > 1 (up to max_levels(Hs, Ws)): each image keeps levels - 1 prefiltered half-size copies beside it, rebuilt by write(); a loader
+// on the dataset then gathers every sample from the level whose residual shrink is below 2, so a map that shrinks by 2 or more no
+// longer aliases.  At most a third more memory; nothing else about the loader changes.
 class ResidentDataset {
 public:
-    ResidentDataset(const long long N, const int Hs, const int Ws) { must(cnn_dataset_create_u8(&handle, N, Hs, Ws), "ResidentDataset"); }
+    ResidentDataset(const long long N, const int Hs, const int Ws, const int levels = 1) {
+        must(cnn_dataset_create_u8_levels(&handle, N, Hs, Ws, levels), "ResidentDataset");
+    }
     ~ResidentDataset() {
         if (handle && cnn_dataset_destroy(handle) != 0) std::fprintf(stderr, "~ResidentDataset: %s\n", cnn_amd_last_error());
     }
@@ -41,6 +46,17 @@ public:
         must(cnn_dataset_read(handle, first, count, images, labels), "ResidentDataset::read");
     }
     void info(long long* N, int* Hs, int* Ws) const { must(cnn_dataset_info(handle, N, Hs, Ws), "ResidentDataset::info"); }
+    static int max_levels(const int Hs, const int Ws) { return cnn_dataset_max_levels(Hs, Ws); }
+    int levels() const {
+        int n = 0;
+        must(cnn_dataset_level_info(handle, &n, 0, nullptr, nullptr), "ResidentDataset::levels");
+        return n;
+    }
+    void level_size(const int level, int* H_l, int* W_l) const { must(cnn_dataset_level_info(handle, nullptr, level, H_l, W_l), "ResidentDataset::level_size"); }
+    // one level of the same range back to the host, [count][H_l][W_l][3].  Blocks
+    void read_level(const int level, const long long first, const long long count, unsigned char* images) const {
+        must(cnn_dataset_read_level(handle, level, first, count, images), "ResidentDataset::read_level");
+    }
     long long size() const {
         long long n = 0;
         info(&n, nullptr, nullptr);

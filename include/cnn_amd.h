@@ -789,7 +789,8 @@ int cnn_batch_stager_release(void* stager, int slot, void* stream);
 
 /* ---- geometric augmentation of uint8 batches on the device (an addition: ImageAugmentor, pipeline.cpp:40-77, runs OpenCV on the host).
  * Flip, crop, rotate and the resize to the network's size are ONE affine map per sample; one kernel gathers through it while it does the
- * stager's bytes -> fp32 planar conversion.  Decode is not covered, and there is no antialiasing: a large shrink ratio aliases.  Colour
+ * stager's bytes -> fp32 planar conversion.  Decode is not covered.  The gather takes two taps per axis whatever the map's scale: a shrink
+ * ratio of 2 or more aliases, except out of a resident dataset that keeps half-size levels (cnn_dataset_create_u8_levels below).  Colour
  * jitter, normalisation and erasing: the photo stager below.
  * The rule.  Input: interleaved bytes [B][Hs][Ws][3]; output: planar fp32 [B][3][H][W].  Sample b has six floats m[b][0..5] that map
  * OUTPUT pixel indices to SOURCE pixel indices.  Per output pixel (x, y), all in fp32, every product and sum rounded separately:
@@ -913,6 +914,51 @@ int cnn_dataset_destroy(void* dataset);
 int cnn_batch_stager_create_u8_resident(void** stager, void* dataset, int B, int H, int W, int depth);
 int cnn_batch_stager_indices(void* stager, int slot, int** pinned /* [B] */);
 int cnn_batch_stager_labels(void* stager, int slot, const int** labels_dev /* [B] */);
+
+/* ---- half-size levels for antialiased shrinking out of a resident dataset.  The gather's two taps per axis skip source pixels once the
+ * map shrinks by 2 or more.  A dataset made with levels = L > 1 keeps, beside each image, a chain of L - 1 prefiltered half-size images,
+ * built once at write time; a stager attached to it picks per sample the level whose residual shrink is below 2, and the gather stays the
+ * four-tap kernel with the same traffic per batch.  The store grows by at most a third.
+ * The rule.  Levels: level 0 is the image as written, Hs x Ws x 3 interleaved bytes.  Level l has H_l = (H_{l-1} + 1) / 2 and
+ * W_l = (W_{l-1} + 1) / 2 (rounded up); its pixel (y, x), channel c, in integers, with p = level l - 1:
+ *     y0 = 2y, y1 = min(2y + 1, H_{l-1} - 1), x0 = 2x, x1 = min(2x + 1, W_{l-1} - 1)
+ *     v  = (p[y0][x0] + p[y0][x1] + p[y1][x0] + p[y1][x1] + 2) >> 2
+ * -- an edge-replicated 2 x 2 box, rounded half up: no floating point, exact on any machine.  The centre of level-l pixel x lies at
+ * level-0 coordinate 2^l * (x + 0.5) - 0.5; on an odd size the last pixel is the replicated edge.  L runs from 1 to
+ * cnn_dataset_max_levels(Hs, Ws), the number of levels until both dimensions are 1 (at most 14, for 8192).
+ * Level choice and level map: host arithmetic in double from the sample's six fp32 floats m, every operation rounded separately:
+ *     rx = sqrt(m0*m0 + m3*m3), ry = sqrt(m1*m1 + m4*m4), r = max(rx, ry)      (source pixels per output pixel)
+ *     l  = 0; while (l + 1 < L && r >= 2^(l+1)) ++l;                           (rx or ry not finite: l = 0)
+ *     l == 0:  m' = m, bit for bit
+ *     l  > 0:  m'0,1,3,4 = m0,1,3,4 / 2^l   (exact)
+ *              m'2 = (m2 + 0.5) / 2^l - 0.5,  m'5 likewise                     (double, rounded to fp32 once)
+ * The residual ratio r / 2^l stays in [1, 2) while levels remain: there the bilinear rule's two taps per axis give every pixel of the
+ * level a non-zero weight.  The nearest LOWER level is used; there is no blend between two levels, no anisotropic choice.
+ * Gather: sample b with index idx and level l is the gather + photometric + resident rule above, unchanged, applied to image idx of
+ * level l with Hs, Ws := H_l, W_l and m := m' (the `inside` test is against the level's size); idx == -1 reads nothing at any level;
+ * labels_out as above.  tests/mip_ref.py restates all three parts; the kernels equal it bit for bit.
+ * cnn_dataset_max_levels, cnn_augment_level: the two host halves of the rule (no GPU call).  _max_levels returns 0 (and sets the
+ * message) for a size outside 1 .. 8192; _augment_level takes levels in 1 .. 14 and writes the level and the six floats of m' (m_level
+ * may be m itself).
+ * cnn_dataset_create_u8_levels: cnn_dataset_create_u8 with `levels` in 1 .. cnn_dataset_max_levels(Hs, Ws) levels; levels = 1 IS
+ * cnn_dataset_create_u8.  One allocation: the level-0 region [N][Hs][Ws][3] first, as ever, then each higher level as [N][H_l][W_l][3];
+ * every offset is 64-bit, every byte starts as 0 (the all-zero image's levels are all zero).
+ * cnn_dataset_write with images rebuilds, behind the copy, levels 1 .. L-1 of exactly the samples written (one launch of dataset_halve_u8
+ * per level on a stream of the dataset's own) and returns when they are done: still a blocking host call, under the same rule about
+ * submitted gathers.  A labels-only write launches nothing.  cnn_dataset_read and _info are unchanged (level 0).
+ * cnn_dataset_read_level: samples [first, first + count) of one level back to the host, [count][H_l][W_l][3]; blocking.
+ * cnn_dataset_level_info: the number of levels and the size of level `level` (each pointer may be NULL, not all three).
+ * A resident stager attached to a dataset with L > 1: its slots' pinned block carries, behind the B indices and B * 26 floats, B int32
+ * levels and B * 6 level maps (one allocation and one upload still).  submit(), after the index check, runs cnn_augment_level on the
+ * caller's maps -- which are not overwritten -- and launches augment_u8_resident_levels in place of augment_u8_resident.
+ * cnn_batch_stager_levels hands out the levels the last submit() of that slot chose; CNN_AMD_E_BADARG on the other kinds of stager and
+ * on stagers of a one-level dataset.  A stager on a one-level dataset is what it was in every respect. */
+int cnn_dataset_max_levels(int Hs, int Ws);
+int cnn_augment_level(const float m[6], int levels, int* level, float m_level[6]);
+int cnn_dataset_create_u8_levels(void** dataset, long long N, int Hs, int Ws, int levels);
+int cnn_dataset_read_level(void* dataset, int level, long long first, long long count, unsigned char* images /* [count][H_l][W_l][3] */);
+int cnn_dataset_level_info(void* dataset, int* levels, int level, int* H_l, int* W_l);
+int cnn_batch_stager_levels(void* stager, int slot, const int** pinned /* [B] */);
 
 /* page-locked host memory (async H2D / D2H copies are only asynchronous from / to pinned buffers) */
 int cnn_host_alloc_pinned(void** ptr, size_t bytes);
