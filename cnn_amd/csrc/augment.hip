@@ -1,6 +1,6 @@
 // augment.hip -- geometric augmentation of uint8 image batches on the device (an addition: the reference's ImageAugmentor runs OpenCV on
 // the host, pipeline.cpp:40-77): flip, crop, rotate and the resize to the network's size as ONE per-sample affine gather, fused with the
-// bytes -> fp32 planar conversion the u8 stager does anyway (abi.hip, u8hwc_to_f32chw).  Decode stays on the host.
+// bytes -> fp32 planar conversion the u8 stager does anyway (staging.hip, u8hwc_to_f32chw).  Decode stays on the host.
 //
 // The rule (restated in NumPy by tests/augment_ref.py; the kernel equals it bit for bit).  Input: interleaved bytes [B][Hs][Ws][3];
 // output: planar fp32 [B][3][H][W]; sample b has six floats m[b][0..5] that map OUTPUT pixel indices to SOURCE pixel indices.  Per output
@@ -52,9 +52,7 @@ using namespace cnn_amd;
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kMaxDim = 8192;  // fp32 holds every pixel index (and index + 0.5) below this exactly
-constexpr int kMaxLevels = 14;  // 8192 halves to 1 in 13 steps
+constexpr int kBlock = 256;  // (kMaxDim, kMaxLevels: stager_layout.h)
 
 // where output pixel (x, y) samples the source: the byte offsets of the four taps inside the sample's image and the two weights
 struct Taps {
@@ -130,22 +128,7 @@ __device__ __forceinline__ unsigned long long load_u64(const unsigned char* p) {
 // sample idx + 1, or leave the allocation behind the last one).  idx == -1: no pixel of the sample is inside, so every thread takes the
 // no-load route and no byte of the store is read; fill and the erase box apply as ever.  The stager has checked the indices on the host;
 // one that is not in [0, N) here is treated as -1 all the same, so that no index can form an address outside the store.  One lane of one
-// workgroup per sample writes labels_out[b] = idx < 0 ? -1 : labels[idx].
-struct PhotoNorm {
-    float s[3], t[3];
-    int clamp;
-};
-struct ResidentArgs {
-    const int* indices;  // [B], device
-    const int* labels;   // [N], the dataset's
-    int* labels_out;     // [B]
-    long long N;
-    // kLevels only: the sample's level, and the dataset's table of levels (device memory: a by-value array indexed by a runtime level
-    // would live in scratch)
-    const int* levels;        // [B], device
-    const DatasetLevel* table;  // [L]
-    int L;
-};
+// workgroup per sample writes labels_out[b] = idx < 0 ? -1 : labels[idx].  (PhotoNorm, ResidentArgs: common.h)
 // kLevels (augment_u8_resident_levels): `mats` holds the LEVEL maps and sample b reads image idx of level l = levels[b], two more uniform
 // loads: the level, and that level's row of the dataset's table -- Hs, Ws, the sample's byte count and the level's base.  sample_bytes,
 // `wide` and the pulled-back load's bound are then the LEVEL's sample's (a load that ran past a level-l sample would read its neighbour,
@@ -296,6 +279,53 @@ __global__ __launch_bounds__(kBlock) void dataset_halve_u8_kernel(const unsigned
     }
 }
 
+bool dims_ok(int Hs, int Ws, int H, int W) { return Hs > 0 && Ws > 0 && H > 0 && W > 0 && Hs <= kMaxDim && Ws <= kMaxDim && H <= kMaxDim && W <= kMaxDim; }
+
+// 2 x 3 affine maps in double, a[r][0] * x + a[r][1] * y + a[r][2]; compose(a, t) = a after t
+struct Affine {
+    double v[2][3];
+};
+Affine compose(const Affine& a, const Affine& t) {
+    Affine r;
+    for (int i = 0; i < 2; ++i) {
+        r.v[i][0] = a.v[i][0] * t.v[0][0] + a.v[i][1] * t.v[1][0];
+        r.v[i][1] = a.v[i][0] * t.v[0][1] + a.v[i][1] * t.v[1][1];
+        r.v[i][2] = a.v[i][0] * t.v[0][2] + a.v[i][1] * t.v[1][2] + a.v[i][2];
+    }
+    return r;
+}
+
+// every instantiation there is, by what the job carries; .quad: W % 4 == 0 and dst 16-byte aligned.  (The order of the rows is the order of
+// the eight kernels in the code object, which follows their first mention: reordering them reorders the object.)
+using AugmentKernel = void (*)(const unsigned char*, const float*, const float*, float*, int, int, int, int, int, float, const float*, PhotoNorm,
+                               ResidentArgs);
+enum { kRowPhoto, kRowPlain, kRowLevels, kRowResident };
+const struct {
+    const char* name;
+    AugmentKernel quad, px;
+} kAugmentKernels[4] = {
+    {"augment_u8_photo", augment_u8_kernel<true, true>, augment_u8_kernel<false, true>},
+    {"augment_u8", augment_u8_kernel<true, false>, augment_u8_kernel<false, false>},
+    {"augment_u8_resident_levels", augment_u8_kernel<true, true, true, true>, augment_u8_kernel<false, true, true, true>},
+    {"augment_u8_resident", augment_u8_kernel<true, true, true>, augment_u8_kernel<false, true, true>},
+};
+
+// 3 x 4 affine colour maps in double, v[r][0..2] * rgb + v[r][3]; compose(l, a) = l after a
+struct Colour {
+    double v[3][4];
+};
+Colour compose(const Colour& l, const Colour& a) {
+    Colour r;
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) r.v[i][j] = l.v[i][0] * a.v[0][j] + l.v[i][1] * a.v[1][j] + l.v[i][2] * a.v[2][j];
+        r.v[i][3] = l.v[i][0] * a.v[0][3] + l.v[i][1] * a.v[1][3] + l.v[i][2] * a.v[2][3] + l.v[i][3];
+    }
+    return r;
+}
+
+}  // namespace
+
+namespace cnn_amd {
 // lut[v] = v * 1.f / 255 (data_format.cpp:19-21, the reference's own expression, evaluated on the host): one device copy per device,
 // made at first use and kept for the life of the process
 int device_lut(const float** out) {
@@ -320,153 +350,30 @@ int device_lut(const float** out) {
     return CNN_AMD_OK;
 }
 
-bool dims_ok(int Hs, int Ws, int H, int W) { return Hs > 0 && Ws > 0 && H > 0 && W > 0 && Hs <= kMaxDim && Ws <= kMaxDim && H <= kMaxDim && W <= kMaxDim; }
-
-// 2 x 3 affine maps in double, a[r][0] * x + a[r][1] * y + a[r][2]; compose(a, t) = a after t
-struct Affine {
-    double v[2][3];
-};
-Affine compose(const Affine& a, const Affine& t) {
-    Affine r;
-    for (int i = 0; i < 2; ++i) {
-        r.v[i][0] = a.v[i][0] * t.v[0][0] + a.v[i][1] * t.v[1][0];
-        r.v[i][1] = a.v[i][0] * t.v[0][1] + a.v[i][1] * t.v[1][1];
-        r.v[i][2] = a.v[i][0] * t.v[0][2] + a.v[i][1] * t.v[1][2] + a.v[i][2];
-    }
-    return r;
-}
-
-// one launch per batch; `photo` ([B][20], device) selects the kPhoto instantiations.  The callers have checked the arguments.
-int launch_augment(const unsigned char* src, int B, int Hs, int Ws, const float* mats, float fill, float* dst, int H, int W, const float* photo,
-                   const PhotoNorm& norm, hipStream_t s) {
+// one launch per batch.  The stager (staging.hip) has checked a resident job's indices on the host.
+int augment_u8_run(const char* who, const AugmentJob& j, hipStream_t s) {
+    const ResidentArgs& r = j.res;
+    const bool resident = r.indices != nullptr, levels = r.levels != nullptr;
+    CNN_REQUIRE(j.src && j.mats && j.dst && (!resident || (r.labels && r.labels_out && j.photo)) && (!levels || (resident && r.table)),
+                "%s: null pointer", who);
+    CNN_REQUIRE(j.B > 0 && j.B <= kMaxDim && dims_ok(j.Hs, j.Ws, j.H, j.W), "%s: B=%d source %dx%d output %dx%d (each 1..%d)", who, j.B, j.Hs, j.Ws,
+                j.H, j.W, kMaxDim);
+    CNN_REQUIRE(!resident || (r.N > 0 && r.N <= 2147483647LL), "%s: N=%lld (1..2^31-1)", who, r.N);
+    CNN_REQUIRE(!levels || (r.L > 1 && r.L <= kMaxLevels), "%s: levels=%d (2..%d)", who, r.L, kMaxLevels);
+    CNN_REQUIRE(std::isfinite(j.fill), "%s: fill is not finite", who);
     const float* lut = nullptr;
     if (int rc = device_lut(&lut)) return rc;
-    const int W4 = (W + 3) / 4;
-    const int quads = H * W4;
+    const int W4 = (j.W + 3) / 4;
+    const int quads = j.H * W4;
     const int need = (quads + kBlock - 1) / kBlock;
-    const dim3 grid((unsigned)(need < 4096 ? need : 4096), (unsigned)B);
-    const bool quad = W % 4 == 0 && aligned16(dst);
-    if (photo) {
-        if (quad)
-            CNN_KLAUNCH(s, "augment_u8_photo", (augment_u8_kernel<true, true><<<grid, kBlock, 0, s>>>(src, mats, lut, dst, Hs, Ws, H, W, W4, fill, photo, norm, ResidentArgs())),
-                        "B=%d src=%dx%d out=%dx%d quad", B, Hs, Ws, H, W);
-        else
-            CNN_KLAUNCH(s, "augment_u8_photo", (augment_u8_kernel<false, true><<<grid, kBlock, 0, s>>>(src, mats, lut, dst, Hs, Ws, H, W, W4, fill, photo, norm, ResidentArgs())),
-                        "B=%d src=%dx%d out=%dx%d px", B, Hs, Ws, H, W);
-    } else if (quad)
-        CNN_KLAUNCH(s, "augment_u8", (augment_u8_kernel<true, false><<<grid, kBlock, 0, s>>>(src, mats, lut, dst, Hs, Ws, H, W, W4, fill, nullptr, norm, ResidentArgs())),
-                    "B=%d src=%dx%d out=%dx%d quad", B, Hs, Ws, H, W);
-    else
-        CNN_KLAUNCH(s, "augment_u8", (augment_u8_kernel<false, false><<<grid, kBlock, 0, s>>>(src, mats, lut, dst, Hs, Ws, H, W, W4, fill, nullptr, norm, ResidentArgs())),
-                    "B=%d src=%dx%d out=%dx%d px", B, Hs, Ws, H, W);
+    const dim3 grid((unsigned)(need < 4096 ? need : 4096), (unsigned)j.B);
+    const bool quad = j.W % 4 == 0 && aligned16(j.dst);
+    const auto& k = kAugmentKernels[levels ? kRowLevels : resident ? kRowResident : j.photo ? kRowPhoto : kRowPlain];
+    char lv[16] = "";  // (the tag is only formatted while the kernel timer is on)
+    if (levels && ktimer_active()) snprintf(lv, sizeof(lv), " L=%d", r.L);
+    CNN_KLAUNCH(s, k.name, ((quad ? k.quad : k.px)<<<grid, kBlock, 0, s>>>(j.src, j.mats, lut, j.dst, j.Hs, j.Ws, j.H, j.W, W4, j.fill, j.photo, j.norm, r)),
+                "B=%d src=%dx%d%s out=%dx%d %s", j.B, j.Hs, j.Ws, lv, j.H, j.W, quad ? "quad" : "px");
     return CNN_AMD_OK;
-}
-
-// the resident stager's launch: the photo kernel with a dataset's store as its source; one launch per batch as well
-int launch_resident(const unsigned char* store, int B, int Hs, int Ws, const float* mats, float fill, float* dst, int H, int W, const float* photo,
-                    const PhotoNorm& norm, const ResidentArgs& res, hipStream_t s) {
-    const float* lut = nullptr;
-    if (int rc = device_lut(&lut)) return rc;
-    const int W4 = (W + 3) / 4;
-    const int quads = H * W4;
-    const int need = (quads + kBlock - 1) / kBlock;
-    const dim3 grid((unsigned)(need < 4096 ? need : 4096), (unsigned)B);
-    if (res.levels) {  // a dataset with more than one level: the same launch of the kLevels instantiations
-        if (W % 4 == 0 && aligned16(dst))
-            CNN_KLAUNCH(s, "augment_u8_resident_levels",
-                        (augment_u8_kernel<true, true, true, true><<<grid, kBlock, 0, s>>>(store, mats, lut, dst, Hs, Ws, H, W, W4, fill, photo, norm, res)),
-                        "B=%d src=%dx%d L=%d out=%dx%d quad", B, Hs, Ws, res.L, H, W);
-        else
-            CNN_KLAUNCH(s, "augment_u8_resident_levels",
-                        (augment_u8_kernel<false, true, true, true><<<grid, kBlock, 0, s>>>(store, mats, lut, dst, Hs, Ws, H, W, W4, fill, photo, norm, res)),
-                        "B=%d src=%dx%d L=%d out=%dx%d px", B, Hs, Ws, res.L, H, W);
-        return CNN_AMD_OK;
-    }
-    if (W % 4 == 0 && aligned16(dst))
-        CNN_KLAUNCH(s, "augment_u8_resident", (augment_u8_kernel<true, true, true><<<grid, kBlock, 0, s>>>(store, mats, lut, dst, Hs, Ws, H, W, W4, fill, photo, norm, res)),
-                    "B=%d src=%dx%d out=%dx%d quad", B, Hs, Ws, H, W);
-    else
-        CNN_KLAUNCH(s, "augment_u8_resident", (augment_u8_kernel<false, true, true><<<grid, kBlock, 0, s>>>(store, mats, lut, dst, Hs, Ws, H, W, W4, fill, photo, norm, res)),
-                    "B=%d src=%dx%d out=%dx%d px", B, Hs, Ws, H, W);
-    return CNN_AMD_OK;
-}
-
-// 3 x 4 affine colour maps in double, v[r][0..2] * rgb + v[r][3]; compose(l, a) = l after a
-struct Colour {
-    double v[3][4];
-};
-Colour compose(const Colour& l, const Colour& a) {
-    Colour r;
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) r.v[i][j] = l.v[i][0] * a.v[0][j] + l.v[i][1] * a.v[1][j] + l.v[i][2] * a.v[2][j];
-        r.v[i][3] = l.v[i][0] * a.v[0][3] + l.v[i][1] * a.v[1][3] + l.v[i][2] * a.v[2][3] + l.v[i][3];
-    }
-    return r;
-}
-
-}  // namespace
-
-namespace cnn_amd {
-int augment_u8_photo(const unsigned char* src, int B, int Hs, int Ws, const float* mats_dev, float fill, float* dst, int H, int W,
-                     const float* photo_dev, const float s[3], const float t[3], int clamp, hipStream_t stream) {
-    CNN_REQUIRE(src && mats_dev && dst && photo_dev, "augment_u8_photo: null pointer");
-    CNN_REQUIRE(B > 0 && B <= kMaxDim && dims_ok(Hs, Ws, H, W), "augment_u8_photo: B=%d source %dx%d output %dx%d (each 1..%d)", B, Hs, Ws, H, W, kMaxDim);
-    CNN_REQUIRE(std::isfinite(fill), "augment_u8_photo: fill is not finite");
-    PhotoNorm norm;
-    for (int c = 0; c < 3; ++c) {
-        norm.s[c] = s[c];
-        norm.t[c] = t[c];
-    }
-    norm.clamp = clamp ? 1 : 0;
-    return launch_augment(src, B, Hs, Ws, mats_dev, fill, dst, H, W, photo_dev, norm, stream);
-}
-
-// the same out of a dataset's store (abi.hip, the resident stager's submit): indices_dev [B] in [-1, N), checked by the caller on the host
-int augment_u8_resident(const unsigned char* store, const int* labels, long long N, const int* indices_dev, int* labels_out, int B, int Hs, int Ws,
-                        const float* mats_dev, float fill, float* dst, int H, int W, const float* photo_dev, const float s[3], const float t[3],
-                        int clamp, hipStream_t stream) {
-    CNN_REQUIRE(store && labels && indices_dev && labels_out && mats_dev && dst && photo_dev, "augment_u8_resident: null pointer");
-    CNN_REQUIRE(N > 0 && N <= 2147483647LL && B > 0 && B <= kMaxDim && dims_ok(Hs, Ws, H, W),
-                "augment_u8_resident: N=%lld B=%d source %dx%d output %dx%d (each 1..%d)", N, B, Hs, Ws, H, W, kMaxDim);
-    CNN_REQUIRE(std::isfinite(fill), "augment_u8_resident: fill is not finite");
-    PhotoNorm norm;
-    for (int c = 0; c < 3; ++c) {
-        norm.s[c] = s[c];
-        norm.t[c] = t[c];
-    }
-    norm.clamp = clamp ? 1 : 0;
-    ResidentArgs res = ResidentArgs();
-    res.indices = indices_dev;
-    res.labels = labels;
-    res.labels_out = labels_out;
-    res.N = N;
-    return launch_resident(store, B, Hs, Ws, mats_dev, fill, dst, H, W, photo_dev, norm, res, stream);
-}
-
-int augment_u8_resident_levels(const unsigned char* store, const int* labels, long long N, const int* indices_dev, int* labels_out, int B, int Hs,
-                               int Ws, const float* mats_dev, const int* levels_dev, const DatasetLevel* table_dev, int L, float fill, float* dst, int H,
-                               int W, const float* photo_dev, const float s[3], const float t[3], int clamp, hipStream_t stream) {
-    CNN_REQUIRE(store && labels && indices_dev && labels_out && mats_dev && dst && photo_dev && levels_dev && table_dev,
-                "augment_u8_resident_levels: null pointer");
-    CNN_REQUIRE(N > 0 && N <= 2147483647LL && B > 0 && B <= kMaxDim && dims_ok(Hs, Ws, H, W) && L > 1 && L <= kMaxLevels,
-                "augment_u8_resident_levels: N=%lld B=%d source %dx%d output %dx%d (each 1..%d) levels=%d (2..%d)", N, B, Hs, Ws, H, W, kMaxDim, L,
-                kMaxLevels);
-    CNN_REQUIRE(std::isfinite(fill), "augment_u8_resident_levels: fill is not finite");
-    PhotoNorm norm;
-    for (int c = 0; c < 3; ++c) {
-        norm.s[c] = s[c];
-        norm.t[c] = t[c];
-    }
-    norm.clamp = clamp ? 1 : 0;
-    ResidentArgs res = ResidentArgs();
-    res.indices = indices_dev;
-    res.labels = labels;
-    res.labels_out = labels_out;
-    res.N = N;
-    res.levels = levels_dev;
-    res.table = table_dev;
-    res.L = L;
-    return launch_resident(store, B, Hs, Ws, mats_dev, fill, dst, H, W, photo_dev, norm, res, stream);
 }
 
 int dataset_halve_u8(const unsigned char* src, unsigned char* dst, long long first, long long count, int Hp, int Wp, hipStream_t stream) {
@@ -485,10 +392,7 @@ int dataset_halve_u8(const unsigned char* src, unsigned char* dst, long long fir
 extern "C" {
 
 int cnn_augment_u8(const unsigned char* src, int B, int Hs, int Ws, const float* matrices_dev, float fill, float* dst, int H, int W, void* stream) {
-    CNN_REQUIRE(src && matrices_dev && dst, "cnn_augment_u8: null pointer");
-    CNN_REQUIRE(B > 0 && B <= kMaxDim && dims_ok(Hs, Ws, H, W), "cnn_augment_u8: B=%d source %dx%d output %dx%d (each 1..%d)", B, Hs, Ws, H, W, kMaxDim);
-    CNN_REQUIRE(std::isfinite(fill), "cnn_augment_u8: fill is not finite");
-    return launch_augment(src, B, Hs, Ws, matrices_dev, fill, dst, H, W, nullptr, PhotoNorm(), as_stream(stream));
+    return augment_u8_run("cnn_augment_u8", AugmentJob{src, B, Hs, Ws, matrices_dev, fill, dst, H, W, nullptr, PhotoNorm(), ResidentArgs()}, as_stream(stream));
 }
 
 // Host only.  The ops transform a canvas that starts as the source, in order, the way ImageAugmentor::make_augment transforms its cv::Mat;

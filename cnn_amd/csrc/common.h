@@ -11,6 +11,7 @@
 #include <initializer_list>
 
 #include "cnn_amd.h"
+#include "stager_layout.h"
 
 namespace cnn_amd {
 
@@ -439,27 +440,57 @@ inline unsigned stream_grid(size_t work_items, int block) {
     return (unsigned)(need < 1 ? 1 : (need > cap ? cap : need));
 }
 
-// augment.hip: cnn_augment_u8 with the photometric epilogue (include/cnn_amd.h), for the photo stager's submit() in abi.hip -- no export
-// of its own.  photo_dev: [B][20] device floats; s, t, clamp: the stager's normalisation.  Same argument checks as cnn_augment_u8.
-int augment_u8_photo(const unsigned char* src, int B, int Hs, int Ws, const float* mats_dev, float fill, float* dst, int H, int W,
-                     const float* photo_dev, const float s[3], const float t[3], int clamp, hipStream_t stream);
-// ... and with a resident dataset's store as the source (cnn_batch_stager_create_u8_resident): sample b reads sample indices_dev[b]
-int augment_u8_resident(const unsigned char* store, const int* labels, long long N, const int* indices_dev, int* labels_out, int B, int Hs, int Ws,
-                        const float* mats_dev, float fill, float* dst, int H, int W, const float* photo_dev, const float s[3], const float t[3],
-                        int clamp, hipStream_t stream);
 // One level of a dataset with half-size levels (cnn_dataset_create_u8_levels): where its [N][H][W][3] region begins in the store, its
-// size and the bytes of one sample (H * W * 3).  The dataset keeps a host and a device copy of the table.
+// size and the bytes of one sample (H * W * 3).  The dataset (staging.hip) keeps a host and a device copy of the table.
 struct DatasetLevel {
     long long base;
     int H, W;
     int sample_bytes;
     int reserved;
 };
-// ... the same out of level levels_dev[b] of a dataset with `L` > 1 levels (augment_u8_resident_levels): mats_dev holds the LEVEL maps
-// (cnn_augment_level), table_dev the dataset's L levels; Hs, Ws are level 0's
-int augment_u8_resident_levels(const unsigned char* store, const int* labels, long long N, const int* indices_dev, int* labels_out, int B, int Hs,
-                               int Ws, const float* mats_dev, const int* levels_dev, const DatasetLevel* table_dev, int L, float fill, float* dst, int H,
-                               int W, const float* photo_dev, const float s[3], const float t[3], int clamp, hipStream_t stream);
+
+}  // namespace cnn_amd
+
+// The two argument blocks of augment.hip's kernel template beside the pointers.  Unnamed namespace on purpose: a kernel's symbol spells
+// the types of its parameters, and with internal linkage here the symbols are the same whichever file fills the blocks.
+namespace {
+struct PhotoNorm {  // the photo stager's normalisation: out = u * s[c] + t[c], u clamped to [0, 1] first if `clamp`
+    float s[3], t[3];
+    int clamp;
+};
+struct ResidentArgs {
+    const int* indices;  // [B], device; null: the source is the batch's own images
+    const int* labels;   // [N], the dataset's
+    int* labels_out;     // [B]
+    long long N;
+    // levels only (`levels` non-null): the sample's level, and the dataset's table of levels (device memory: a by-value array indexed by
+    // a runtime level would live in scratch)
+    const int* levels;                   // [B], device
+    const cnn_amd::DatasetLevel* table;  // [L]
+    int L;
+};
+}  // namespace
+
+namespace cnn_amd {
+
+// augment.hip: one launch of the augmenting gather per batch, for cnn_augment_u8 and for the submit() of the augmenting stagers
+// (staging.hip).  src: [B][Hs][Ws][3] device bytes, or a dataset's store when res.indices is set (Hs, Ws: level 0's; with res.levels set
+// `mats` holds the LEVEL maps of cnn_augment_level).  photo ([B][20], device) is null for the plain gather.  augment_u8_run checks
+// pointers, sizes and fill, and names `who` in the message.
+struct AugmentJob {
+    const unsigned char* src;
+    int B, Hs, Ws;
+    const float* mats;  // [B][6], device
+    float fill;
+    float* dst;  // [B][3][H][W]
+    int H, W;
+    const float* photo;
+    PhotoNorm norm;
+    ResidentArgs res;
+};
+int augment_u8_run(const char* who, const AugmentJob& job, hipStream_t stream);
+// lut[v] = v * 1.f / 255 evaluated on the host, on the current device: one copy per device, made at first use, kept for the process
+int device_lut(const float** out);
 // level l of samples [first, first + count) from level l - 1 (dataset_halve_u8): src [N][Hp][Wp][3], dst [N][(Hp+1)/2][(Wp+1)/2][3]
 int dataset_halve_u8(const unsigned char* src, unsigned char* dst, long long first, long long count, int Hp, int Wp, hipStream_t stream);
 
