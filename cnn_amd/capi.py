@@ -24,6 +24,7 @@ class ConvDesc(C.Structure):
 
 
 POOL_MASK_PACKED = 1  # CNN_CONV2D_POOL_MASK_PACKED (include/cnn_amd.h)
+DEPTHWISE = 4  # CNN_CONV2D_DEPTHWISE: Co == Ci, w is [C][1][k][k]; the plain forward / backward entries only
 
 
 class MixDesc(C.Structure):

@@ -39,7 +39,7 @@ int get_side(SideStream** out) {
 // 2 631).  The switch stays (SERIAL_BWD_GFLOP=<limit>; 0 = every layer serial); the default no longer serialises any layer.
 bool heavy_layer(const cnn_conv2d_desc* d) {
     const double Ho = cnn_conv2d_out_dim(d->H, d->k, d->s, d->pad), Wo = cnn_conv2d_out_dim(d->W, d->k, d->s, d->pad);
-    const double flops = 2.0 * d->B * d->Co * Ho * Wo * d->Ci * d->k * d->k;
+    const double flops = 2.0 * d->B * d->Co * Ho * Wo * (is_depthwise(d) ? 1 : d->Ci) * d->k * d->k;
     const double limit = CNN_OPT("SERIAL_BWD_GFLOP").as_double(1e9) * 1e9;
     return flops >= limit;
 }
@@ -56,6 +56,11 @@ int fork_side(SideStream* side, hipStream_t main) {
     return CNN_AMD_OK;
 }
 size_t dgrad_region_bytes(const cnn_conv2d_desc* d) { return ((igemm_workspace_floats(d) + 63) / 64) * 64 * sizeof(float); }
+// a depthwise desc is checked (served: accepted = CNN_CONV2D_DEPTHWISE; refused: 0) before the side stream is asked for, so that the
+// answer needs no device; every other desc is checked by the calls below as before
+int check_if_depthwise(const char* who, const cnn_conv2d_desc* d, int accepted) {
+    return (d && is_depthwise(d)) ? check_desc(who, d, accepted) : CNN_AMD_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -93,6 +98,7 @@ int cnn_amd_side_stream_join(void* stream) {
 
 int cnn_conv2d_backward(const cnn_conv2d_desc* d, const float* x, const float* dy, const float* w, float* gw, float* gb,
                         float* dx, float divisor, void* ws, size_t ws_bytes, void* stream, int defer_join) {
+    if (int rc = check_if_depthwise("cnn_conv2d_backward", d, CNN_CONV2D_DEPTHWISE)) return rc;
     CNN_REQUIRE(d && x && dy && w && gw && dx && ws, "cnn_conv2d_backward: null pointer");
     const size_t dbytes = dgrad_region_bytes(d);
     if (ws_bytes < dbytes + 256)
@@ -127,6 +133,7 @@ int cnn_conv2d_backward_prepared(const cnn_conv2d_desc* d, const float* x, const
 int cnn_conv2d_backward_prepared_relu(const cnn_conv2d_desc* d, const float* x, const float* dy, const void* prepared_dgrad,
                                       const float* relu_below, float* gw, float* gb, float* dx, float divisor, void* ws,
                                       size_t ws_bytes, void* stream, int defer_join) {
+    if (int rc = check_if_depthwise("cnn_conv2d_backward_prepared", d, 0)) return rc;
     CNN_REQUIRE(d && x && dy && prepared_dgrad && gw && dx && ws, "cnn_conv2d_backward_prepared: null pointer");
     SideStream* side = nullptr;
     if (int rc = get_side(&side)) return rc;
@@ -165,6 +172,7 @@ int cnn_conv2d_backward_prepared_relu(const cnn_conv2d_desc* d, const float* x, 
  * reduction recorded for the join -- for callers that obtain the data gradients of several layers another way */
 int cnn_conv2d_backward_weight_side(const cnn_conv2d_desc* d, const float* x, const float* dy, float* gw, float* gb, float divisor, void* ws,
                                     size_t ws_bytes, void* stream) {
+    if (int rc = check_if_depthwise("cnn_conv2d_backward_weight_side", d, CNN_CONV2D_DEPTHWISE)) return rc;
     CNN_REQUIRE(d && x && dy && gw && ws, "cnn_conv2d_backward_weight_side: null pointer");
     SideStream* side = nullptr;
     if (int rc = get_side(&side)) return rc;
@@ -182,6 +190,7 @@ int cnn_conv2d_backward_weight_side(const cnn_conv2d_desc* d, const float* x, co
 int cnn_conv2d_backward_pooled2_prepared(const cnn_conv2d_desc* d, const float* x, const float* dpool, const int32_t* mask,
                                          const float* pooled, const void* prepared_dgrad, float* gw, float* gb, float* dx,
                                          float divisor, void* ws, size_t ws_bytes, void* stream, int defer_join) {
+    if (int rc = check_if_depthwise("cnn_conv2d_backward_pooled2_prepared", d, 0)) return rc;
     CNN_REQUIRE(d && x && dpool && mask && prepared_dgrad && gw && dx && ws, "cnn_conv2d_backward_pooled2_prepared: null pointer");
     SideStream* side = nullptr;
     if (int rc = get_side(&side)) return rc;

@@ -50,6 +50,8 @@ ImageKind copy_of_w(const cnn_conv2d_desc*) { return IMAGE_COPY_OF_W; }
 size_t filter_floats(const cnn_conv2d_desc* d) { return (size_t)d->Co * d->Ci * d->k * d->k; }
 size_t direct_floats(const cnn_conv2d_desc*) { return 1024; }  // packed filter copies of the first-layer kernels (conv_direct.hip)
 bool always(const cnn_conv2d_desc*) { return true; }
+ImageKind no_image(const cnn_conv2d_desc*) { return IMAGE_NONE; }
+size_t no_floats(const cnn_conv2d_desc*) { return 0; }
 
 int thin_pack_jobs(int n, const ConvPrepJob* jobs, hipStream_t s) {
     for (int i = 0; i < n; ++i)
@@ -64,8 +66,11 @@ int run_rows(const ConvCall& c, int mode) {
                     mode == MODE_FWD ? nullptr : c.out2, c.s);
 }
 
-// ---- forward: direct -> 1x1 -> rows -> fwd_rd -> stem -> implicit GEMM ----
+// ---- forward: depthwise (iff the desc carries the flag: no later row ever sees such a desc, see facts_of) -> direct -> 1x1 -> rows ->
+// fwd_rd -> stem -> implicit GEMM ----
 const Route kFwdRoutes[] = {
+    /* depthwise */ {is_depthwise, NEED_NOTHING, no_image, no_floats, nullptr,
+     [](const ConvCall& c) { return dw_run(c.d, MODE_FWD, c.in, c.w, c.bias, c.out, c.out2, c.s); }, false},
     /* direct */ {direct_conv_supported, NEED_NOTHING,  // (picks its packed or its plain kernel by the buffer itself)
      [](const cnn_conv2d_desc* d) { return direct_fwd_pk_ok(d) ? IMAGE_PACKED : IMAGE_NONE; }, direct_floats, direct_prepare_batch,
      [](const ConvCall& c) { return direct_conv_forward(c.d, c.in, c.w, c.bias, c.out, c.out2, c.ws, c.ws_bytes, c.s, c.prepared); }, true},
@@ -85,8 +90,11 @@ const Route kFwdRoutes[] = {
      [](const ConvCall& c) { return igemm_run(c.who, c.d, MODE_FWD, c.in, c.w, c.bias, c.out, c.out2, c.ws, c.ws_bytes, c.s, c.prepared); }, false},
 };
 
-// ---- data gradient: direct -> 1x1 -> thin (packed, then scalar operands) -> rows -> dgrad_rd -> pk_s2 -> implicit GEMM ----
+// ---- data gradient: depthwise (as above) -> direct -> 1x1 -> thin (packed, then scalar operands) -> rows -> dgrad_rd -> pk_s2 ->
+// implicit GEMM ----
 const Route kDgradRoutes[] = {
+    /* depthwise */ {is_depthwise, NEED_NOTHING, no_image, no_floats, nullptr,
+     [](const ConvCall& c) { return dw_run(c.d, MODE_DGRAD, c.in, c.w, nullptr, c.out, c.out2, c.s); }, false},
     /* direct */ {direct_conv_supported, NEED_NOTHING,
      [](const cnn_conv2d_desc* d) { return direct_dgrad_pk_ok(d) ? IMAGE_PACKED : IMAGE_NONE; }, direct_floats, direct_prepare_batch,
      [](const ConvCall& c) {  // the first-layer kernels have no masked epilogue: same result from the ReLU kernel
@@ -120,7 +128,7 @@ const Route kDgradRoutes[] = {
 };
 
 constexpr int kNumFwdRoutes = (int)(sizeof(kFwdRoutes) / sizeof(kFwdRoutes[0])), kNumDgradRoutes = (int)(sizeof(kDgradRoutes) / sizeof(kDgradRoutes[0]));
-constexpr int kMaxRoutes = 8;
+constexpr int kMaxRoutes = 9;
 static_assert(kNumFwdRoutes <= kMaxRoutes && kNumDgradRoutes <= kMaxRoutes, "RouteFacts holds kMaxRoutes rows per pass");
 const Route* routes(int mode) { return mode == MODE_FWD ? kFwdRoutes : kDgradRoutes; }
 int num_routes(int mode) { return mode == MODE_FWD ? kNumFwdRoutes : kNumDgradRoutes; }
@@ -160,6 +168,7 @@ const RouteFacts& facts_of(const cnn_conv2d_desc* d) {
             f.pass[mode].image[i] = r.image(d);
             f.pass[mode].floats[i] = r.floats(d);
             if (f.pass[mode].floats[i] > f.prepared_floats) f.prepared_floats = f.pass[mode].floats[i];
+            if (i == 0 && is_depthwise(d)) break;  // (the dense families' predicates and planners never see a depthwise desc)
         }
     return f;
 }
@@ -180,7 +189,7 @@ int resolve(int mode, const RouteFacts& f, const void* buf, size_t bytes) {
 
 // prepared: c.ws is a buffer of cnn_conv2d_prepared_bytes(d) bytes holding the route's image (c.ws_bytes is filled in here)
 int run_pass(int mode, ConvCall c) {
-    if (int rc = check_desc(c.who, c.d)) return rc;
+    if (int rc = check_desc(c.who, c.d, c.prepared ? 0 : CNN_CONV2D_DEPTHWISE)) return rc;
     const RouteFacts& f = facts_of(c.d);
     if (c.prepared) c.ws_bytes = prepared_bytes_of(f);
     const int i = resolve(mode, f, c.ws, c.ws_bytes);

@@ -13,17 +13,30 @@ namespace cnn_amd {
 
 enum { MODE_FWD = 0, MODE_DGRAD = 1 };  // the `mode` argument below: forward / data gradient
 
-// every C entry point that takes a desc starts with this
-inline int check_desc(const char* who, const cnn_conv2d_desc* d) {
+// every C entry point that takes a desc starts with this.  accepted_extra: the flag bits beyond the pool-mask one that the entry
+// serves (CNN_CONV2D_DEPTHWISE for the entries listed in include/cnn_amd.h, 0 everywhere else: those refuse a depthwise desc here,
+// before any launch)
+inline int check_desc(const char* who, const cnn_conv2d_desc* d, int accepted_extra = 0) {
     CNN_REQUIRE(d != nullptr, "%s: desc is null", who);
     CNN_REQUIRE(d->B > 0 && d->Ci > 0 && d->H > 0 && d->W > 0 && d->Co > 0 && d->k > 0 && d->s > 0 && d->pad >= 0,
                 "%s: bad desc B=%d Ci=%d H=%d W=%d Co=%d k=%d s=%d pad=%d", who, d->B, d->Ci, d->H, d->W, d->Co, d->k,
                 d->s, d->pad);
     CNN_REQUIRE(d->H + 2 * d->pad >= d->k && d->W + 2 * d->pad >= d->k, "%s: kernel %d larger than padded input", who,
                 d->k);
-    CNN_REQUIRE((d->flags & ~CNN_CONV2D_POOL_MASK_PACKED) == 0, "%s: unknown desc flags 0x%x", who, (unsigned)d->flags);
+    CNN_REQUIRE((d->flags & ~(CNN_CONV2D_POOL_MASK_PACKED | CNN_CONV2D_DEPTHWISE)) == 0, "%s: unknown desc flags 0x%x", who, (unsigned)d->flags);
+    if (d->flags & CNN_CONV2D_DEPTHWISE) {
+        CNN_REQUIRE((accepted_extra & CNN_CONV2D_DEPTHWISE) != 0, "%s: no depthwise path (CNN_CONV2D_DEPTHWISE is served by the plain forward / backward entries only)", who);
+        CNN_REQUIRE(d->flags == CNN_CONV2D_DEPTHWISE, "%s: depthwise desc with other flags 0x%x", who, (unsigned)d->flags);
+        CNN_REQUIRE(d->Co == d->Ci, "%s: depthwise needs Co == Ci (Ci=%d Co=%d)", who, d->Ci, d->Co);
+        // the depthwise kernels index in 32 bits
+        const double Ho = cnn_conv2d_out_dim(d->H, d->k, d->s, d->pad), Wo = cnn_conv2d_out_dim(d->W, d->k, d->s, d->pad);
+        const double planes = (double)d->B * d->Ci;  // (doubles: the products of four ints overflow 64 bits)
+        CNN_REQUIRE(planes * d->H * d->W < 2147483648.0 && planes * Ho * Wo < 2147483648.0,
+                    "%s: depthwise tensors must have fewer than 2^31 elements (B=%d C=%d %dx%d)", who, d->B, d->Ci, d->H, d->W);
+    }
     return CNN_AMD_OK;
 }
+inline bool is_depthwise(const cnn_conv2d_desc* d) { return (d->flags & CNN_CONV2D_DEPTHWISE) != 0; }
 
 // one filter-preparation job of cnn_conv2d_prepare_filters: layer `layer` of the call, its image for `mode` goes to `image`.
 // A family's batch preparer gets the jobs that resolved to it (conv_dispatch.hip) and serves them in one launch.
@@ -147,6 +160,12 @@ int wgrad_rd_launch(const cnn_conv2d_desc* d, const float* x, const float* dy, f
 int wgrad_rd_pooled_slots(const cnn_conv2d_desc* d);
 int wgrad_rd_launch_pooled(const cnn_conv2d_desc* d, const float* x, const float* dpool, const int32_t* mask, const float* pooled,
                            float* slabs, hipStream_t s);
+
+// ---- conv_depthwise.hip: CNN_CONV2D_DEPTHWISE, every pass (VALU, HBM-bound).  w is [C][1][k][k] ----
+// forward: out = y (nullable when out2 is given), out2 = relu(y) (nullable); data gradient: out = dx, out2 = the ReLU output below (nullable)
+int dw_run(const cnn_conv2d_desc* d, int mode, const float* in, const float* w, const float* bias, float* out, float* out2, hipStream_t s);
+int dw_wgrad_slots(const cnn_conv2d_desc* d);  // batch slabs of [C][k*k | 1] floats (planned by num_cus())
+int dw_wgrad_launch(const cnn_conv2d_desc* d, const float* x, const float* dy, float* slabs, hipStream_t s);
 
 // ---- conv_wgrad.hip, for conv_backward.hip: record (true) / launch at once (false) the final slab reductions of this thread ----
 void wgrad_defer_reduce(bool on);

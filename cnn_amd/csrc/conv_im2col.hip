@@ -172,6 +172,10 @@ extern "C" {
 
 size_t cnn_conv2d_im2col_workspace_bytes(const cnn_conv2d_desc* d) {
     if (!d) return 0;
+    if (is_depthwise(d)) {
+        fail(CNN_AMD_E_BADARG, "cnn_conv2d_im2col_workspace_bytes: no depthwise path");
+        return 0;
+    }
     const Geo g = make_geo(d);
     const size_t per_img = ((size_t)g.K * g.P + (size_t)g.Co * g.K) * sizeof(float);
     const size_t fixed = (size_t)g.Co * g.K * sizeof(float) + 256;

@@ -796,6 +796,7 @@ const SlabFamily kSlabFamilies[] = {
     /* stem */ {stem_wgrad_slots, stem_wgrad_launch, 49, nullptr},
 };
 size_t slab_floats(const cnn_conv2d_desc* d, int taps) { return (size_t)d->Co * (d->Ci * taps + 1); }
+size_t dw_slab_floats(const cnn_conv2d_desc* d) { return (size_t)d->Ci * (d->k * d->k + 1); }  // depthwise: [C][k*k | 1]
 // slab rows a family's workspace holds: its slabs, then the stage-1 scratch of a reduction of more than 64 of them
 size_t slab_rows(int slots) { return (size_t)(slots + (slots + 63) / 64); }
 
@@ -839,10 +840,15 @@ int wgrad_flush_reduces(hipStream_t s) { return flush_reduces(s); }
 extern "C" {
 
 size_t cnn_conv2d_workspace_bytes(const cnn_conv2d_desc* d) {
-    if (check_desc("cnn_conv2d_workspace_bytes", d)) return 0;
+    if (check_desc("cnn_conv2d_workspace_bytes", d, CNN_CONV2D_DEPTHWISE)) return 0;
     static thread_local DescMemo memo;
     size_t known = 0;
     if (memo.find(d, &known)) return known;
+    if (is_depthwise(d)) {  // its batch slabs + the reduction's scratch; forward and data gradient need nothing
+        const size_t bytes = (slab_rows(dw_wgrad_slots(d)) * dw_slab_floats(d) + 64) * sizeof(float);
+        memo.put(d, bytes);
+        return bytes;
+    }
     WPlan pl;
     size_t wg = 0;
     if (make_wplan("cnn_conv2d_workspace_bytes", d, &pl) == CNN_AMD_OK) wg = pl.part_floats + pl.bias_floats + pl.tmp_floats;
@@ -899,10 +905,19 @@ int cnn_amd_flush_reduces(void* stream) { return flush_reduces(as_stream(stream)
 
 int cnn_conv2d_backward_weight(const cnn_conv2d_desc* d, const float* x, const float* dy, float* gw, float* gb,
                                float divisor, void* ws, size_t ws_bytes, void* stream) {
-    if (int rc = check_desc("cnn_conv2d_backward_weight", d)) return rc;
+    if (int rc = check_desc("cnn_conv2d_backward_weight", d, CNN_CONV2D_DEPTHWISE)) return rc;
     CNN_REQUIRE(x && dy && gw, "cnn_conv2d_backward_weight: null pointer");
     CNN_REQUIRE(divisor != 0.f, "cnn_conv2d_backward_weight: divisor is 0");
     CNN_REQUIRE(ws != nullptr, "cnn_conv2d_backward_weight: workspace is null");
+    if (is_depthwise(d)) {  // batch slabs of [C][k*k | 1], summed and divided like every slab family's
+        const int slots = dw_wgrad_slots(d);
+        const size_t n = dw_slab_floats(d), need = slab_rows(slots) * n * sizeof(float);
+        if (ws_bytes < need) return fail(CNN_AMD_E_WORKSPACE, "cnn_conv2d_backward_weight: workspace %zu B < %zu B", ws_bytes, need);
+        if (int rc = dw_wgrad_launch(d, x, dy, (float*)ws, as_stream(stream))) return rc;
+        char tag[160];
+        snprintf(tag, sizeof(tag), CONV_TAG(d));
+        return reduce_slabs(as_stream(stream), (float*)ws, slots, n, (float*)ws + (size_t)slots * n, gw, divisor, tag, d->k * d->k, gb);
+    }
     for (const SlabFamily& f : kSlabFamilies) {
         if (f.wanted && !f.wanted(d)) continue;
         const int slots = f.slots(d);

@@ -248,6 +248,39 @@ public:
     size_t delta_floats() const { return delta_buf.sample_len * delta_buf.views.size(); }
 };
 
+// addition: depthwise convolution (one k x k filter per channel, C -> C; the 3x3 half of a depthwise-separable block, the other half
+// is Conv2D with a 1x1 kernel).  A desc with CNN_CONV2D_DEPTHWISE through the plain C entry points: no fusion wiring, no prepared
+// filters, no tuning -- to a container it is an unfused layer with a parameter block.  Parameters: weights [C][1][k][k] then bias [C],
+// initialised by Conv2D's scheme (the layer's own engine, seed 212, bias first, N(0, 1) / random_times).
+class DepthwiseConv2D : public Layer {
+private:
+    const int channels, kernel_size, stride, padding;
+    std::default_random_engine seed;
+    ParamBlock pb;
+    bool grads_ready = false;
+    BatchBuffer out_buf, delta_buf, in_stage, delta_stage;
+    const data_type* saved_input = nullptr;
+    std::vector<tensor> saved_input_tensors;
+    Workspace workspace;
+    size_t weight_count() const { return (size_t)channels * kernel_size * kernel_size; }
+    cnn_conv2d_desc desc(int B) const { return cnn_conv2d_desc{B, channels, in.H, in.W, channels, kernel_size, stride, padding, CNN_CONV2D_DEPTHWISE}; }
+
+public:
+    DepthwiseConv2D(std::string _name, const int _channels, const int _kernel_size = 3, const int _stride = 1, const int _padding = 1);
+    std::vector<tensor> forward(const std::vector<tensor>& input) override;
+    std::vector<tensor> backward(std::vector<tensor>& delta) override;
+    void update_gradients(const data_type learning_rate = 1e-4) override;
+    void save_weights(std::ofstream& writer) const override;
+    void load_weights(std::ifstream& reader) override;
+    size_t param_count() const override { return weight_count() + (size_t)channels; }
+    void decay_ranges(bool bias_and_norm, RangeList& out) const override { out.emplace_back((size_t)0, bias_and_norm ? param_count() : weight_count()); }
+    void param_tensors(RangeList& out) const override {
+        out.emplace_back((size_t)0, weight_count());
+        out.emplace_back(weight_count(), param_count());
+    }
+    void bind_arena(data_type* params_dev, data_type* grads_dev) override;
+};
+
 class MaxPool2D : public Layer {
 private:
     const int kernel_size, step, padding;
@@ -904,6 +937,9 @@ void build_vgg11(Sequential& net, const int num_classes = 3, const bool batch_no
 // 7x7 s2 p3 stem, MaxPool2D(2,2), four stages of four convolutions (3x3 s1 p1 inside a stage; stage entries 3x3 s2 p1,
 // 1x1 s2, 3x3 s2 p1), BatchNorm2D + ReLU after every convolution, LinearLayer(512*7*7 -> classes).
 void build_resnet18(Sequential& net, const int num_classes = 3, const bool batch_norm = true);
+// MobileNet-V1-shaped (cnn_amd/stacks.py mobilenet_v1): 3x3 s2 p1 stem 3->32, the 13 blocks of DepthwiseConv2D(3x3, stride 1 or 2) +
+// Conv2D(1x1), BatchNorm2D + ReLU after each of the two, MaxPool2D(7,7) in the average pool's place, LinearLayer(1024 -> classes).
+void build_mobilenet_v1(Sequential& net, const int num_classes = 3, const bool batch_norm = true);
 
 }  // namespace architectures
 

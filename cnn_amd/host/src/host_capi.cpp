@@ -72,6 +72,9 @@ void* cnnh_seq_create(int in_channels, int classes) {
 void cnnh_seq_add_conv(void* hv, const char* name, int ci, int co, int k, int stride, int pad) {
     ((Handle*)hv)->net->add(new Conv2D(name, ci, co, k, stride, pad));
 }
+void cnnh_seq_add_dwconv(void* hv, const char* name, int channels, int k, int stride, int pad) {
+    ((Handle*)hv)->net->add(new DepthwiseConv2D(name, channels, k, stride, pad));
+}
 void cnnh_seq_add_bn(void* hv, const char* name, int channels) { ((Handle*)hv)->net->add(new BatchNorm2D(name, channels)); }
 void cnnh_seq_add_dropout(void* hv, const char* name, float p) { ((Handle*)hv)->net->add(new Dropout(name, p)); }
 void cnnh_seq_add_relu(void* hv, const char* name) { ((Handle*)hv)->net->add(new ReLU(name)); }

@@ -432,6 +432,69 @@ void Conv2D::load_weights(std::ifstream& reader) {
 int Conv2D::get_params_num() const { return (params_for_one_kernel + 1) * out_channels; }
 
 // ---------------------------------------------------------------------------------------------------------------
+// DepthwiseConv2D
+DepthwiseConv2D::DepthwiseConv2D(std::string _name, const int _channels, const int _kernel_size, const int _stride, const int _padding)
+    : Layer(_name), channels(_channels), kernel_size(_kernel_size), stride(_stride), padding(_padding) {
+    assert(_kernel_size >= 1 && _channels > 0 && _stride > 0 && _padding >= 0);
+    in.C = channels;
+    pb.allocate(param_count());
+    // Conv2D's scheme: bias first, then the filters, stored weights-then-bias
+    std::vector<data_type> host(pb.n);
+    this->seed.seed(212);
+    std::normal_distribution<float> engine(0.0, 1.0);
+    data_type* bias = host.data() + weight_count();
+    for (int c = 0; c < channels; ++c) bias[c] = engine(this->seed) / random_times;
+    for (size_t i = 0; i < weight_count(); ++i) host[i] = engine(this->seed) / random_times;
+    pb.upload(host.data());
+}
+
+void DepthwiseConv2D::bind_arena(data_type* params_dev, data_type* grads_dev) { pb.adopt(params_dev, grads_dev, /*zero_grads=*/false); }
+
+std::vector<tensor> DepthwiseConv2D::forward(const std::vector<tensor>& input) {
+    Tensor3D::device_work_enqueued();
+    const int B = (int)input.size();
+    const int H = input[0]->H, W = input[0]->W;
+    const int out_H = cnn_conv2d_out_dim(H, kernel_size, stride, padding);
+    const int out_W = cnn_conv2d_out_dim(W, kernel_size, stride, padding);
+    static_output(out_buf, B, Shape{input[0]->C, H, W}, Shape{channels, out_H, out_W}, /*fatal=*/true);
+    const cnn_conv2d_desc d = desc(B);
+    const size_t need = no_grad ? cnn_conv2d_workspace_bytes(&d) : cnn_conv2d_backward_workspace_bytes(&d);
+    if (need == 0) must(1, "cnn_conv2d_workspace_bytes");
+    workspace.reserve(need);
+    const data_type* x = batch_device_pointer(input, in_stage, name);
+    if (!no_grad) {
+        saved_input = x;
+        saved_input_tensors = input;
+    }
+    must(cnn_conv2d_forward(&d, x, pb.params, pb.params + weight_count(), out_buf.base, workspace.ptr, workspace.bytes, stream), "cnn_conv2d_forward");
+    return first_n(output, B);
+}
+
+std::vector<tensor> DepthwiseConv2D::backward(std::vector<tensor>& delta) {
+    Tensor3D::device_work_enqueued();
+    const int B = (int)delta.size();
+    assert(saved_input != nullptr && "backward without a recorded forward (no_grad?)");
+    const cnn_conv2d_desc d = desc(B);
+    if (delta_buf.empty()) delta_buf.allocate(batch, channels, in.H, in.W, name + "_delta");
+    workspace.reserve(cnn_conv2d_backward_workspace_bytes(&d));
+    const data_type* dy = batch_device_pointer(delta, delta_stage, name + "_dy");
+    // gradients averaged over the batch that ran (Conv2D's divisor), weight / bias gradient beside the data gradient, joined here
+    must(cnn_conv2d_backward(&d, saved_input, dy, pb.params, pb.grads, pb.grads + weight_count(), delta_buf.base, (float)B, workspace.ptr,
+                             workspace.bytes, stream, /*defer_join=*/0),
+         "cnn_conv2d_backward");
+    grads_ready = true;
+    return first_n(delta_buf.views, B);
+}
+
+void DepthwiseConv2D::update_gradients(const data_type learning_rate) {
+    assert(grads_ready);
+    must(cnn_sgd_update(pb.params, pb.grads, param_count(), learning_rate, 1.f, stream), "cnn_sgd_update");
+}
+
+void DepthwiseConv2D::save_weights(std::ofstream& writer) const { pb.save(writer); }
+void DepthwiseConv2D::load_weights(std::ifstream& reader) { pb.load(reader); }
+
+// ---------------------------------------------------------------------------------------------------------------
 // MaxPool2D
 MaxPool2D::~MaxPool2D() {
     if (mask) cnn_device_free(mask);

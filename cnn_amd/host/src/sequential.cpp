@@ -902,6 +902,14 @@ struct StackBuilder {
         H = cnn_conv2d_out_dim(H, k, s, pad);
         W = cnn_conv2d_out_dim(W, k, s, pad);
     }
+    void dwconv(int k, int s, int pad) {  // (numbered with the convolutions, like cnn_amd/hostapi.py)
+        const std::string id = std::to_string(++n_conv);
+        net.add(new DepthwiseConv2D("dw_layer_" + id, C, k, s, pad));
+        if (batch_norm) net.add(new BatchNorm2D("bn_layer_" + id, C));
+        net.add(new ReLU("relu_layer_" + id));
+        H = cnn_conv2d_out_dim(H, k, s, pad);
+        W = cnn_conv2d_out_dim(W, k, s, pad);
+    }
     void pool(int k, int step) {
         net.add(new MaxPool2D("max_pool_" + std::to_string(++n_pool), k, step));
         H = cnn_maxpool2d_out_dim(H, k, step);
@@ -932,5 +940,18 @@ void architectures::build_resnet18(Sequential& net, const int num_classes, const
     for (int i = 0; i < 3; ++i) b.conv(256, 3, 1, 1);
     b.conv(512, 3, 2, 1);
     for (int i = 0; i < 3; ++i) b.conv(512, 3, 1, 1);
+    b.linear(num_classes);
+}
+
+void architectures::build_mobilenet_v1(Sequential& net, const int num_classes, const bool batch_norm) {
+    StackBuilder b{net, batch_norm};
+    b.conv(32, 3, 2, 1);
+    const int chans[13] = {64, 128, 128, 256, 256, 512, 512, 512, 512, 512, 512, 1024, 1024};
+    const int strides[13] = {1, 2, 1, 2, 1, 2, 1, 1, 1, 1, 1, 2, 1};
+    for (int i = 0; i < 13; ++i) {
+        b.dwconv(3, strides[i], 1);
+        b.conv(chans[i], 1, 1, 0);
+    }
+    b.pool(7, 7);
     b.linear(num_classes);
 }

@@ -19,6 +19,7 @@ SIGNATURES = {
     "cnnh_net_create_ex": (C.c_void_p, [C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "cnnh_seq_create": (C.c_void_p, [C.c_int, C.c_int]),
     "cnnh_seq_add_conv": (None, [C.c_void_p, C.c_char_p] + [C.c_int] * 5),
+    "cnnh_seq_add_dwconv": (None, [C.c_void_p, C.c_char_p] + [C.c_int] * 4),
     "cnnh_seq_add_bn": (None, [C.c_void_p, C.c_char_p, C.c_int]),
     "cnnh_seq_add_relu": (None, [C.c_void_p, C.c_char_p]),
     "cnnh_seq_add_dropout": (None, [C.c_void_p, C.c_char_p, C.c_float]),
@@ -700,6 +701,9 @@ def _layer_names(spec):
         if kind == "conv":
             n_conv += 1
             names.append(f"conv_layer_{n_conv}")
+        elif kind == "dwconv":  # (counted with the convolutions: the layers behind it carry its number)
+            n_conv += 1
+            names.append(f"dw_layer_{n_conv}")
         elif kind == "bn":
             names.append(f"bn_layer_{n_conv}")
         elif kind == "relu":
@@ -731,6 +735,8 @@ class HostSequential(HostNet):
             nm = name.encode()
             if item[0] == "conv":
                 self.lib.cnnh_seq_add_conv(h, nm, ent["in"][0], item[1], item[2], item[3], item[4])
+            elif item[0] == "dwconv":
+                self.lib.cnnh_seq_add_dwconv(h, nm, ent["in"][0], item[1], item[2], item[3])
             elif item[0] == "bn":
                 self.lib.cnnh_seq_add_bn(h, nm, ent["in"][0])
             elif item[0] == "relu":

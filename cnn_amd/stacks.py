@@ -4,6 +4,7 @@ Conv2D / BatchNorm2D / ReLU / MaxPool2D / LinearLayer.  Pure host data: no devic
 
 A spec is a list of tuples
     ("conv", Co, k, stride, pad)   Conv2D(name, Ci, Co, k, stride[, pad])      architectures.h:69 (+ the padding extension)
+    ("dwconv", k, stride, pad)     DepthwiseConv2D(name, C, k, stride, pad)    (addition: one k x k filter per channel, C -> C)
     ("bn",)                        BatchNorm2D(name, C)                        architectures.h:167
     ("relu",)                      ReLU(name)                                  architectures.h:109
     ("pool", k, step)              MaxPool2D(name, k, step)                    architectures.h:96
@@ -74,6 +75,32 @@ def resnet18(classes=3, batch_norm=True):
     return spec
 
 
+def mobilenet_v1(classes=3, batch_norm=True):
+    """The convolution SHAPES of MobileNet-V1 (width 1.0) as a strictly sequential list: 3x3 stride-2 pad-1 stem 3->32 (224 -> 112),
+    then the 13 depthwise-separable blocks -- a 3x3 depthwise convolution (stride 2 in blocks 2, 4, 6 and 12) and a 1x1 convolution
+    to 64, 128, 128, 256, 256, 512, 512 x 5, 1024, 1024 channels, BatchNorm2D and ReLU after each of the two -- down to 1024 x 7 x 7;
+    MaxPool(7,7) stands in for the network's average pool (the container has none), Linear(1024 -> classes).  Not in STACKS: the
+    benchmark and the oracle-backed stack tests key on that table, and the oracle has no depthwise layer."""
+    spec = []
+
+    def act():
+        if batch_norm:
+            spec.append(("bn",))
+        spec.append(("relu",))
+
+    spec.append(("conv", 32, 3, 2, 1))
+    act()
+    blocks = [(64, 1), (128, 2), (128, 1), (256, 2), (256, 1), (512, 2)] + [(512, 1)] * 5 + [(1024, 2), (1024, 1)]
+    for co, s in blocks:
+        spec.append(("dwconv", 3, s, 1))
+        act()
+        spec.append(("conv", co, 1, 1, 0))
+        act()
+    spec.append(("pool", 7, 7))
+    spec.append(("linear", classes))
+    return spec
+
+
 STACKS = {"alexnet": alexnet, "vgg11": vgg11, "resnet18": resnet18}
 # per-GPU batch of the BASELINE configuration each stack is quoted on (configs[1], [3], [4] = 512 over 8 GPUs)
 DEFAULT_BATCH = {"alexnet": 256, "vgg11": 128, "resnet18": 64}
@@ -90,6 +117,10 @@ def walk(spec, C=3, H=224, W=224):
             _, co, k, s, p = item
             ent.update(Co=co, k=k, s=s, pad=p, params=co * C * k * k + co)
             C, H, W = co, (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+        elif kind == "dwconv":  # weights [C][1][k][k], then bias [C]
+            _, k, s, p = item
+            ent.update(k=k, s=s, pad=p, params=C * k * k + C)
+            H, W = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
         elif kind == "bn":
             ent.update(params=4 * C)
         elif kind == "relu":
@@ -126,6 +157,9 @@ def train_flops_per_image(spec, H=224, W=224):
         if e["kind"] == "conv":
             co, ho, wo = e["out"]
             fl += 2.0 * co * ho * wo * e["in"][0] * e["k"] ** 2
+        elif e["kind"] == "dwconv":
+            c, ho, wo = e["out"]
+            fl += 2.0 * c * ho * wo * e["k"] ** 2
         elif e["kind"] == "linear":
             fl += 2.0 * e["n_in"] * e["n_out"]
     return 3.0 * fl
@@ -146,6 +180,10 @@ def he_init(layout, seed):
             ci, co, k = e["in"][0], e["Co"], e["k"]
             parts.append(rs.standard_normal(co * ci * k * k) * np.sqrt(2.0 / (ci * k * k)))
             parts.append(rs.standard_normal(co) * 0.05)
+        elif kind == "dwconv":  # fan-in k*k
+            c, k = e["in"][0], e["k"]
+            parts.append(rs.standard_normal(c * k * k) * np.sqrt(2.0 / (k * k)))
+            parts.append(rs.standard_normal(c) * 0.05)
         elif kind == "bn":
             c = e["in"][0]
             parts += [1.0 + 0.1 * rs.standard_normal(c), 0.1 * rs.standard_normal(c), np.zeros(c), np.zeros(c)]

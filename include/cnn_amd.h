@@ -80,11 +80,18 @@ typedef struct {
     int B, Ci, H, W; /* input  batch / channels / height / width */
     int Co, k, s;    /* filters, kernel edge (any k >= 1; the reference asserts odd >= 3), stride */
     int pad;         /* zero padding on each side (extension; the reference is fixed at 0, architectures.h:59) */
-    int flags;       /* 0, or CNN_CONV2D_POOL_MASK_PACKED (ABI version 2; only the fused Conv2D -> ReLU -> MaxPool2D family reads it) */
+    int flags;       /* 0, CNN_CONV2D_POOL_MASK_PACKED (ABI version 2; only the fused Conv2D -> ReLU -> MaxPool2D family reads it) or CNN_CONV2D_DEPTHWISE */
 } cnn_conv2d_desc;
 /* flags bit: the pool mask the fused first-block entry points (cnn_conv2d_relu_maxpool2_forward*, cnn_conv2d_backward_*pooled2*)
  * write and read is ONE BYTE per window instead of an int32 flat index -- see cnn_conv2d_pool_mask_packed_supported below */
 #define CNN_CONV2D_POOL_MASK_PACKED 1
+/* flags bit: DEPTHWISE convolution (one filter per channel).  Co == Ci = C, w is [C][1][k][k] (C*k*k floats), bias [C]:
+ * y[b][c] = bias[c] + x[b][c] (*) w[c];  gw[c] = (sum_b sum_pq dy * x) / divisor, gb[c] = (sum dy) / divisor;  dx is the gather form
+ * (rows / columns no window covers come out +0).  Served by cnn_conv2d_workspace_bytes, cnn_conv2d_forward, _forward_relu,
+ * _backward_data, _backward_data_relu, _backward_weight, _backward_weight_side, _backward_workspace_bytes and cnn_conv2d_backward;
+ * every other entry that takes a desc refuses the flag (a non-zero status, or 0 from size queries and predicates; the error text
+ * says "depthwise").  Both tensors must have fewer than 2^31 elements.  (Value 2 is NOT a flag.) */
+#define CNN_CONV2D_DEPTHWISE 4
 
 /* scratch needed by ANY of the three MFMA entry points below for this geometry */
 size_t cnn_conv2d_workspace_bytes(const cnn_conv2d_desc* d);
