@@ -20,6 +20,10 @@
 // Padding is zeros in registers, never an out-of-tensor read.  All indices are 32-bit: check_desc refuses tensors of 2^31 elements.
 #include "conv_families.h"
 
+// the geometry tag of a specialised launch names the code bodies it chose (the kernel name in front of `|` does not): " off<OFF> v<vst|vdy>"
+// (dw3_rows, dw3_wgrad) or " pp<PP> v<vst>" (dw3_dgrad_s2).  tests/depthwise_ref.launch_variants is the same choice on the CPU.
+#define DW_TAG(d, key, which, vec) CONV_TAG_FMT " " key "%d v%d", CONV_TAG_ARGS(d), (int)(which), (int)(vec)
+
 namespace cnn_amd {
 namespace {
 
@@ -414,10 +418,10 @@ template <int S>
 int launch_rows(const cnn_conv2d_desc* d, const char* name, const DwRows& p, int off, hipStream_t s) {
     const unsigned grid = (p.items + kDwBlock - 1) / kDwBlock;
     switch (off) {
-        case 0: CNN_KLAUNCH(s, name, (dw3_rows<S, 0><<<grid, kDwBlock, 0, s>>>(p)), CONV_TAG(d)); break;
-        case 1: CNN_KLAUNCH(s, name, (dw3_rows<S, 1><<<grid, kDwBlock, 0, s>>>(p)), CONV_TAG(d)); break;
-        case 2: CNN_KLAUNCH(s, name, (dw3_rows<S, 2><<<grid, kDwBlock, 0, s>>>(p)), CONV_TAG(d)); break;
-        default: CNN_KLAUNCH(s, name, (dw3_rows<S, -1><<<grid, kDwBlock, 0, s>>>(p)), CONV_TAG(d)); break;
+        case 0: CNN_KLAUNCH(s, name, (dw3_rows<S, 0><<<grid, kDwBlock, 0, s>>>(p)), DW_TAG(d, "off", off, p.vst)); break;
+        case 1: CNN_KLAUNCH(s, name, (dw3_rows<S, 1><<<grid, kDwBlock, 0, s>>>(p)), DW_TAG(d, "off", off, p.vst)); break;
+        case 2: CNN_KLAUNCH(s, name, (dw3_rows<S, 2><<<grid, kDwBlock, 0, s>>>(p)), DW_TAG(d, "off", off, p.vst)); break;
+        default: CNN_KLAUNCH(s, name, (dw3_rows<S, -1><<<grid, kDwBlock, 0, s>>>(p)), DW_TAG(d, "off", off, p.vst)); break;
     }
     return CNN_AMD_OK;
 }
@@ -425,10 +429,10 @@ int launch_rows(const cnn_conv2d_desc* d, const char* name, const DwRows& p, int
 template <int S>
 int launch_wgrad3(const cnn_conv2d_desc* d, const char* name, const DwWgrad& p, int off, dim3 grid, hipStream_t s) {
     switch (off) {
-        case 0: CNN_KLAUNCH(s, name, (dw3_wgrad<S, 0><<<grid, kDwBlock, 0, s>>>(p)), CONV_TAG(d)); break;
-        case 1: CNN_KLAUNCH(s, name, (dw3_wgrad<S, 1><<<grid, kDwBlock, 0, s>>>(p)), CONV_TAG(d)); break;
-        case 2: CNN_KLAUNCH(s, name, (dw3_wgrad<S, 2><<<grid, kDwBlock, 0, s>>>(p)), CONV_TAG(d)); break;
-        default: CNN_KLAUNCH(s, name, (dw3_wgrad<S, -1><<<grid, kDwBlock, 0, s>>>(p)), CONV_TAG(d)); break;
+        case 0: CNN_KLAUNCH(s, name, (dw3_wgrad<S, 0><<<grid, kDwBlock, 0, s>>>(p)), DW_TAG(d, "off", off, p.vdy)); break;
+        case 1: CNN_KLAUNCH(s, name, (dw3_wgrad<S, 1><<<grid, kDwBlock, 0, s>>>(p)), DW_TAG(d, "off", off, p.vdy)); break;
+        case 2: CNN_KLAUNCH(s, name, (dw3_wgrad<S, 2><<<grid, kDwBlock, 0, s>>>(p)), DW_TAG(d, "off", off, p.vdy)); break;
+        default: CNN_KLAUNCH(s, name, (dw3_wgrad<S, -1><<<grid, kDwBlock, 0, s>>>(p)), DW_TAG(d, "off", off, p.vdy)); break;
     }
     return CNN_AMD_OK;
 }
@@ -474,8 +478,8 @@ int dw_run(const cnn_conv2d_desc* d, int mode, const float* in, const float* w, 
         p.items = planes * (unsigned)p.ntile * (unsigned)p.nstrip;
         p.vst = vst ? 1 : 0;
         const unsigned grid = (p.items + kDwBlock - 1) / kDwBlock;
-        if (d->pad & 1) CNN_KLAUNCH(s, "dw_dgrad<3x3,s2>", (dw3_dgrad_s2<1><<<grid, kDwBlock, 0, s>>>(p)), CONV_TAG(d));
-        else CNN_KLAUNCH(s, "dw_dgrad<3x3,s2>", (dw3_dgrad_s2<0><<<grid, kDwBlock, 0, s>>>(p)), CONV_TAG(d));
+        if (d->pad & 1) CNN_KLAUNCH(s, "dw_dgrad<3x3,s2>", (dw3_dgrad_s2<1><<<grid, kDwBlock, 0, s>>>(p)), DW_TAG(d, "pp", 1, p.vst));
+        else CNN_KLAUNCH(s, "dw_dgrad<3x3,s2>", (dw3_dgrad_s2<0><<<grid, kDwBlock, 0, s>>>(p)), DW_TAG(d, "pp", 0, p.vst));
         return CNN_AMD_OK;
     }
     DwAny p;

@@ -6,8 +6,10 @@
 #pragma once
 #include "common.h"
 
-// printf-style geometry tag of a launch (CNN_KLAUNCH's trailing arguments)
-#define CONV_TAG(d) "B%d Ci%d %dx%d Co%d k%d s%d p%d", (d)->B, (d)->Ci, (d)->H, (d)->W, (d)->Co, (d)->k, (d)->s, (d)->pad
+// printf-style geometry tag of a launch (CNN_KLAUNCH's trailing arguments); format and arguments apart for a family that appends to it
+#define CONV_TAG_FMT "B%d Ci%d %dx%d Co%d k%d s%d p%d"
+#define CONV_TAG_ARGS(d) (d)->B, (d)->Ci, (d)->H, (d)->W, (d)->Co, (d)->k, (d)->s, (d)->pad
+#define CONV_TAG(d) CONV_TAG_FMT, CONV_TAG_ARGS(d)
 
 namespace cnn_amd {
 

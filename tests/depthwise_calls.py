@@ -1,6 +1,6 @@
 """The depthwise calls of the C ABI on guarded buffers (tests/guarded.py), for tests/test_gpu_depthwise.py and
 tests/test_gpu_stream_order_depthwise.py: every operand and output lies between NaN guard bands, the workspace is NaN-filled scratch of
-exactly the size the query names, and shift_bytes moves x, dy and w off every 16-byte boundary."""
+exactly the size the query names, and shift_bytes moves x, dy and w off every 16-byte boundary (`shifts`: every operand group by itself)."""
 import ctypes as C
 
 import numpy as np
@@ -11,7 +11,9 @@ from tests import guarded
 class Layer:
     """one case (B, C, H, W, k, s, pad) with its operands (x, w [C][1][k][k], b, dy, relu_below as host arrays) on the device"""
 
-    def __init__(self, T, case, ins, shift_bytes=0, guard_outputs=True):
+    def __init__(self, T, case, ins, shift_bytes=0, guard_outputs=True, shifts=None):
+        """shifts: bytes off the 256-byte boundary per operand group, {"x", "dy", "w", "below", "out"} (out: every output tensor);
+        missing groups, and shifts=None, follow shift_bytes: x, dy and w moved by it, relu_below and the outputs on the boundary"""
         from cnn_amd import capi
 
         B, Cn, H, W, k, s, pad = case
@@ -19,9 +21,12 @@ class Layer:
         self.desc = capi.ConvDesc(B, Cn, H, W, Cn, k, s, pad, capi.DEPTHWISE)
         self.Ho, self.Wo = capi.conv_out_dim(H, k, s, pad), capi.conv_out_dim(W, k, s, pad)
         x, w, b, dy, below = ins
-        op = lambda a, name, sh: guarded.operand(np.array(a), keep=self.keep, name=name, shift_bytes=sh)
-        self.x, self.w, self.dy = op(x, "x", shift_bytes), op(w, "w", shift_bytes), op(dy, "dy", shift_bytes)
-        self.b, self.below = op(b, "bias", 0), op(below, "relu_below", 0)
+        sh = dict({"x": shift_bytes, "dy": shift_bytes, "w": shift_bytes, "below": 0, "out": 0}, **(shifts or {}))
+        assert set(sh) == {"x", "dy", "w", "below", "out"} and (guard_outputs or sh["out"] == 0), sh
+        self.shifts = sh
+        op = lambda a, name, by: guarded.operand(np.array(a), keep=self.keep, name=name, shift_bytes=by)
+        self.x, self.w, self.dy = op(x, "x", sh["x"]), op(w, "w", sh["w"]), op(dy, "dy", sh["dy"])
+        self.b, self.below = op(b, "bias", 0), op(below, "relu_below", sh["below"])
         self.ws_bytes = int(self.lib.cnn_conv2d_workspace_bytes(C.byref(self.desc)))
         self.bws_bytes = int(self.lib.cnn_conv2d_backward_workspace_bytes(C.byref(self.desc)))
         assert 0 < self.ws_bytes <= self.bws_bytes, self.lib.cnn_amd_last_error().decode()
@@ -37,7 +42,7 @@ class Layer:
     def _out(self, shape, name):
         if not self.guard_outputs:  # (the stream-order harness: a guarded output is a fresh 128 KiB+ allocation, which waits for the gate)
             return self.T.full(shape, 7.0, dtype=self.T.float32, device="cuda")
-        return guarded.output(shape, keep=self.keep, name=name)
+        return guarded.output(shape, keep=self.keep, name=name, shift_bytes=self.shifts["out"])
 
     def _d(self):
         return C.byref(self.desc)
@@ -116,8 +121,9 @@ class Layer:
         return {"gw": gw, "gb": gb, "dx": dx}
 
 
-def logged(T, fn):
-    """fn() with the kernel-timing report on -> (its result, [kernel names in first-launch order])"""
+def logged(T, fn, keys=False):
+    """fn() with the kernel-timing report on -> (its result, [kernel names in first-launch order]); keys=True: the whole keys
+    "name|geometry tag" instead of the names"""
     from cnn_amd import capi
 
     T.cuda.synchronize()
@@ -125,7 +131,7 @@ def logged(T, fn):
     try:
         out = fn()
         T.cuda.synchronize()
-        names = [k.split("|")[0] for k in capi.kernel_timing_report()]
+        names = [k if keys else k.split("|")[0] for k in capi.kernel_timing_report()]
     finally:
         capi.kernel_timing(0)
     return out, names

@@ -21,9 +21,85 @@ K3_S2 = [(2, 5, 9, 9, 3, 2, 1),
          (2, 4, 10, 13, 3, 2, 0),     # even H: the last row is covered by no window and must come out +0
          (3, 33, 14, 14, 3, 2, 1), (2, 3, 56, 31, 3, 2, 1), (1, 2, 129, 66, 3, 2, 0)]
 GENERIC = [(2, 3, 11, 12, 5, 1, 2), (2, 3, 13, 11, 5, 2, 0), (1, 2, 15, 9, 7, 2, 3), (2, 4, 6, 6, 1, 1, 0), (2, 3, 9, 9, 3, 3, 0)]
-CASES = K3_S1 + K3_S2 + GENERIC
+# Widths that are multiples of 4 and pads 0..4: with SHIFT_ROWS these reach every (kernel, stride, OFF / PP, vector flag) the 3x3 launches
+# can choose (variants(), below; tests/test_depthwise_reference.py proves it) -- the lists above, all of odd widths, reach 9 of the 34.
+VARIANT_S1 = [(2, 3, 8, 8, 3, 1, 1),
+              (2, 40, 4, 4, 3, 1, 1),      # one strip, many planes per wave
+              (2, 5, 20, 28, 3, 1, 1),     # three row tiles, seven strips
+              (2, 3, 6, 12, 3, 1, 0),      # OFF 0
+              (2, 3, 10, 10, 3, 1, 0),     # data gradient OFF 2 (Wo = 8); forward float4 stores behind scalar loads
+              (2, 2, 7, 16, 3, 1, 2),      # OFF 2 forward
+              (2, 3, 5, 6, 3, 1, 2),       # data gradient OFF 0 (Wo = 8)
+              (1, 2, 5, 8, 3, 1, 3),       # OFF -1 by padding; the data gradient's pad' = -1
+              (1, 2, 6, 12, 3, 1, 4)]      # pad' = -2
+VARIANT_S2 = [(2, 3, 8, 8, 3, 2, 1), (2, 5, 20, 28, 3, 2, 1),
+              (2, 3, 9, 12, 3, 2, 1),      # Wo = 6: float4 loads, scalar stores
+              (2, 3, 9, 16, 3, 2, 0), (2, 3, 11, 9, 3, 2, 0), (2, 2, 7, 16, 3, 2, 2), (1, 2, 9, 8, 3, 2, 3), (2, 33, 4, 4, 3, 2, 1),
+              (2, 3, 7, 11, 3, 2, 1)]
+VARIANT_CASES = VARIANT_S1 + VARIANT_S2
+ODD_WIDTH_CASES = K3_S1 + K3_S2 + GENERIC  # (run at SHIFTS_BOTH: everything aligned, and x / dy / w shifted by 4)
+CASES = ODD_WIDTH_CASES + VARIANT_CASES
 NARROW_CASES = [K3_S1[0], K3_S2[0]]  # one per stride on exact.NARROW
+VARIANT_NARROW_CASES = [VARIANT_S1[2], VARIANT_S2[1]]
 LARGEST = [K3_S1[5], K3_S2[4]]       # the planner-branch cases (by elements)
+
+# byte shifts off the 256-byte boundary of (x and w, dy, the outputs, relu_below): each operand group alone, pairs, and 8 (off 16 bytes too)
+SHIFT_ROWS = [(0, 0, 0, 0), (4, 4, 0, 0), (0, 0, 4, 0), (0, 0, 0, 4), (4, 0, 0, 0), (0, 4, 0, 0), (8, 8, 8, 8)]
+SHIFTS_BOTH = [(0, 0, 0, 0), (4, 4, 0, 0)]
+CALLS = ("forward", "forward_relu", "forward_relu/only", "backward_data", "backward_data_relu", "backward_weight")
+
+
+def shifts_of(row):
+    """a SHIFT_ROWS row -> the shift of every operand group of tests/depthwise_calls.Layer"""
+    xw, dy, out, below = row
+    return {"x": xw, "w": xw, "dy": dy, "out": out, "below": below}
+
+
+def shift_key(row):
+    return "shift" + "-".join(str(v) for v in row)
+
+
+# ---- which code bodies a 3x3 launch chooses (conv_depthwise.hip: dw_off, vst, vdy), restated ----------------------------------------
+def dw_off(aligned, IW, pad):
+    """OFF of dw_load_row for rows of IW floats: -1 (scalar loads) unless the base is 16-byte aligned and IW % 4 == 0; then pad mod 4
+    where that is at most 2"""
+    if not aligned or IW % 4 != 0:
+        return -1
+    off = ((pad % 4) + 4) % 4
+    return off if off <= 2 else -1
+
+
+def launch_variants(case, shifts):
+    """call (CALLS) -> (kernel, S, OFF or PP, v) of the specialised kernel the call launches: the kernel's family ("dw_fwd", "dw_dgrad",
+    "dw_wgrad"), its stride, OFF of its row loads (PP = pad & 1 for the stride-2 data gradient) and whether it moves its outputs (the weight
+    gradient: its dy) as float4.  Empty for a geometry of the generic kernels.  Every tensor starts on a 256-byte boundary plus its shift and
+    planes are whole numbers of rows, so a tensor is 16-byte aligned iff its shift % 16 == 0."""
+    B, C, H, W, k, s, pad, Ho, Wo = geometry(case)
+    if k != 3 or s not in (1, 2):
+        return {}
+    al = {name: sh % 16 == 0 for name, sh in shifts.items()}
+    fwd = ("dw_fwd", s, dw_off(al["x"], W, pad), int(Wo % 4 == 0 and al["out"]))
+    out = {"forward": fwd, "forward_relu": fwd, "forward_relu/only": fwd}
+    for call, below_ok in (("backward_data", True), ("backward_data_relu", al["below"])):
+        v = int(W % 4 == 0 and al["out"] and below_ok)
+        out[call] = ("dw_dgrad", s, dw_off(al["dy"], Wo, 2 - pad) if s == 1 else pad & 1, v)
+    out["backward_weight"] = ("dw_wgrad", s, dw_off(al["x"], W, pad), int(Wo % 4 == 0 and al["dy"]))
+    return out
+
+
+def variants(case, shifts):
+    """the set of (kernel, S, OFF or PP, v) the three passes of one case launch"""
+    return set(launch_variants(case, shifts).values())
+
+
+def tag_variant(kernel_key):
+    """a kernel-timing key "dw_fwd<3x3,s2>|B2 ... p1 off1 v0" -> ("dw_fwd", 2, 1, 0); None for a key without the suffix"""
+    import re
+
+    m = re.fullmatch(r"(dw_\w+)<3x3,s([12])>\|.* (off|pp)(-?\d+) v([01])", kernel_key)
+    if not m or (m.group(3) == "pp") != (m.group(1) == "dw_dgrad" and m.group(2) == "2"):  # (pp: the stride-2 data gradient, and only it)
+        return None
+    return (m.group(1), int(m.group(2)), int(m.group(4)), int(m.group(5)))
 
 
 def key(case):

@@ -5,7 +5,12 @@ masked dx, gw and gb), the suite's tolerance against the C oracle on block-diago
 (the dw_* names of the kernel-timing report: the specialised 3x3 kernels for k = 3 and stride 1 / 2, the generic ones otherwise, never
 a dense family), the slab planner's branches (CUS), cnn_conv2d_backward with both defer_join values and the weight gradient on the
 side stream, and that a depthwise call leaves the routes and results of flag-free descs in the same process alone.  Every case runs
-once more with x, dy and w moved off every 16-byte boundary (the scalar-load bodies of the same kernels)."""
+once more with x, dy and w moved off every 16-byte boundary (the scalar-load bodies of the same kernels).
+
+Which body ran: a 3x3 launch picks its row loads (dw_load_row<NW, OFF>, OFF in {0, 1, 2, -1}; PP for the stride-2 data gradient) and
+float4 or scalar stores / mask reads / dy loads from widths, padding and pointer alignment, and says so behind the geometry tag of its
+kernel-timing key.  depthwise_ref.VARIANT_CASES x SHIFT_ROWS launch all 34 reachable combinations (proven on the CPU in
+tests/test_depthwise_reference.py); every launch here must carry the variant depthwise_ref.launch_variants names for it."""
 import numpy as np
 import pytest
 
@@ -59,14 +64,23 @@ def _expected_kernels(case, call):
 
 
 def _hold_exact(T, case, lattice, divisor, shift_bytes, calls=None, check_kernels=True):
+    """shift_bytes: one number (x, dy and w moved by it) or a row of depthwise_ref.SHIFT_ROWS"""
     (x, w, b, dy, below), truth = D.lattice_case(case, lattice)
-    L = DC.Layer(T, case, (x, w, b, dy, below), shift_bytes)
+    row = shift_bytes if isinstance(shift_bytes, tuple) else (shift_bytes, shift_bytes, 0, 0)
+    L = DC.Layer(T, case, (x, w, b, dy, below), shifts=D.shifts_of(row))
     want = _want_lattice(truth, below, divisor)
+    model = D.launch_variants(case, L.shifts)
     wrong = []
     for name, fn in (calls(L) if calls else _all_calls(L, divisor)).items():
-        out, names = DC.logged(T, fn)
+        out, keys = DC.logged(T, fn, keys=True)
+        names = [k.split("|")[0] for k in keys]
         if check_kernels and names != _expected_kernels(case, name):
             wrong.append(f"{name}: launched {names}, expected {_expected_kernels(case, name)}")
+        for k in keys:  # the body the launch chose is the one the model names (for this call where it is one of D.CALLS)
+            if model and k.startswith("dw_"):
+                got = D.tag_variant(k)
+                if got is None or (got != model[name] if name in model else got not in set(model.values())):
+                    wrong.append(f"{name}: {k} is variant {got}, the model says {model.get(name, sorted(set(model.values())))}")
         if any(d in n for n in names for d in DENSE_NAMES):
             wrong.append(f"{name}: a dense family ran: {names}")
         for o, t in sorted(out.items()):
@@ -78,7 +92,7 @@ def _hold_exact(T, case, lattice, divisor, shift_bytes, calls=None, check_kernel
 
 
 def _runs():
-    return [(c, X.WIDE) for c in D.CASES] + [(c, X.NARROW) for c in D.NARROW_CASES]
+    return [(c, X.WIDE) for c in D.ODD_WIDTH_CASES] + [(c, X.NARROW) for c in D.NARROW_CASES]
 
 
 @pytest.mark.parametrize("shift_bytes", [0, 4], ids=["aligned", "shift4"])
@@ -88,7 +102,21 @@ def test_every_pass_is_exact_and_runs_its_kernel(T, case, lattice, shift_bytes):
     _hold_exact(T, case, lattice, 4.0, shift_bytes)
 
 
-@pytest.mark.parametrize("case", [D.K3_S1[2], D.K3_S2[2], D.GENERIC[0]], ids=D.key)
+@pytest.mark.parametrize("row", D.SHIFT_ROWS, ids=D.shift_key)
+@pytest.mark.parametrize("case", D.VARIANT_CASES, ids=D.key)
+def test_every_load_and_store_variant_is_exact_and_is_the_one_the_model_names(T, case, row):
+    """widths that are multiples of 4, pads 0..4 and every operand group on and off the 16-byte boundary: the float4 bodies of the row
+    loads, the stores, the mask read and the dy load, bit for bit in every pass, each launch tagged with the variant the model names"""
+    _hold_exact(T, case, X.WIDE, 4.0, row)
+
+
+@pytest.mark.parametrize("row", D.SHIFTS_BOTH, ids=D.shift_key)
+@pytest.mark.parametrize("case", D.VARIANT_NARROW_CASES, ids=D.key)
+def test_float4_bodies_are_exact_on_the_narrow_lattice(T, case, row):
+    _hold_exact(T, case, X.NARROW, 4.0, row)
+
+
+@pytest.mark.parametrize("case", [D.K3_S1[2], D.K3_S2[2], D.GENERIC[0], D.VARIANT_S1[2], D.VARIANT_S2[0]], ids=D.key)
 def test_weight_gradient_is_the_rounded_quotient(T, case):
     """divisor 3: the correctly rounded quotient of the exact sum, which sum * (1 / 3) or a division per slab does not give"""
     _hold_exact(T, case, X.WIDE, 3.0, 0, calls=lambda L: {"backward_weight": lambda: L.backward_weight(3.0)})
@@ -136,10 +164,11 @@ def test_largest_cases_give_the_same_bits_at_other_cu_counts(T, lib_option, case
 
 
 @pytest.mark.parametrize("cus,slabs", [("1", 2), ("2", 3), (None, 6)])
-@pytest.mark.parametrize("case", [(6, 3, 9, 9, 3, 1, 1), (6, 3, 11, 12, 5, 1, 2)], ids=D.key)
+@pytest.mark.parametrize("case", [(6, 3, 9, 9, 3, 1, 1), (6, 3, 11, 12, 5, 1, 2), (6, 3, 8, 8, 3, 1, 1)], ids=D.key)
 def test_slab_planner_branches_give_the_same_bits(T, lib_option, case, cus, slabs):
     """six samples of three channels: the planner (four workgroups per compute unit over the channels) makes two slabs of three samples
-    at CUS=1, three of two at CUS=2 and one per sample on the whole card -- seen in the workspace size -- and the bits do not move"""
+    at CUS=1, three of two at CUS=2 and one per sample on the whole card -- seen in the workspace size -- and the bits do not move
+    (9x9: the scalar bodies of dw3_wgrad, 8x8: its float4 row and dy loads)"""
     import ctypes as C
 
     from cnn_amd import capi
@@ -152,7 +181,7 @@ def test_slab_planner_branches_give_the_same_bits(T, lib_option, case, cus, slab
                                                           "backward_weight/3": lambda: L.backward_weight(4.0)})
 
 
-@pytest.mark.parametrize("case", [D.K3_S1[3], D.K3_S2[2], D.GENERIC[1]], ids=D.key)
+@pytest.mark.parametrize("case", [D.K3_S1[3], D.K3_S2[2], D.GENERIC[1], D.VARIANT_S1[2]], ids=D.key)
 def test_backward_in_one_call_equals_the_separate_calls(T, case):
     """cnn_conv2d_backward with defer_join 0 and 1 (join, then compare) and cnn_conv2d_backward_weight_side: the bits of the separate calls"""
     def calls(L):

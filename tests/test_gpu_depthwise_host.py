@@ -1,6 +1,8 @@
 """architectures::DepthwiseConv2D inside a Sequential (cnn_amd.hostapi.HostSequential) against the oracle's SeqNet on the expanded net.
 
-The net: conv(8,3,2,1) bn relu dwconv(3,1,1) bn relu conv(16,1,1,0) relu dwconv(3,2,1) relu pool(2,2) linear(3) on 3x33x29.  The
+The net: conv(8,3,2,1) bn relu dwconv(3,1,1) bn relu conv(16,1,1,0) relu dwconv(3,2,1) relu pool(2,2) linear(3) on 3x33x29, and the
+three steps once more on 3x32x32: there dw_layer_2 works on 8x16x16 and dw_layer_4 takes 16x16 to 8x8, so the layer's own buffers reach
+the 16-byte load / store bodies of the depthwise kernels (17x15 and 9x8 planes stay on the scalar ones).  The
 reference is oracle.pyoracle.SeqNet on tests/depthwise_ref.expand_spec (every dwconv as a dense convolution with block-diagonal
 filters), its parameters re-expanded from the net's before every step (the dense net's SGD step would fill the off-diagonal zeros), its
 gradients and parameters read back through diag_grads.  Batches of 5, 3 (a partial batch) and 5 again; logits, loss, every layer's
@@ -17,6 +19,7 @@ pytestmark = pytest.mark.gpu
 SPEC = [("conv", 8, 3, 2, 1), ("bn",), ("relu",), ("dwconv", 3, 1, 1), ("bn",), ("relu",), ("conv", 16, 1, 1, 0), ("relu",),
         ("dwconv", 3, 2, 1), ("relu",), ("pool", 2, 2), ("linear", 3)]
 IN_SHAPE = (3, 33, 29)
+ALIGNED_SHAPE = (3, 32, 32)
 BATCHES = (5, 3, 5)
 LR = 1e-2
 
@@ -29,17 +32,17 @@ def T():
     return torch
 
 
-def _net():
+def _net(in_shape=IN_SHAPE):
     from cnn_amd import hostapi, stacks
 
-    net = hostapi.HostSequential(SPEC, IN_SHAPE)
+    net = hostapi.HostSequential(SPEC, in_shape)
     p0 = stacks.he_init(net.layout, 4242)
     net.set_params(p0)
     return net, p0
 
 
-def _data(i, B):
-    x = util.uniform_pm1(8800 + i, (B,) + IN_SHAPE)
+def _data(i, B, in_shape=IN_SHAPE):
+    x = util.uniform_pm1(8800 + i, (B,) + in_shape)
     labels = ((np.arange(B) + i) % 3).astype(np.int32)
     return x, labels
 
@@ -47,27 +50,27 @@ def _data(i, B):
 _REF = {}
 
 
-def _reference():
-    """the three steps on the oracle, once: per step (logits, loss, gradients, parameters after the step, the activation of dw_layer_2),
-    all in the depthwise net's own layout"""
-    if not _REF:
+def _reference(in_shape=IN_SHAPE):
+    """the three steps on the oracle, once per input shape: per step (logits, loss, gradients, parameters after the step, the activation
+    of dw_layer_2), all in the depthwise net's own layout"""
+    if in_shape not in _REF:
         from cnn_amd import stacks
         from oracle import pyoracle as O
 
-        layout = stacks.walk(SPEC, *IN_SHAPE)
-        ref = O.SeqNet(D.expand_spec(SPEC), IN_SHAPE)
+        layout = stacks.walk(SPEC, *in_shape)
+        ref = O.SeqNet(D.expand_spec(SPEC), in_shape)
         p = stacks.he_init(layout, 4242)
         steps = []
         for i, B in enumerate(BATCHES):
             ref.params[:] = D.expand_params(layout, p)
-            x, labels = _data(i, B)
+            x, labels = _data(i, B, in_shape)
             loss, _ = ref.train_step(x, labels, LR)
             g = D.diag_grads(layout, ref.grads)
             p_new = D.diag_grads(layout, ref.params)
             steps.append(dict(p_before=p, logits=ref.acts[-1].copy(), loss=float(loss), grads=g, params=p_new, dw2=ref.acts[3].copy()))
             p = p_new
-        _REF["steps"], _REF["layout"] = steps, layout
-    return _REF["steps"], _REF["layout"]
+        _REF[in_shape] = (steps, layout)
+    return _REF[in_shape]
 
 
 def _blocks(layout):
@@ -85,14 +88,15 @@ def _close_by_layer(names, layout, got, want, what):
         util.assert_close(got[a:b], want[a:b], util.REL_TOL, what=f"{what}: {name}")
 
 
-@pytest.mark.parametrize("driver", ["train_step", "forward_backward_update"])
-def test_three_steps_match_the_oracle_on_the_expanded_net(T, driver):
-    steps, layout = _reference()
-    net, _ = _net()
+def _three_steps(T, driver, in_shape):
+    steps, layout = _reference(in_shape)
+    net, _ = _net(in_shape)
+    dw2_shape = tuple(layout[3]["out"])
+    assert dw2_shape == {IN_SHAPE: (8, 17, 15), ALIGNED_SHAPE: (8, 16, 16)}[in_shape] and layout[3]["kind"] == "dwconv"
     try:
         assert net.names[3] == "dw_layer_2" and net.names[8] == "dw_layer_4" and net.n_params == sum(e["params"] for e in layout)
         for i, (B, want) in enumerate(zip(BATCHES, steps)):
-            x, labels = _data(i, B)
+            x, labels = _data(i, B, in_shape)
             xd, ld = T.from_numpy(x).cuda(), T.from_numpy(labels).cuda()
             if driver == "train_step":
                 net.train_step(xd, ld, LR)
@@ -105,9 +109,20 @@ def test_three_steps_match_the_oracle_on_the_expanded_net(T, driver):
             assert abs(net.last_loss() - want["loss"]) < 1e-4 * max(1.0, abs(want["loss"])), (what, net.last_loss(), want["loss"])
             _close_by_layer(net.names, layout, net.get_grads(), want["grads"], what + ": gradient")
             _close_by_layer(net.names, layout, net.get_params(), want["params"], what + ": parameters")
-            util.assert_close(net.layer_output("dw_layer_2", (B, 8, 17, 15)), want["dw2"], util.REL_TOL, what=what + ": dw_layer_2 output")
+            util.assert_close(net.layer_output("dw_layer_2", (B,) + dw2_shape), want["dw2"], util.REL_TOL, what=what + ": dw_layer_2 output")
     finally:
         net.close()
+
+
+@pytest.mark.parametrize("driver", ["train_step", "forward_backward_update"])
+def test_three_steps_match_the_oracle_on_the_expanded_net(T, driver):
+    _three_steps(T, driver, IN_SHAPE)
+
+
+@pytest.mark.parametrize("driver", ["train_step", "forward_backward_update"])
+def test_three_steps_match_the_oracle_on_planes_of_whole_float4_rows(T, driver):
+    """3x32x32: 16x16 and 8x8 depthwise planes in the net's own (256-byte aligned) buffers -- the float4 bodies inside a whole step"""
+    _three_steps(T, driver, ALIGNED_SHAPE)
 
 
 def test_checkpoint_round_trip(T, tmp_path):
