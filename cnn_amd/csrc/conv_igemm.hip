@@ -1198,19 +1198,25 @@ __global__ __launch_bounds__(256) void split_reduce(const float* __restrict__ pa
 
 // ---- host-side planning ------------------------------------------------------------------------------------
 struct Plan {
-    int cfg;  // which instantiation
+    int cfg;  // which tile (a row of kTiles)
     int MT, NPIX, CK, MF;
     IgemmParams p;
     PrepParams q;
     size_t lds_bytes;
     size_t a_floats;
     unsigned grid_x, grid_y;
-    int dma;  // double-buffered DMA-staged kernel
-    int xm;   // DMA kernel staging mode: 0 rows, 1 whole images, 2 whole images + masked taps
+    bool dma;  // double-buffered DMA-staged kernel
+    bool img;  // the tile has the whole-image staging instances
+    int xm;   // DMA kernel staging mode: 0 rows, 1 whole images, 2 whole images + masked taps, 3 whole images + masked taps + tap skipping
     int ksplit;        // > 1: split-K, partial tensors behind the filter image in the workspace (see IgemmParams::ksplit)
     size_t out_floats;  // floats of the output tensor (= one partial tensor)
+    // (split-K: the partial tensors start 256-byte aligned behind the filter image)
+    size_t part_offset() const { return (a_floats + 63) / 64 * 64; }
+    // floats of workspace the plan runs in
+    size_t ws_floats() const { return ksplit > 1 ? part_offset() + (size_t)ksplit * (size_t)p.zstride : a_floats; }
 };
 
+// The number of a tile is ABI: cnn_conv2d_tune_export / _import ship it, CNN_AMD_IGEMM_CFG takes it, kTuneCandidates names tiles by it.
 enum { CFG_M128_L = 100, CFG_M128 = 0, CFG_M128_S, CFG_M64, CFG_M64_S, CFG_M32, CFG_M32_S, CFG_M16_CK4, CFG_M16_CK16, CFG_M16_CK4_L, CFG_M16_CK8, CFG_M16_CK8_L, CFG_D_M128 = 200, CFG_D_M64, CFG_D_M64W4, CFG_D_M128W4, CFG_D_M128W4N2, CFG_D_M128W4_C4, CFG_D_M128_C4, CFG_D_M64W4_C4, CFG_D_M64W4N1_C4,
        CFG_D16_C4 /*209*/, CFG_D16_C4_L, CFG_D16_C16, CFG_D16_C16_L, CFG_D16_C8, CFG_D16_C8_L,
        CFG_D_M32 /*215*/, CFG_D_M32_C4, CFG_D_M64N1 /*217*/, CFG_D_M128S /*218*/, CFG_D_M128S_C4, CFG_D_M64S /*220*/, CFG_D_M64S_C4,
@@ -1219,6 +1225,64 @@ enum { CFG_M128_L = 100, CFG_M128 = 0, CFG_M128_S, CFG_M64, CFG_M64_S, CFG_M32, 
        CFG_W26_M128_N2_K2 /*230*/, CFG_W26_M128_N2_K4, CFG_W26_M128_N2_K8, CFG_W26_M64_N4_K2 /*233*/, CFG_W26_M64_N4_K4, CFG_W26_M64_N4_K8 /*235*/,
        CFG_M64_S_C16 = 20, CFG_M64_S_C32, CFG_M128_S_C16, CFG_M128_S_C32, CFG_M32_S_C16 /*24*/, CFG_M64_S_C4 /*25*/, CFG_M128_S_C4 /*26*/,
        CFG_M32_S_C4 /*27*/ };
+
+// Everything the host knows about a tile, once: make_plan, the staging choice and run_plan's dispatch read this table and nothing else.
+// dma: igemm_dma_kernel<MF, MA, NB, WM, WN, CK / k-step, XM> (double-buffered), else igemm_kernel<MF, MA, NB, WM, WN, CK>; CK: channels
+// per chunk; img: the whole-image staging instances (XM 1 .. 3) exist; Z: split-K ranges.  A new tile is an enum name and a row here
+// (and a kTuneCandidates entry if the tuner should try it).
+struct Tile {
+    int cfg;
+    bool dma;
+    int MF, MA, NB, WM, WN, CK;
+    bool img;
+    int Z;
+    constexpr int kstep() const { return MF == 32 ? Acc<32>::kStep : Acc<16>::kStep; }
+    constexpr int MT() const { return MF * MA * WM; }    // output rows per workgroup
+    constexpr int NPIX() const { return MF * NB * WN; }  // pixels per workgroup
+    constexpr int S() const { return CK / kstep(); }     // the DMA kernel's k-steps per tap
+};
+constexpr Tile kTiles[] = {
+    {CFG_M128, false, 32, 4, 1, 1, 4, 8, false, 1}, {CFG_M128_S, false, 32, 2, 1, 2, 2, 8, false, 1}, {CFG_M64, false, 32, 2, 2, 1, 4, 8, false, 1},
+    {CFG_M64_S, false, 32, 1, 1, 2, 2, 8, false, 1}, {CFG_M32, false, 32, 1, 4, 1, 4, 8, false, 1}, {CFG_M32_S, false, 32, 1, 1, 1, 4, 8, false, 1},
+    {CFG_M16_CK4, false, 16, 1, 4, 1, 4, 4, false, 1}, {CFG_M16_CK16, false, 16, 1, 4, 1, 4, 16, false, 1}, {CFG_M16_CK4_L, false, 16, 1, 8, 1, 4, 4, false, 1},
+    {CFG_M16_CK8, false, 16, 1, 4, 1, 4, 8, false, 1}, {CFG_M16_CK8_L, false, 16, 1, 8, 1, 4, 8, false, 1},
+    {CFG_M64_S_C16, false, 32, 1, 1, 2, 2, 16, false, 1}, {CFG_M64_S_C32, false, 32, 1, 1, 2, 2, 32, false, 1}, {CFG_M128_S_C16, false, 32, 2, 1, 2, 2, 16, false, 1},
+    {CFG_M128_S_C32, false, 32, 2, 1, 2, 2, 32, false, 1}, {CFG_M32_S_C16, false, 32, 1, 1, 1, 4, 16, false, 1}, {CFG_M64_S_C4, false, 32, 1, 1, 2, 2, 4, false, 1},
+    {CFG_M128_S_C4, false, 32, 2, 1, 2, 2, 4, false, 1}, {CFG_M32_S_C4, false, 32, 1, 1, 1, 4, 4, false, 1}, {CFG_M128_L, false, 32, 4, 2, 1, 4, 8, false, 1},
+    {CFG_D_M128, true, 32, 4, 1, 1, 8, 8, false, 1}, {CFG_D_M64, true, 32, 2, 1, 1, 8, 8, false, 1}, {CFG_D_M64W4, true, 32, 2, 2, 1, 4, 8, false, 1},
+    {CFG_D_M128W4, true, 32, 4, 1, 1, 4, 8, false, 1}, {CFG_D_M128W4N2, true, 32, 4, 2, 1, 4, 8, false, 1}, {CFG_D_M128W4_C4, true, 32, 4, 1, 1, 4, 4, false, 1},
+    {CFG_D_M128_C4, true, 32, 4, 1, 1, 8, 4, false, 1}, {CFG_D_M64W4_C4, true, 32, 2, 2, 1, 4, 4, false, 1}, {CFG_D_M64W4N1_C4, true, 32, 2, 1, 1, 4, 4, true, 1},
+    {CFG_D16_C4, true, 16, 1, 4, 1, 4, 4, false, 1}, {CFG_D16_C4_L, true, 16, 1, 8, 1, 4, 4, false, 1}, {CFG_D16_C16, true, 16, 1, 4, 1, 4, 16, false, 1},
+    {CFG_D16_C16_L, true, 16, 1, 8, 1, 4, 16, false, 1}, {CFG_D16_C8, true, 16, 1, 4, 1, 4, 8, false, 1}, {CFG_D16_C8_L, true, 16, 1, 8, 1, 4, 8, false, 1},
+    {CFG_D_M32, true, 32, 1, 1, 1, 4, 8, true, 1}, {CFG_D_M32_C4, true, 32, 1, 1, 1, 4, 4, true, 1}, {CFG_D_M64N1, true, 32, 2, 1, 1, 4, 8, false, 1},
+    {CFG_D_M128S, true, 32, 2, 1, 2, 2, 8, true, 1}, {CFG_D_M128S_C4, true, 32, 2, 1, 2, 2, 4, true, 1}, {CFG_D_M64S, true, 32, 1, 1, 2, 2, 8, true, 1},
+    {CFG_D_M64S_C4, true, 32, 1, 1, 2, 2, 4, true, 1}, {CFG_D_M32_C16, true, 32, 1, 1, 1, 4, 16, true, 1}, {CFG_D_M64S_C16, true, 32, 1, 1, 2, 2, 16, true, 1},
+    {CFG_D_M128S_C16, true, 32, 2, 1, 2, 2, 16, true, 1}, {CFG_D_M64W4N1_C16, true, 32, 2, 1, 1, 4, 16, true, 1}, {CFG_D_M64W4N1_C8, true, 32, 2, 1, 1, 4, 8, true, 1},
+    {CFG_D_M64N2W8, true, 32, 2, 2, 1, 8, 8, false, 1},
+    // (the wide tiles were measured with whole-image staging too: 14x14 k/4 192 vs 172 us, 7x7 k/8 193 vs 188 us -- rows stay)
+    {CFG_W26_M64_N4, true, 16, 2, 13, 2, 4, 8, false, 1}, {CFG_W26_M128_N2, true, 16, 2, 13, 4, 2, 8, false, 1},
+    {CFG_W26_M128_N2_K2, true, 16, 2, 13, 4, 2, 8, false, 2}, {CFG_W26_M128_N2_K4, true, 16, 2, 13, 4, 2, 8, false, 4}, {CFG_W26_M128_N2_K8, true, 16, 2, 13, 4, 2, 8, false, 8},
+    {CFG_W26_M64_N4_K2, true, 16, 2, 13, 2, 4, 8, false, 2}, {CFG_W26_M64_N4_K4, true, 16, 2, 13, 2, 4, 8, false, 4}, {CFG_W26_M64_N4_K8, true, 16, 2, 13, 2, 4, 8, false, 8}};
+constexpr int kNumTiles = (int)(sizeof(kTiles) / sizeof(kTiles[0]));
+constexpr const Tile* find_tile(int cfg) {
+    for (const Tile& t : kTiles)
+        if (t.cfg == cfg) return &t;
+    return nullptr;
+}
+template <class F>
+constexpr bool every_tile(F ok) {
+    for (const Tile& t : kTiles)
+        if (!ok(t)) return false;
+    return true;
+}
+static_assert(every_tile([](const Tile& t) { return find_tile(t.cfg) == &t; }), "kTiles: an id appears twice");
+static_assert(every_tile([](const Tile& t) { return t.Z >= 1 && t.CK % t.kstep() == 0; }), "kTiles: CK is no multiple of the MFMA's k-step");
+static_assert(every_tile([](const Tile& t) { return t.dma || (t.Z == 1 && !t.img); }), "kTiles: split-K and whole-image staging exist in the DMA kernel only");
+// the plan's tile facts from the row of `cfg` (every enum name has a row: tests/test_igemm_tile_list.py)
+void choose(Plan* pl, int cfg) {
+    const Tile& t = *find_tile(cfg);
+    pl->cfg = t.cfg; pl->MF = t.MF; pl->MT = t.MT(); pl->NPIX = t.NPIX(); pl->CK = t.CK; pl->dma = t.dma; pl->img = t.img;
+}
 
 // taps of dy one parity class reads: offsets d in [e - J + 1, e], e = (ph+pad)/s, J = #taps kx = kx0 + s*j < k
 void dgrad_window(int k, int s, int pad, int* r0, int* TR) {
@@ -1309,39 +1373,35 @@ int make_plan(const char* who, const cnn_conv2d_desc* d, int mode, Plan* pl, boo
     // (only when the large MFMA tiles below would leave CUs idle: a 28x28 layer at batch 128 is a big GEMM)
     const bool small_img = dma_ok && p.XH * p.XW <= 1024 && p.M > 32 && !CNN_OPT_SET("IGEMM_NOIMG") &&
                            !(p.M > 64 && blocks_for(128, 256) >= 2 * num_cus()) && !(p.M <= 64 && blocks_for(64, 128) >= 8 * num_cus());
-    if (small_img && p.M > 64 && mode == MODE_FWD) { pl->cfg = CFG_D_M64S; pl->MF = 32; pl->MT = 64; pl->NPIX = 64; pl->CK = 8; }
-    else if (small_img && p.M > 64 && p.C >= 128) { pl->cfg = CFG_D_M64S_C16; pl->MF = 32; pl->MT = 64; pl->NPIX = 64; pl->CK = 16; }
-    else if (small_img && p.M > 64) { pl->cfg = CFG_D_M32; pl->MF = 32; pl->MT = 32; pl->NPIX = 128; pl->CK = 8; }
-    else if (small_img && p.C >= 16) { pl->cfg = CFG_D_M64W4N1_C4; pl->MF = 32; pl->MT = 64; pl->NPIX = 128; pl->CK = 4; }
+    // (the blocks_for arguments are the candidate tile's MT x NPIX, written out: they are part of the rule)
+    if (small_img && p.M > 64 && mode == MODE_FWD) choose(pl, CFG_D_M64S);
+    else if (small_img && p.M > 64 && p.C >= 128) choose(pl, CFG_D_M64S_C16);
+    else if (small_img && p.M > 64) choose(pl, CFG_D_M32);
+    else if (small_img && p.C >= 16) choose(pl, CFG_D_M64W4N1_C4);
     else if (p.M > 64) {
-        pl->MF = 32; pl->MT = 128; pl->CK = 8;
-        if (allow_dma && blocks_for(128, 256) >= 2 * num_cus() && p.TR * p.TC <= 9 && p.N < (1ll << 31) - 1024) { pl->cfg = CFG_D_M128; pl->NPIX = 256; }
-        else if (blocks_for(128, 128) >= kWantBlocks) { pl->cfg = CFG_M128; pl->NPIX = 128; }
-        else if (dma_ok && unpadded && blocks_for(128, 64) >= num_cus() / 2) { pl->cfg = CFG_D_M128S; pl->NPIX = 64; }
-        else { pl->cfg = CFG_M128_S; pl->NPIX = 64; }
+        if (allow_dma && blocks_for(128, 256) >= 2 * num_cus() && p.TR * p.TC <= 9 && p.N < (1ll << 31) - 1024) choose(pl, CFG_D_M128);
+        else if (blocks_for(128, 128) >= kWantBlocks) choose(pl, CFG_M128);
+        else if (dma_ok && unpadded && blocks_for(128, 64) >= num_cus() / 2) choose(pl, CFG_D_M128S);
+        else choose(pl, CFG_M128_S);
     } else if (p.M > 32) {
-        pl->MF = 32; pl->MT = 64; pl->CK = 8;
-        if (allow_dma && blocks_for(64, 128) >= 4 * num_cus() && p.TR * p.TC <= 9 && p.N < (1ll << 31) - 1024 && p.C >= 16) {
-            pl->cfg = CFG_D_M64W4N1_C4; pl->NPIX = 128; pl->CK = 4;
-        } else if (blocks_for(64, 256) >= kWantBlocks) { pl->cfg = CFG_M64; pl->NPIX = 256; }
-        else { pl->cfg = CFG_M64_S; pl->NPIX = 64; }
+        if (allow_dma && blocks_for(64, 128) >= 4 * num_cus() && p.TR * p.TC <= 9 && p.N < (1ll << 31) - 1024 && p.C >= 16) choose(pl, CFG_D_M64W4N1_C4);
+        else if (blocks_for(64, 256) >= kWantBlocks) choose(pl, CFG_M64);
+        else choose(pl, CFG_M64_S);
     } else if (p.M > 16) {
-        pl->MF = 32; pl->MT = 32; pl->CK = 8;
-        if (dma_ok && unpadded && blocks_for(32, 128) >= kWantBlocks && blocks_for(32, 512) < 4 * kWantBlocks) {
-            pl->cfg = CFG_D_M32_C4; pl->NPIX = 128; pl->CK = 4;
-        } else if (blocks_for(32, 512) >= kWantBlocks) { pl->cfg = CFG_M32; pl->NPIX = 512; }
-        else { pl->cfg = CFG_M32_S; pl->NPIX = 128; }
-    } else if (p.C <= 4) { pl->cfg = CFG_M16_CK4; pl->MF = 16; pl->MT = 16; pl->NPIX = 256; pl->CK = 4; }
-    else if (allow_dma && p.N < (1ll << 31) - 1024 && p.TR * p.TC <= 9) { pl->cfg = CFG_D16_C4; pl->MF = 16; pl->MT = 16; pl->NPIX = 256; pl->CK = 4; }
-    else { pl->cfg = CFG_M16_CK16; pl->MF = 16; pl->MT = 16; pl->NPIX = 256; pl->CK = 16; }
+        if (dma_ok && unpadded && blocks_for(32, 128) >= kWantBlocks && blocks_for(32, 512) < 4 * kWantBlocks) choose(pl, CFG_D_M32_C4);
+        else if (blocks_for(32, 512) >= kWantBlocks) choose(pl, CFG_M32);
+        else choose(pl, CFG_M32_S);
+    } else if (p.C <= 4) choose(pl, CFG_M16_CK4);
+    else if (allow_dma && p.N < (1ll << 31) - 1024 && p.TR * p.TC <= 9) choose(pl, CFG_D16_C4);
+    else choose(pl, CFG_M16_CK16);
 
     // LDS fallback chain (large filters / wide rows): narrower pixel tile, then 4-channel chunks
     if (shrink >= 1) {
         const bool c4 = shrink >= 2;
-        if (p.M > 64) { pl->cfg = c4 ? CFG_M128_S_C4 : CFG_M128_S; pl->MF = 32; pl->MT = 128; pl->NPIX = 64; pl->CK = c4 ? 4 : 8; }
-        else if (p.M > 32) { pl->cfg = c4 ? CFG_M64_S_C4 : CFG_M64_S; pl->MF = 32; pl->MT = 64; pl->NPIX = 64; pl->CK = c4 ? 4 : 8; }
-        else if (p.M > 16) { pl->cfg = c4 ? CFG_M32_S_C4 : CFG_M32_S; pl->MF = 32; pl->MT = 32; pl->NPIX = 128; pl->CK = c4 ? 4 : 8; }
-        else { pl->cfg = CFG_M16_CK4; pl->MF = 16; pl->MT = 16; pl->NPIX = 256; pl->CK = 4; }
+        if (p.M > 64) choose(pl, c4 ? CFG_M128_S_C4 : CFG_M128_S);
+        else if (p.M > 32) choose(pl, c4 ? CFG_M64_S_C4 : CFG_M64_S);
+        else if (p.M > 16) choose(pl, c4 ? CFG_M32_S_C4 : CFG_M32_S);
+        else choose(pl, CFG_M16_CK4);
     }
     // overrides: CNN_AMD_IGEMM_CFG=<cfg id> (debug only) > the tuner's probe > the tuner's pinned choice for this geometry
     int override_cfg = -1;
@@ -1353,42 +1413,17 @@ int make_plan(const char* who, const cnn_conv2d_desc* d, int mode, Plan* pl, boo
         if (it != tune_table().end()) override_cfg = it->second;
     }
     const bool pinned = override_cfg >= 0;
-    if (pinned) {
-        const int c = override_cfg;
-        struct { int cfg, MF, MT, NPIX, CK, Z; } tab[] = {
-            {CFG_M128_L, 32, 128, 256, 8}, {CFG_M128, 32, 128, 128, 8}, {CFG_M128_S, 32, 128, 64, 8},
-            {CFG_M64, 32, 64, 256, 8}, {CFG_M64_S, 32, 64, 64, 8}, {CFG_M32, 32, 32, 512, 8}, {CFG_M32_S, 32, 32, 128, 8},
-            {CFG_M16_CK4, 16, 16, 256, 4}, {CFG_M16_CK16, 16, 16, 256, 16}, {CFG_M16_CK4_L, 16, 16, 512, 4},
-            {CFG_M16_CK8, 16, 16, 256, 8}, {CFG_M16_CK8_L, 16, 16, 512, 8},
-            {CFG_D_M128, 32, 128, 256, 8}, {CFG_D_M64, 32, 64, 256, 8}, {CFG_D_M64W4, 32, 64, 256, 8},
-            {CFG_D_M128W4, 32, 128, 128, 8}, {CFG_D_M128W4N2, 32, 128, 256, 8}, {CFG_D_M128W4_C4, 32, 128, 128, 4},
-            {CFG_D_M128_C4, 32, 128, 256, 4}, {CFG_D_M64W4_C4, 32, 64, 256, 4}, {CFG_D_M64W4N1_C4, 32, 64, 128, 4},
-            {CFG_D16_C4, 16, 16, 256, 4}, {CFG_D16_C4_L, 16, 16, 512, 4}, {CFG_D16_C16, 16, 16, 256, 16},
-            {CFG_D16_C16_L, 16, 16, 512, 16}, {CFG_D16_C8, 16, 16, 256, 8}, {CFG_D16_C8_L, 16, 16, 512, 8},
-            {CFG_D_M32, 32, 32, 128, 8}, {CFG_D_M32_C4, 32, 32, 128, 4}, {CFG_D_M64N1, 32, 64, 128, 8},
-            {CFG_D_M128S, 32, 128, 64, 8}, {CFG_D_M128S_C4, 32, 128, 64, 4}, {CFG_D_M64S, 32, 64, 64, 8}, {CFG_D_M64S_C4, 32, 64, 64, 4},
-            {CFG_D_M32_C16, 32, 32, 128, 16}, {CFG_D_M64S_C16, 32, 64, 64, 16}, {CFG_D_M128S_C16, 32, 128, 64, 16},
-            {CFG_D_M64W4N1_C16, 32, 64, 128, 16}, {CFG_D_M64W4N1_C8, 32, 64, 128, 8}, {CFG_D_M64N2W8, 32, 64, 512, 8},
-            {CFG_W26_M64_N4, 16, 64, 832, 8}, {CFG_W26_M128_N2, 16, 128, 416, 8},
-            {CFG_W26_M128_N2_K2, 16, 128, 416, 8, 2}, {CFG_W26_M128_N2_K4, 16, 128, 416, 8, 4}, {CFG_W26_M128_N2_K8, 16, 128, 416, 8, 8},
-            {CFG_W26_M64_N4_K2, 16, 64, 832, 8, 2}, {CFG_W26_M64_N4_K4, 16, 64, 832, 8, 4}, {CFG_W26_M64_N4_K8, 16, 64, 832, 8, 8},
-            {CFG_M64_S_C16, 32, 64, 64, 16}, {CFG_M64_S_C32, 32, 64, 64, 32}, {CFG_M128_S_C16, 32, 128, 64, 16},
-            {CFG_M128_S_C32, 32, 128, 64, 32}, {CFG_M32_S_C16, 32, 32, 128, 16}, {CFG_M64_S_C4, 32, 64, 64, 4},
-            {CFG_M128_S_C4, 32, 128, 64, 4}, {CFG_M32_S_C4, 32, 32, 128, 4}};
-        for (auto& t : tab)
-            if (t.cfg == c && p.M <= ((p.M + t.MT - 1) / t.MT) * t.MT && (t.MT >= 32 || p.M <= 16)) {
-                if (t.Z > 1) {
-                    // split-K tiles: only where the plain tile leaves CUs without a workgroup and the split fills about one round, every
-                    // range keeps >= 2 chunks, and the partial tensors stay small (they live in the caller's workspace / prepared buffer)
-                    const long long blocks = blocks_for(t.MT, t.NPIX), chunks = (p.C + t.CK - 1) / t.CK;
-                    const long long outf = mode == MODE_FWD ? p.N * p.M : (long long)p.B * d->Ci * d->H * d->W;
-                    if (!(blocks < num_cus() && blocks * t.Z <= num_cus() + num_cus() / 4 && blocks * t.Z > num_cus() / 2 && chunks >= 2 * t.Z &&
-                          outf * t.Z <= (64ll << 20) && dma_ok))
-                        continue;
-                    pl->ksplit = t.Z;
-                }
-                pl->cfg = t.cfg; pl->MF = t.MF; pl->MT = t.MT; pl->NPIX = t.NPIX; pl->CK = t.CK;
-            }
+    // (an id that is no row, or a 16-row tile where M > 16, leaves the rule-based choice in place)
+    if (const Tile* t = pinned ? find_tile(override_cfg) : nullptr; t != nullptr && (t->MT() >= 32 || p.M <= 16)) {
+        // split-K tiles: only where the plain tile leaves CUs without a workgroup and the split fills about one round, every
+        // range keeps >= 2 chunks, and the partial tensors stay small (they live in the caller's workspace / prepared buffer)
+        const long long blocks = blocks_for(t->MT(), t->NPIX()), chunks = (p.C + t->CK - 1) / t->CK;
+        const long long outf = mode == MODE_FWD ? p.N * p.M : (long long)p.B * d->Ci * d->H * d->W;
+        if (t->Z == 1 || (blocks < num_cus() && blocks * t->Z <= num_cus() + num_cus() / 4 && blocks * t->Z > num_cus() / 2 && chunks >= 2 * t->Z &&
+                          outf * t->Z <= (64ll << 20) && dma_ok)) {
+            pl->ksplit = t->Z;
+            choose(pl, t->cfg);
+        }
     }
     p.nchunk = (p.C + pl->CK - 1) / pl->CK;
     p.padL = p.c0 < 0 ? -p.c0 : 0;
@@ -1397,13 +1432,12 @@ int make_plan(const char* who, const cnn_conv2d_desc* d, int mode, Plan* pl, boo
     p.LW = p.padL + p.XW + padR;
     // DMA configurations on padded layers whose rows are 16-byte multiples: 4-float left pad, pitch a multiple of 4 floats -> the row
     // image is staged by 16-byte DMA instructions that span several rows (run_mode 3 of igemm_dma_kernel)
-    const bool dma_cfg = pl->cfg >= CFG_D_M128;
     // (round 3) rows that are NOT whole 16-byte units (the north-star data gradient: dy rows of 110 floats, pad 2) take the same
     // path: the last unit of a row then carries XW % 4 valid floats and up to three floats of whatever follows the row in memory,
     // which land in the right-pad columns -- the wave that issued the unit zeroes them again once its DMA has landed (the pad
     // columns must read as zeros).  IGEMM_RAGGED_ROWS=0: the old per-row 4-byte DMA for such layers.
     const bool ragged_ok = p.XW % 4 == 0 || CNN_OPT_INT("IGEMM_RAGGED_ROWS", 1) != 0;
-    const bool vecrows = dma_cfg && ragged_ok && p.XW >= 4 && p.padL > 0 && p.padL <= 4 && !((CNN_OPT_SET("IGEMM_NOVECROWS") && CNN_OPT_INT("IGEMM_NOVECROWS", 0) != 0));
+    const bool vecrows = pl->dma && ragged_ok && p.XW >= 4 && p.padL > 0 && p.padL <= 4 && !((CNN_OPT_SET("IGEMM_NOVECROWS") && CNN_OPT_INT("IGEMM_NOVECROWS", 0) != 0));
     if (vecrows) {
         p.padL = 4;
         p.LW = (4 + p.XW + padR + 3) & ~3;
@@ -1420,7 +1454,6 @@ int make_plan(const char* who, const cnn_conv2d_desc* d, int mode, Plan* pl, boo
         p.chs += ((want - p.chs % 32) + 32) % 32;
     }
     const int T = p.TR * p.TC;
-    pl->dma = pl->cfg >= CFG_D_M128;
     if (pl->dma) p.chs = (p.chs + 3) & ~3;  // 16-byte aligned buffers for the dwordx4 DMA
     pl->a_floats = (size_t)((p.M + pl->MT - 1) / pl->MT) * p.nchunk * T * pl->CK * pl->MT;
     pl->lds_bytes = ((size_t)T * pl->CK * pl->MT + (size_t)pl->CK * p.chs) * sizeof(float) * (pl->dma ? 2 : 1) +
@@ -1434,13 +1467,9 @@ int make_plan(const char* who, const cnn_conv2d_desc* d, int mode, Plan* pl, boo
         const int UVp = p.U * p.V;
         long long nimg = (pl->NPIX + UVp - 2) / UVp + 1;
         if (nimg > p.B) nimg = p.B;
-        const bool img_cfg = pl->cfg == CFG_D_M64W4N1_C4 || pl->cfg == CFG_D_M64W4N1_C8 || pl->cfg == CFG_D_M64W4N1_C16 ||
-                             pl->cfg == CFG_D_M32 || pl->cfg == CFG_D_M32_C4 || pl->cfg == CFG_D_M32_C16 ||
-                             pl->cfg == CFG_D_M128S || pl->cfg == CFG_D_M128S_C4 || pl->cfg == CFG_D_M128S_C16 ||
-                             pl->cfg == CFG_D_M64S || pl->cfg == CFG_D_M64S_C4 || pl->cfg == CFG_D_M64S_C16;  // (the wide tiles were measured with whole-image staging too: 14x14 k/4 192 vs 172 us, 7x7 k/8 193 vs 188 us -- rows stay)
         const OptVal xe = CNN_OPT_VAL("IGEMM_XM");
         const size_t lds = 2 * ((size_t)T * pl->CK * pl->MT + (size_t)nimg * pl->CK * HW) * sizeof(float);
-        if (img_cfg && HW <= 1024 && lds <= 160 * 1024 && (long long)p.B * p.C * HW < (1ll << 31) && !(xe && atoi(xe) == 0)) {
+        if (pl->img && HW <= 1024 && lds <= 160 * 1024 && (long long)p.B * p.C * HW < (1ll << 31) && !(xe && atoi(xe) == 0)) {
             pl->xm = p.need_zero ? 2 : 1;
             p.padL = 0;
             p.LW = p.XW;
@@ -1553,14 +1582,27 @@ int launch_cfg(const Plan& pl, hipStream_t s, const cnn_conv2d_desc* d) {
                          : launch_cfg2<MF, MA, NB, WM, WN, CK, false>(pl, s, d);
 }
 
+// row I of kTiles -> the launcher of its kernel (rows of one kernel share its launcher and the launcher's DeviceOnce)
+template <int I>
+int launch_row(const Plan& pl, hipStream_t s, const cnn_conv2d_desc* d) {
+    constexpr Tile t = kTiles[I];
+    if constexpr (t.dma) return launch_dma<t.MF, t.MA, t.NB, t.WM, t.WN, t.S(), t.img>(pl, s, d);
+    else return launch_cfg<t.MF, t.MA, t.NB, t.WM, t.WN, t.CK>(pl, s, d);
+}
+template <int... I>
+int launch_rows(const Plan& pl, hipStream_t s, const cnn_conv2d_desc* d, std::integer_sequence<int, I...>) {
+    int rc = CNN_AMD_OK;
+    if (((pl.cfg == kTiles[I].cfg && ((rc = launch_row<I>(pl, s, d)), true)) || ...)) return rc;
+    return fail(CNN_AMD_E_BADARG, "internal: cfg %d is no row of kTiles", pl.cfg);
+}
+int launch_tile(const Plan& pl, hipStream_t s, const cnn_conv2d_desc* d) { return launch_rows(pl, s, d, std::make_integer_sequence<int, kNumTiles>()); }
+
 // prepared: `ws` already holds the re-arranged filters (cnn_conv2d_prepare_filters); w is then unused
 int run_plan(Plan& pl, const cnn_conv2d_desc* d, const float* X, const float* w, const float* bias, float* Y, float* Y2,
              void* ws, size_t ws_bytes, hipStream_t s, const char* who, bool prepared = false) {
     CNN_REQUIRE(ws != nullptr, "%s: workspace is null", who);
-    const size_t a_al = (pl.a_floats + 63) / 64 * 64;  // (split-K: the partial tensors start 256-byte aligned behind the filter image)
-    const size_t need = pl.ksplit > 1 ? a_al + (size_t)pl.ksplit * (size_t)pl.p.zstride : pl.a_floats;
-    if (ws_bytes < need * sizeof(float))
-        return fail(CNN_AMD_E_WORKSPACE, "%s: workspace %zu B < %zu B", who, ws_bytes, need * sizeof(float));
+    if (ws_bytes < pl.ws_floats() * sizeof(float))
+        return fail(CNN_AMD_E_WORKSPACE, "%s: workspace %zu B < %zu B", who, ws_bytes, pl.ws_floats() * sizeof(float));
     if (!prepared) {
         pl.q.w = w;
         pl.q.A = (float*)ws;
@@ -1573,16 +1615,11 @@ int run_plan(Plan& pl, const cnn_conv2d_desc* d, const float* X, const float* w,
     pl.p.X = X; pl.p.A = (const float*)ws; pl.p.bias = bias; pl.p.Y = Y; pl.p.Y2 = Y2;
     if (pl.ksplit > 1) {
         // the ranges write partial tensors (plain epilogue), split_reduce adds them in range order and applies the fused epilogue
-        float* part = (float*)ws + a_al;
+        float* part = (float*)ws + pl.part_offset();
         CNN_REQUIRE(reinterpret_cast<uintptr_t>(part) % 16 == 0 && (Y == nullptr || reinterpret_cast<uintptr_t>(Y) % 16 == 0) &&
                         (Y2 == nullptr || reinterpret_cast<uintptr_t>(Y2) % 16 == 0), "%s: split-K needs 16-byte aligned tensors", who);
         pl.p.Y = part; pl.p.Y2 = nullptr;
-        int rc;
-        switch (pl.cfg) {
-            case CFG_W26_M128_N2_K2: case CFG_W26_M128_N2_K4: case CFG_W26_M128_N2_K8: rc = launch_dma<16, 2, 13, 4, 2, 2>(pl, s, d); break;
-            default: rc = launch_dma<16, 2, 13, 2, 4, 2>(pl, s, d); break;
-        }
-        if (rc) return rc;
+        if (int rc = launch_tile(pl, s, d)) return rc;
         const size_t n = pl.out_floats, n4 = n / 4;
         size_t g = (n4 + 255) / 256;
         if (g > 4096) g = 4096;
@@ -1591,58 +1628,7 @@ int run_plan(Plan& pl, const cnn_conv2d_desc* d, const float* X, const float* w,
                     (split_reduce<<<(unsigned)g, 256, 0, s>>>(part, pl.p.zstride, pl.ksplit, n4, n, Y, Y2, pl.p.mode)), CONV_TAG(d));
         return CNN_AMD_OK;
     }
-    switch (pl.cfg) {
-        case CFG_D_M128: return launch_dma<32, 4, 1, 1, 8, 4>(pl, s, d);
-        case CFG_D_M64: return launch_dma<32, 2, 1, 1, 8, 4>(pl, s, d);
-        case CFG_D_M64W4: return launch_dma<32, 2, 2, 1, 4, 4>(pl, s, d);
-        case CFG_D_M128W4: return launch_dma<32, 4, 1, 1, 4, 4>(pl, s, d);
-        case CFG_D_M128W4N2: return launch_dma<32, 4, 2, 1, 4, 4>(pl, s, d);
-        case CFG_D_M128W4_C4: return launch_dma<32, 4, 1, 1, 4, 2>(pl, s, d);
-        case CFG_D_M128_C4: return launch_dma<32, 4, 1, 1, 8, 2>(pl, s, d);
-        case CFG_D_M64W4_C4: return launch_dma<32, 2, 2, 1, 4, 2>(pl, s, d);
-        case CFG_D_M64W4N1_C4: return launch_dma<32, 2, 1, 1, 4, 2, true>(pl, s, d);
-        case CFG_D_M32: return launch_dma<32, 1, 1, 1, 4, 4, true>(pl, s, d);
-        case CFG_D_M32_C4: return launch_dma<32, 1, 1, 1, 4, 2, true>(pl, s, d);
-        case CFG_D_M64N1: return launch_dma<32, 2, 1, 1, 4, 4>(pl, s, d);
-        case CFG_D_M128S: return launch_dma<32, 2, 1, 2, 2, 4, true>(pl, s, d);
-        case CFG_D_M128S_C4: return launch_dma<32, 2, 1, 2, 2, 2, true>(pl, s, d);
-        case CFG_D_M64S: return launch_dma<32, 1, 1, 2, 2, 4, true>(pl, s, d);
-        case CFG_D_M64S_C4: return launch_dma<32, 1, 1, 2, 2, 2, true>(pl, s, d);
-        case CFG_D_M32_C16: return launch_dma<32, 1, 1, 1, 4, 8, true>(pl, s, d);
-        case CFG_D_M64S_C16: return launch_dma<32, 1, 1, 2, 2, 8, true>(pl, s, d);
-        case CFG_D_M128S_C16: return launch_dma<32, 2, 1, 2, 2, 8, true>(pl, s, d);
-        case CFG_D_M64W4N1_C16: return launch_dma<32, 2, 1, 1, 4, 8, true>(pl, s, d);
-        case CFG_D_M64W4N1_C8: return launch_dma<32, 2, 1, 1, 4, 4, true>(pl, s, d);
-        case CFG_D_M64N2W8: return launch_dma<32, 2, 2, 1, 8, 4>(pl, s, d);
-        case CFG_W26_M64_N4: case CFG_W26_M64_N4_K2: case CFG_W26_M64_N4_K4: case CFG_W26_M64_N4_K8: return launch_dma<16, 2, 13, 2, 4, 2>(pl, s, d);
-        case CFG_W26_M128_N2: case CFG_W26_M128_N2_K2: case CFG_W26_M128_N2_K4: case CFG_W26_M128_N2_K8: return launch_dma<16, 2, 13, 4, 2, 2>(pl, s, d);
-        case CFG_M64_S_C16: return launch_cfg<32, 1, 1, 2, 2, 16>(pl, s, d);
-        case CFG_M64_S_C32: return launch_cfg<32, 1, 1, 2, 2, 32>(pl, s, d);
-        case CFG_M128_S_C16: return launch_cfg<32, 2, 1, 2, 2, 16>(pl, s, d);
-        case CFG_M128_S_C32: return launch_cfg<32, 2, 1, 2, 2, 32>(pl, s, d);
-        case CFG_M32_S_C16: return launch_cfg<32, 1, 1, 1, 4, 16>(pl, s, d);
-        case CFG_M64_S_C4: return launch_cfg<32, 1, 1, 2, 2, 4>(pl, s, d);
-        case CFG_M128_S_C4: return launch_cfg<32, 2, 1, 2, 2, 4>(pl, s, d);
-        case CFG_M32_S_C4: return launch_cfg<32, 1, 1, 1, 4, 4>(pl, s, d);
-        case CFG_D16_C4: return launch_dma<16, 1, 4, 1, 4, 1>(pl, s, d);
-        case CFG_D16_C4_L: return launch_dma<16, 1, 8, 1, 4, 1>(pl, s, d);
-        case CFG_D16_C16: return launch_dma<16, 1, 4, 1, 4, 4>(pl, s, d);
-        case CFG_D16_C16_L: return launch_dma<16, 1, 8, 1, 4, 4>(pl, s, d);
-        case CFG_D16_C8: return launch_dma<16, 1, 4, 1, 4, 2>(pl, s, d);
-        case CFG_D16_C8_L: return launch_dma<16, 1, 8, 1, 4, 2>(pl, s, d);
-        case CFG_M128_L: return launch_cfg<32, 4, 2, 1, 4, 8>(pl, s, d);
-        case CFG_M128: return launch_cfg<32, 4, 1, 1, 4, 8>(pl, s, d);
-        case CFG_M128_S: return launch_cfg<32, 2, 1, 2, 2, 8>(pl, s, d);
-        case CFG_M64: return launch_cfg<32, 2, 2, 1, 4, 8>(pl, s, d);
-        case CFG_M64_S: return launch_cfg<32, 1, 1, 2, 2, 8>(pl, s, d);
-        case CFG_M32: return launch_cfg<32, 1, 4, 1, 4, 8>(pl, s, d);
-        case CFG_M32_S: return launch_cfg<32, 1, 1, 1, 4, 8>(pl, s, d);
-        case CFG_M16_CK4: return launch_cfg<16, 1, 4, 1, 4, 4>(pl, s, d);
-        case CFG_M16_CK4_L: return launch_cfg<16, 1, 8, 1, 4, 4>(pl, s, d);
-        case CFG_M16_CK8: return launch_cfg<16, 1, 4, 1, 4, 8>(pl, s, d);
-        case CFG_M16_CK8_L: return launch_cfg<16, 1, 8, 1, 4, 8>(pl, s, d);
-        default: return launch_cfg<16, 1, 4, 1, 4, 16>(pl, s, d);
-    }
+    return launch_tile(pl, s, d);
 }
 
 }  // namespace
@@ -1664,8 +1650,7 @@ size_t igemm_image_floats(const cnn_conv2d_desc* d, int mode) {
         const int rc = make_plan("ws", d, mode, &pl);
         g_forced_cfg = -1;
         if (rc != CNN_AMD_OK || (c >= 0 && pl.cfg != c)) continue;
-        const size_t need = pl.ksplit > 1 ? (pl.a_floats + 63) / 64 * 64 + (size_t)pl.ksplit * (size_t)pl.p.zstride : pl.a_floats;
-        if (need > n) n = need;
+        if (pl.ws_floats() > n) n = pl.ws_floats();
     }
     return n;
 }
@@ -1715,8 +1700,11 @@ static size_t autotune_scratch_floats(const cnn_conv2d_desc* d, size_t* nx, size
 // does cnn_conv2d_autotune measure anything for this geometry in this mode (the specialised kernels keep their layers; a geometry is
 // measured once per process)?
 static bool autotune_applies(const cnn_conv2d_desc* d, int mode) {
+    // geometries that never reach the implicit GEMM in this mode
     if (direct_conv_supported(d) || c11_supported(d)) return false;
     if (rows_workspace_floats(d, mode) > 0) return false;  // (conv_rows.hip has no tile to choose)
+    // register-direct kernels for BIG layers (stride-1 / stride-2 3x3, pad 0, Ci <= 64; stride-1 data gradient) are measured
+    // against the implicit GEMM by autotune_impl; the small-layer kernels, the first-layer kernels and the stem keep their layers
     const bool rd_fwd = mode == MODE_FWD && fwd_rd_supported(d);
     const bool rd_dgrad = mode == MODE_DGRAD && dgrad_rd_supported(d);
     if (rd_fwd && fwd_rd_small(d)) return false;
@@ -1743,26 +1731,12 @@ size_t cnn_conv2d_autotune_workspace_bytes(const cnn_conv2d_desc* d) {
 // scratch == NULL: buffers of the library's own for the duration of the call (the older entry point, cnn_conv2d_autotune)
 static int autotune_impl(const cnn_conv2d_desc* d, void* scratch, size_t scratch_bytes, void* stream) {
     if (int rc = check_desc("cnn_conv2d_autotune", d)) return rc;
-    if (const OptVal e = CNN_OPT_VAL("IGEMM_AUTOTUNE"))
-        if (atoi(e) == 0) return CNN_AMD_OK;
-    if (CNN_OPT_SET("IGEMM_CFG")) return CNN_AMD_OK;
+    if (!autotune_enabled()) return CNN_AMD_OK;
     hipStream_t s = as_stream(stream);
     for (int mode = 0; mode < 2; ++mode) {
-        // geometries that never reach the implicit GEMM in this mode
-        if (direct_conv_supported(d) || c11_supported(d)) continue;
-        if (rows_workspace_floats(d, mode) > 0) continue;  // (conv_rows.hip has no tile to choose)
-        // register-direct kernels for BIG layers (stride-1 / stride-2 3x3, pad 0, Ci <= 64; stride-1 data gradient) are measured
-        // against the implicit GEMM below; the small-layer kernels, the first-layer kernels and the stem keep their layers
+        if (!autotune_applies(d, mode)) continue;
         const bool rd_fwd = mode == MODE_FWD && fwd_rd_supported(d);
         const bool rd_dgrad = mode == MODE_DGRAD && dgrad_rd_supported(d);
-        if (rd_fwd && fwd_rd_small(d)) continue;
-        if (mode == MODE_FWD && !rd_fwd && stem_fwd_supported(d)) continue;
-        if (rd_dgrad && d->s != 1) continue;
-        if (mode == MODE_DGRAD && !rd_dgrad && (pk_dgrad_s2_supported(d) || thin_dgrad_supported(d))) continue;
-        {
-            std::lock_guard<std::mutex> lk(tune_mutex());
-            if (tune_table().count(tune_key(d, mode))) continue;
-        }
         size_t nx, ny, nw, na;
         const size_t total = autotune_scratch_floats(d, &nx, &ny, &nw, &na);
         float *bx = nullptr, *by = nullptr, *bw = nullptr, *ba = nullptr, *bb = nullptr;

@@ -4,7 +4,65 @@ cnn_conv2d_autotune times kTuneCandidates (cnn_amd/csrc/conv_igemm.hip) on all-z
 pass without looking at a result; cnn_conv2d_tune_import spreads the choice to every replica.  tests/test_gpu_igemm_tiles.py pins every
 candidate through the import call on every desc below and holds what it computes to the integer truth of tests/exact.py;
 tests/test_igemm_tile_list.py keeps this module in step with the source."""
+import os
 import re
+
+SOURCE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cnn_amd", "csrc", "conv_igemm.hip")
+TILE_FIELDS = ("dma", "MF", "MA", "NB", "WM", "WN", "CK", "img", "Z")
+
+
+def source_enum(src=None):
+    """{CFG_ name: number} of the tile enum in conv_igemm.hip"""
+    src = open(SOURCE).read() if src is None else src
+    enum = re.search(r"enum\s*\{\s*(CFG_M128_L\s*=.*?)\};", src, re.S).group(1)
+    enum = re.sub(r"/\*.*?\*/", "", enum)
+    value, ids = -1, {}
+    for item in enum.split(","):
+        item = item.strip()
+        if not item:
+            continue
+        if "=" in item:
+            item, v = (s.strip() for s in item.split("="))
+            value = int(v)
+        else:
+            value += 1
+        assert item not in ids, item
+        ids[item] = value
+    return ids
+
+
+def source_tiles(src=None):
+    """[(CFG_ name, {field: value})] of the rows of kTiles in conv_igemm.hip, in the table's order (duplicates kept)"""
+    src = open(SOURCE).read() if src is None else src
+    body = re.search(r"constexpr\s+Tile\s+kTiles\[\]\s*=\s*\{(.*?)\};", src, re.S).group(1)
+    body = re.sub(r"//[^\n]*", "", body)
+    rows = re.findall(r"\{([^{}]*)\}", body)
+    assert re.sub(r"\{[^{}]*\}|[\s,]", "", body) == "", "kTiles holds something that is no row"
+    out = []
+    for row in rows:
+        cells = [c.strip() for c in row.split(",")]
+        assert len(cells) == 1 + len(TILE_FIELDS), row
+        value = {"true": True, "false": False}
+        out.append((cells[0], {f: value[c] if c in value else int(c) for f, c in zip(TILE_FIELDS, cells[1:])}))
+    return out
+
+
+def source_table(src=None):
+    """{id: row} of kTiles"""
+    ids = source_enum(src)
+    return {ids[name]: row for name, row in source_tiles(src)}
+
+
+def kernel_of(row):
+    """the launch-log name of a row's kernel up to where the staging mode follows (the form of KERNEL below): igemm_dma_kernel<MF, MA, NB,
+    WM, WN, CK / k-step of the MFMA [, k/Z] or igemm_kernel<MF, MA, NB, WM, WN, CK> -- what launch_row in conv_igemm.hip instantiates"""
+    head = "%d,%d,%d,%d,%d," % tuple(row[f] for f in ("MF", "MA", "NB", "WM", "WN"))
+    if not row["dma"]:
+        return _LDS + head + "%d>" % row["CK"]
+    kstep = {32: 2, 16: 4}[row["MF"]]
+    assert row["CK"] % kstep == 0
+    return _DMA + head + "%d" % (row["CK"] // kstep) + (",k/%d" % row["Z"] if row["Z"] > 1 else "")
+
 
 # kTuneCandidates without -1 (the rule-based default)
 CANDIDATES = [200, 201, 206, 207, 208, 226, 222, 224, 215, 216, 219, 225, 0, 1, 22, 227, 202, 228, 229, 230, 231, 232, 233, 234, 235]
@@ -12,7 +70,7 @@ SPLIT = {230: 2, 231: 4, 232: 8, 233: 2, 234: 4, 235: 8}  # the wide tiles with 
 NONE = -2 ** 31  # CNN_TUNE_NONE (include/cnn_amd.h)
 
 _DMA, _LDS = "igemm_dma_kernel<", "igemm_kernel<"
-# the launch-log name of each tile up to where the staging mode follows, restated from the switch in run_plan
+# the launch-log name of each tile up to where the staging mode follows, restated from the rows of kTiles that run_plan dispatches over
 KERNEL = {
     200: _DMA + "32,4,1,1,8,4", 201: _DMA + "32,2,1,1,8,4", 202: _DMA + "32,2,2,1,4,4",
     206: _DMA + "32,4,1,1,8,2", 207: _DMA + "32,2,2,1,4,2", 208: _DMA + "32,2,1,1,4,2",

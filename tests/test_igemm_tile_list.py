@@ -48,31 +48,28 @@ def test_candidates_are_the_tuners():
     assert m and int(m.group(1)) - 1 == G.NONE
 
 
-def test_kernel_names_are_the_switchs():
-    """KERNEL[cfg] against the template arguments of the tile's case in run_plan's switch (the enum gives the number of each name)"""
+def test_kernel_names_are_the_tables():
+    """KERNEL[cfg] against the kernel and the six template arguments run_plan launches for the tile's row of kTiles (the enum gives the
+    number of each name), the ",k/Z" suffix from the row's Z; and the table has one row per enum value"""
     src = open(SOURCE).read()
-    enum = re.search(r"enum\s*\{\s*(CFG_M128_L\s*=.*?)\};", src, re.S).group(1)
-    enum = re.sub(r"/\*.*?\*/", "", enum)
-    value, ids = -1, {}
-    for item in enum.split(","):
-        item = item.strip()
-        if not item:
-            continue
-        if "=" in item:
-            item, v = (s.strip() for s in item.split("="))
-            value = int(v)
-        else:
-            value += 1
-        ids[item] = value
-    plain = src[src.index("    switch (pl.cfg) {\n        case CFG_D_M128:"):]
-    seen = {}
-    for labels, kind, args in re.findall(r"((?:case\s+CFG_\w+:\s*)+)return\s+(launch_dma|launch_cfg)<([^>]*)>", plain):
-        args = [a.strip() for a in args.split(",")]
-        for label in re.findall(r"CFG_\w+", labels):
-            seen[ids[label]] = ("igemm_dma_kernel<" if kind == "launch_dma" else "igemm_kernel<") + ",".join(args[:6])
+    ids, rows = G.source_enum(src), G.source_tiles(src)
+    assert len(set(ids.values())) == len(ids)
+    assert sorted(ids[name] for name, _ in rows) == sorted(ids.values()), "kTiles and the enum do not hold the same ids"
+    # how a row becomes a launch: the two launcher templates and their arguments, S from CK and the MFMA's k-step
+    flat = re.sub(r"\s+", " ", src)
+    assert "if constexpr (t.dma) return launch_dma<t.MF, t.MA, t.NB, t.WM, t.WN, t.S(), t.img>(pl, s, d);" in flat
+    assert "else return launch_cfg<t.MF, t.MA, t.NB, t.WM, t.WN, t.CK>(pl, s, d);" in flat
+    assert "constexpr int S() const { return CK / kstep(); }" in flat
+    assert "constexpr int kstep() const { return MF == 32 ? Acc<32>::kStep : Acc<16>::kStep; }" in flat
+    ksteps = re.findall(r"struct Acc<(\d+)> \{.*?static constexpr int kStep = (\d+);", src, re.S)
+    assert sorted(ksteps) == [("16", "4"), ("32", "2")]
+    assert "switch (pl.cfg)" not in src and "case CFG_" not in src
+    seen = G.source_table(src)
     for cfg in G.CANDIDATES:
-        want = seen[cfg] + (",k/%d" % G.SPLIT[cfg] if cfg in G.SPLIT else "") + (">" if seen[cfg].startswith("igemm_kernel<") else "")
-        assert G.KERNEL[cfg] == want, (cfg, G.KERNEL[cfg], want)
+        assert seen[cfg]["Z"] == G.SPLIT.get(cfg, 1), cfg
+        assert G.KERNEL[cfg] == G.kernel_of(seen[cfg]), (cfg, G.KERNEL[cfg], G.kernel_of(seen[cfg]))
+    for cfg, row in seen.items():  # (what the C++ static_asserts hold, for the rows the tuner does not try as well)
+        assert row["Z"] >= 1 and row["CK"] % {32: 2, 16: 4}[row["MF"]] == 0 and (row["dma"] or (row["Z"] == 1 and not row["img"])), cfg
 
 
 def test_names_resolve_to_one_tile():
